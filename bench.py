@@ -47,6 +47,23 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+DUMP_MAX_BYTES = 64 << 20            # --dump-outputs: at most 64 MB of .npy data per run
+
+
+def dump_outputs(out_dir, arrays, suffix=""):
+    """--dump-outputs: write what the timed path computed in its last step as out_dir/<name><suffix>.npy, float32.  An array that would take the
+    total past budget is replaced by a fixed, seeded sample of its flattened elements (<name>_sample<suffix>.npy, indices depend only on its size)."""
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_MAX_BYTES // max(1, int(os.environ.get("WORLD_SIZE", "1")))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float32)
+        if a.nbytes > left:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=left // 4, replace=False))
+            a, name = a.reshape(-1)[idx], name + "_sample"
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
+        left -= a.nbytes
+
+
 def usable_cores() -> int:
     """host cores this process may really use: affinity mask capped by the cgroup CPU quota"""
     n = len(os.sched_getaffinity(0))
@@ -170,6 +187,8 @@ def bench_vae_qu8(args):
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     assert np.isfinite(img).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"image": img})
     rows = m.hip_profile(args.profile_reps)
     conv = [(ms, fl) for ms, fl, by, what in rows if what.startswith(("Conv qu8", "MatMul qu8 "))]
     c_ms, c_fl = sum(r[0] for r in conv), sum(r[1] for r in conv)
@@ -242,7 +261,13 @@ def main():
                     "random-weight trajectories finite -- they stay finite without it, see config.latent_absmax)")
     ap.add_argument("--breakdown", default="", help="write the per-step HIP-event profile to this file")
     ap.add_argument("--windows", type=int, default=5, help="further one-image windows timed after the K steps (spread only: median / min / max in config.windows_ms_per_step; 0 = none)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step computed (latents; the decoded image when that step "
+                    "ended an image) as DIR/<name>.npy, float32, <= 64 MB in all; the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_outputs and args.mode == "replay" and args.config not in ("VAE_QU8", "VAE_QU8_TINY"):
+        ap.error("--dump-outputs: --mode replay relaunches the captured pass and hands no arrays back; use --mode pipeline")
     if args.config in ("VAE_QU8", "VAE_QU8_TINY"):
         return bench_vae_qu8(args)
 
@@ -441,6 +466,7 @@ def main():
                 dev += d1
                 if trace is not None:
                     trace.append(("loop", n, (tr0 - tr_in) * 1e3, (time.perf_counter() - tr0) * 1e3, d1))
+            state["step_x"] = x
             if i + n == STEPS_PER_IMAGE:
                 tr0 = time.perf_counter()
                 x = end_of_image(x)
@@ -492,6 +518,13 @@ def main():
     barrier()
     wall = time.perf_counter() - t0
     dev_ms = dev_acc / max(args.steps, 1)
+    if args.dump_outputs:
+        # what the K-th timed step handed back: its latents and, when it was the last step of an image, the decoded image (state["i"] wrapped to 0);
+        # copied now, before the windows below go on updating the latents in place
+        dumped = {"latents": np.array(state["step_x"], np.float32)}
+        if state["i"] == 0 and state["last"] is not None:
+            dumped["image"] = np.array(state["last"], np.float32)
+        dump_outputs(args.dump_outputs, dumped, suffix=f"_rank{rank}" if world > 1 else "")
     # ---- spread: `--windows` further windows of one image each (STEPS_PER_IMAGE steps + decode), timed the same way AFTER the contract's K steps.  They do
     # not enter `value` / `ms_per_step`; they show what a 2 % change looks like against the run-to-run spread of this box.
     images_timed = state["images"]
