@@ -15,6 +15,7 @@
 #include "osg_gemm_common.h"
 #include "osg_tune.h"
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -615,6 +616,7 @@ int run_gemm_v2(osg_ctx* ctx, GemmParams p, int batch, const V2Choice* forced) {
 
 template <bool CONV>
 int run_gemm(osg_ctx* ctx, GemmParams p, int batch, const V2Choice* forced = nullptr) {
+    if (epi_check(ctx, p)) return 1;
     {
         static const bool force_v1 = getenv("OSG_GEMM_V1") != nullptr;
         const bool shape_ok = p.K % 64 == 0 && (CONV ? p.Cin % 64 == 0 : p.lda % 8 == 0);
@@ -985,6 +987,7 @@ static int conv2d_v(osg_ctx* ctx, const W8Quant& q, const void* x, const void* w
     int Ho = (H + pt + pb - KH) / sh + 1;
     int Wo = (W + pl + pr - KW) / sw + 1;
     if (Ho <= 0 || Wo <= 0) OSG_FAIL(ctx, "osg_conv2d_nhwc: empty output");
+    if ((long)N * Ho * Wo > INT_MAX) OSG_FAIL(ctx, "osg_conv2d_nhwc: more than 2^31 - 1 output pixels");
     GemmParams p{};
     p.A = (const f16*)x; p.Bt = (const f16*)w; p.C = (f16*)y; p.bias = bias; p.residual = (const f16*)residual;
     p.M = N * Ho * Wo; p.N = Cout; p.K = KH * KW * Cin; p.lda = 0;
@@ -1007,6 +1010,7 @@ static int conv2d_v(osg_ctx* ctx, const W8Quant& q, const void* x, const void* w
     p.sink_hw = ctx->pending_hw;
     ctx->sink_fused = false;
     if (want_sinks && (p.sink_hw <= 0 || p.sink_hw != Ho * Wo)) OSG_FAIL(ctx, "osg_conv2d_nhwc_v: the statistics sinks were set for another image size");
+    if (epi_check(ctx, p)) return 1;
     const int rc = conv2d_route(ctx, p, N, Cin, Cout, KH, KW, sh, sw, pt, pl, pb, pr);
     if (rc || !want_sinks || ctx->sink_fused) return rc;
     return osg_mm::launch_colstats(ctx, p.C, p.ldc ? p.ldc : (long)Cout, p.M, Cout, p.sink_hw, p.sink);

@@ -4,6 +4,7 @@
 #include <vector>
 #include "osg_common.h"
 
+#include <algorithm>
 #include <type_traits>
 #ifndef OSG_EPI_STORE_AUX
 #define OSG_EPI_STORE_AUX 0     // < 0: plain pointer stores with exec masks (rounds 1-5); 0 / 16: buffer stores, plain / sc1 write-through (A/B builds: profiles/r06_epilogue_store_ab.txt)
@@ -71,6 +72,7 @@ struct GemmParams {
     int bias_f32, act;
     int no_epre;                 // OSG_NO_EPI_PREFETCH=1 (A/B): the epilogue fetches its operands on demand, as before round 3
     int rs_np;                   //   = N / 32
+    unsigned rb_bytes;           // byte extent of rowbias, ((images - 1) * rb_ld + N) * 2 (epi_check; the on-demand epilogue's descriptor)
     // the rest: epilogue / split-K
     f16* C;
     float* partial;
@@ -355,6 +357,37 @@ __device__ __forceinline__ void gemm_colstats(const GemmParams& p, const f16x4 (
     }
 }
 
+// ---- buffer descriptors of the epilogue's row operands (C, C2, residual), rebased at the workgroup tile's first row m0 --------------------------------------
+// A descriptor holds 32-bit byte offsets: based at the matrix itself, an output of 2 GiB or more lost every store past 2^31 (the old fixed extent) and one of
+// 4 GiB or more wrapped onto its first rows.  Based at row m0, a lane's offset is at most (BM - 1) * pitch * 2 + N * 2, which epi_check keeps below 2^31 on the
+// host; the extent is what is left of the matrix from m0 on, capped at kEpiOob -- the offset every dropped lane gets, out of range whatever the cap.
+constexpr unsigned kEpiOob = 0x80000000u;
+constexpr int kEpiMaxBM = 128;   // the tallest workgroup tile of every kernel that runs this epilogue (gemm_kernel, gemm2_kernel, conv3x3_kernel)
+__host__ __device__ inline unsigned epi_extent(int rows_left, long pitch, int N) {
+    const long bytes = ((long)(rows_left - 1) * pitch + N) * 2;
+    return bytes < (long)kEpiOob ? (unsigned)bytes : kEpiOob;
+}
+// host side, before any launch that ends in gemm_epilogue: fills rb_bytes; 1 (and ctx->err) when a pitch or the per-image bias is too large for 32-bit offsets
+inline int epi_check(osg_ctx* ctx, GemmParams& p) {
+    const long ldc = p.ldc ? p.ldc : (long)p.N;
+    const long pitch = std::max(std::max(ldc, p.C2 ? p.ldc2 : 0L), (long)p.N);
+    if ((long)kEpiMaxBM * pitch * 2 >= (long)kEpiOob) {
+        ctx->err = "contraction epilogue: an output row pitch of 8 Mi elements or more does not fit the 32-bit store offsets of a 128-row tile";
+        return 1;
+    }
+    p.rb_bytes = 0;
+    if (p.rowbias) {
+        const long rb_rows = p.rb_rows > 0 ? p.rb_rows : 1;
+        const long bytes = (((long)p.M - 1) / rb_rows * p.rb_ld + p.N) * 2;
+        if (bytes >= (long)kEpiOob) {
+            ctx->err = "contraction epilogue: the per-image bias must be smaller than 2 GiB";
+            return 1;
+        }
+        p.rb_bytes = (unsigned)bytes;
+    }
+    return 0;
+}
+
 template <int TM, int TN, bool RB, bool ON, bool BATCH = true>
 __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&acc)[TM][TN], int m0, int n0, int wm0, int wn0, int lane, int zb,
                                                    const EpiOps<TM, TN, RB, ON>& pre, float* stat_lds = nullptr) {
@@ -417,8 +450,9 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
         const unsigned nbytes = (unsigned)N * 2u;
         __amdgpu_buffer_rsrc_t rsB32 = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias, 0, hb32 ? nbytes * 2u : 0u, 0x00020000);
         __amdgpu_buffer_rsrc_t rsB16 = __builtin_amdgcn_make_buffer_rsrc((void*)p.bias, 0, hb16 ? nbytes : 0u, 0x00020000);
-        __amdgpu_buffer_rsrc_t rsRB = __builtin_amdgcn_make_buffer_rsrc((void*)p.rowbias, 0, hrb ? 0x80000000u : 0u, 0x00020000);
-        __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc((void*)R, 0, hres ? (unsigned)p.M * nbytes : 0u, 0x00020000);
+        __amdgpu_buffer_rsrc_t rsRB = __builtin_amdgcn_make_buffer_rsrc((void*)p.rowbias, 0, hrb ? p.rb_bytes : 0u, 0x00020000);
+        // the residual from the tile's first row on (see epi_extent): lane offsets (m - m0) * N * 2 stay below 2^31
+        __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc((void*)(hres ? R + (long)m0 * N : nullptr), 0, hres ? epi_extent(p.M - m0, N, N) : 0u, 0x00020000);
         // Loads through an EMPTY descriptor are not free (tools/gemm_kloop_probe.py PROBE_NO_BIAS=1: the epilogue phase of a launch with NO operand at all took
         // 3.9 us on the 128 x 128 tile and 5.4 us on 128 x 160 against 1.95 / 2.44 us for the same stores behind the on-demand form): a launch with neither row
         // operand -- the merged q / k / v and to_q projections, the feed-forward outputs -- skips the 2 x TM x TN of them behind ONE uniform branch.  Same bits.
@@ -465,7 +499,7 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
                 for (int ii = 0; ii < IB; ii++) {
                     const int m = mb + (i0 + ii) * 16;
                     const unsigned ro = hrb ? (unsigned)(((long)(min(m, p.M - 1) / (p.rb_rows > 0 ? p.rb_rows : 1)) * p.rb_ld + nb) * 2) : 0u;
-                    const unsigned rs = (unsigned)m * nbytes + (unsigned)nb * 2u;
+                    const unsigned rs = (unsigned)(wm0 + (lane & 15) + (i0 + ii) * 16) * nbytes + (unsigned)nb * 2u;
 #pragma unroll
                     for (int jj = 0; jj < JB; jj++) {
                         rbv[ii][jj] = __builtin_bit_cast(f16x4, __builtin_amdgcn_raw_buffer_load_b64(rsRB, ro + (j0 + jj) * 32, 0, 0));
@@ -547,29 +581,31 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
 #if OSG_EPI_STORE_AUX >= 0
     // round 6: the finished tile through a buffer descriptor -- rows / columns outside the matrix get an out-of-range offset and the hardware drops them (no exec-mask
     // code per store), and the cache policy is a compile-time choice (OSG_EPI_STORE_AUX: 0 plain, 16 = sc1 write-through: nothing left dirty in the L2 for the
-    // end-of-kernel write-back to wait for)
+    // end-of-kernel write-back to wait for).  The descriptors start at the workgroup tile's first row m0 and hold what is left of the output from there
+    // (epi_extent): an output of any size, and lane offsets ((m - m0) * ldc + n) * 2 below 2^31 (epi_check).  m0 and the kernel arguments are uniform: scalar descriptors.
     {
         typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-        __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)C, 0, 0x80000000u, 0x00020000)   /* (outputs stay below 2 GiB: the planner's own limit on a tensor) */;
+        const int mr = wm0 + (lane & 15), rows_left = p.M - m0;   // (a lane's rows relative to m0, and the matrix rows from m0 on)
+        __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc((void*)(C + (long)m0 * ldc), 0, epi_extent(rows_left, ldc, N), 0x00020000);
 #pragma unroll
         for (int i = 0; i < TM; i++) {
-            const int m = mb + i * 16;
+            const int r = mr + i * 16;
 #pragma unroll
             for (int j = 0; j < TN; j++) {
                 const int n = nb + j * 16;
-                const unsigned off = (m < p.M && n < N) ? (unsigned)(((long)m * ldc + n) * 2) : 0x80000000u;
+                const unsigned off = (r < rows_left && n < N) ? ((unsigned)r * (unsigned)ldc + (unsigned)n) * 2u : kEpiOob;
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o[i][j]), rsC, off, 0, OSG_EPI_STORE_AUX);
             }
         }
         if (OSG_UNLIKELY_IF(BATCH, p.C2 != nullptr)) {
-            __amdgpu_buffer_rsrc_t rsC2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.C2, 0, 0x80000000u, 0x00020000);
+            __amdgpu_buffer_rsrc_t rsC2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.C2 + (long)m0 * p.ldc2), 0, epi_extent(rows_left, p.ldc2, N), 0x00020000);
 #pragma unroll
             for (int i = 0; i < TM; i++) {
-                const int m = mb + i * 16;
+                const int r = mr + i * 16;
 #pragma unroll
                 for (int j = 0; j < TN; j++) {
                     const int n = nb + j * 16;
-                    const unsigned off = (m < p.M && n < N) ? (unsigned)(((long)m * p.ldc2 + n) * 2) : 0x80000000u;
+                    const unsigned off = (r < rows_left && n < N) ? ((unsigned)r * (unsigned)p.ldc2 + (unsigned)n) * 2u : kEpiOob;
                     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o[i][j]), rsC2, off, 0, OSG_EPI_STORE_AUX);
                 }
             }

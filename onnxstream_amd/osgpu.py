@@ -154,6 +154,15 @@ class DevBuf:
             self.gpu._ck(self.gpu.lib.osg_download(self.gpu.ctx, out.ctypes.data, self.ptr, self.nbytes))
         return out
 
+    def read_rows(self, lo: int, hi: int) -> np.ndarray:
+        """rows [lo, hi) of the buffer seen as [rows, shape[-1]] (NHWC: pixels), copied back without the rest of it"""
+        row = self.shape[-1]
+        assert 0 <= lo <= hi <= self.size // row, (lo, hi, self.shape)
+        out = np.empty((hi - lo, row), self.dtype)
+        if out.nbytes:
+            self.gpu._ck(self.gpu.lib.osg_download(self.gpu.ctx, out.ctypes.data, self.ptr + lo * row * self.dtype.itemsize, out.nbytes))
+        return out
+
     def free(self):
         if self.ptr:
             self.gpu.lib.osg_free(self.gpu.ctx, self.ptr)
