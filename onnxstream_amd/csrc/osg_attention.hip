@@ -218,8 +218,11 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnParams p) {
             }
             mx = row4_max(mx);
             const float m_new = fmaxf(m_run[qt], mx);             // raw (unscaled) running max; scale > 0
-            const float alpha = __builtin_amdgcn_exp2f((m_run[qt] - m_new) * c);
-            const float mc = -m_new * c;
+            // every key seen so far masked with -inf (sliding window, left padding): m_new = -inf would make alpha = exp2(NaN) and the
+            // exponent fma NaN; with 0 in its place the tile contributes exp2(-inf) = 0 and alpha = exp2(-inf) = 0.  Same values for finite m_new.
+            const float m_use = m_new == -INFINITY ? 0.f : m_new;
+            const float alpha = __builtin_amdgcn_exp2f((m_run[qt] - m_use) * c);
+            const float mc = -m_use * c;
             float sum = 0.f;
 #pragma unroll
             for (int t = 0; t < NT; t++)

@@ -214,6 +214,18 @@ class Gpu:
     def sync(self):
         self._ck(self.lib.osg_sync(self.ctx))
 
+    def memset(self, b: DevBuf, byte: int):
+        """every byte of b set to `byte` (on the compute stream, so ordered before the kernels launched after it)"""
+        self._ck(self.lib.osg_memset(self.ctx, b.ptr, byte, b.nbytes))
+
+    def _out(self, out: Optional[DevBuf], shape, dtype) -> DevBuf:
+        """the caller's output buffer (checked against the shape / dtype the op produces), or a fresh one"""
+        if out is None:
+            return self.empty(shape, dtype)
+        if out.size != int(np.prod(shape, dtype=np.int64)) or out.dtype != np.dtype(dtype):
+            raise OsgError(f"out= holds {out.shape} {out.dtype}, the op writes {tuple(shape)} {np.dtype(dtype)}")
+        return out
+
     def timer_start(self):
         self._ck(self.lib.osg_timer_start(self.ctx))
 
@@ -314,12 +326,12 @@ class Gpu:
         self._ck(self.lib.osg_attention(self.ctx, _NP2DT[q.dtype], q.ptr, k.ptr, v.ptr, o.ptr, heads, tq, tkv, d, scale, int(k_is_dt)))
         return o
 
-    def attention_tokens(self, q: DevBuf, k: DevBuf, v: DevBuf, heads: int, scale: float):
+    def attention_tokens(self, q: DevBuf, k: DevBuf, v: DevBuf, heads: int, scale: float, out: Optional[DevBuf] = None):
         """q:[B,Tq,heads*D], k,v:[B,Tkv,heads*D] straight out of the projections -> o:[B,Tq,heads*D]."""
         bsz, tq, c = q.shape
         tkv = k.shape[1]
         d = c // heads
-        o = self.empty(q.shape, q.dtype)
+        o = self._out(out, q.shape, q.dtype)
         self._ck(self.lib.osg_attention_strided(self.ctx, F16, q.ptr, c, d, tq * c, k.ptr, c, d, tkv * c, v.ptr, c, d, tkv * c, o.ptr, c, d,
                                                 tq * c, bsz, heads, tq, tkv, d, scale))
         return o
@@ -383,9 +395,9 @@ class Gpu:
         self._ck(self.lib.osg_tblock_tail(self.ctx, ctypes.byref(a)))
         return out, dumps
 
-    def rms_norm(self, x: DevBuf, w: DevBuf, eps: float):
+    def rms_norm(self, x: DevBuf, w: DevBuf, eps: float, out: Optional[DevBuf] = None):
         rows, c = int(np.prod(x.shape[:-1])), x.shape[-1]
-        y = self.empty(x.shape, x.dtype)
+        y = self._out(out, x.shape, x.dtype)
         self._ck(self.lib.osg_rms_norm(self.ctx, _NP2DT[x.dtype], x.ptr, w.ptr, y.ptr, rows, c, eps))
         return y
 
@@ -396,11 +408,11 @@ class Gpu:
         self._ck(self.lib.osg_rope(self.ctx, _NP2DT[x.dtype], x.ptr, cos.ptr, sin.ptr, y.ptr, int(np.prod(x.shape[:-2])), t, d))
         return y
 
-    def sdpa(self, q: DevBuf, k: DevBuf, v: DevBuf, mask: Optional[DevBuf], scale: float):
+    def sdpa(self, q: DevBuf, k: DevBuf, v: DevBuf, mask: Optional[DevBuf], scale: float, out: Optional[DevBuf] = None):
         """q:[B,Hq,Tq,D], k,v:[B,Hkv,Tkv,D], mask:[Tq,Tkv] additive or None -> o:[B,Hq,Tq,D] (the reference's ScaledDotProductAttention op)."""
         bsz, hq, tq, d = q.shape
         hkv, tkv = k.shape[1], k.shape[2]
-        o = self.empty(q.shape, q.dtype)
+        o = self._out(out, q.shape, q.dtype)
         self._ck(self.lib.osg_sdpa(self.ctx, _NP2DT[q.dtype], q.ptr, k.ptr, v.ptr, self._p(mask), o.ptr, bsz, hq, hkv, tq, tkv, d, scale))
         return o
 
@@ -433,33 +445,39 @@ class Gpu:
         self._ck(self.lib.osg_layer_norm(self.ctx, _NP2DT[x.dtype], x.ptr, gamma.ptr, beta.ptr, y.ptr, rows, c, eps))
         return y
 
-    def reduce_mean_last(self, x: DevBuf):
+    def reduce_mean_last(self, x: DevBuf, out: Optional[DevBuf] = None):
         rows, c = int(np.prod(x.shape[:-1])), x.shape[-1]
-        y = self.empty(x.shape[:-1] + (1,), x.dtype)
+        y = self._out(out, x.shape[:-1] + (1,), x.dtype)
         self._ck(self.lib.osg_reduce_mean_last(self.ctx, _NP2DT[x.dtype], x.ptr, y.ptr, rows, c))
         return y
 
-    def softmax_last(self, x: DevBuf):
+    def softmax_last(self, x: DevBuf, out: Optional[DevBuf] = None):
         rows, c = int(np.prod(x.shape[:-1])), x.shape[-1]
-        y = self.empty(x.shape, x.dtype)
+        y = self._out(out, x.shape, x.dtype)
         self._ck(self.lib.osg_softmax_last(self.ctx, _NP2DT[x.dtype], x.ptr, y.ptr, rows, c))
         return y
 
-    def unary(self, kind: str, x: DevBuf, param: float = 0.0):
-        y = self.empty(x.shape, x.dtype)
+    def unary(self, kind: str, x: DevBuf, param: float = 0.0, out: Optional[DevBuf] = None):
+        y = self._out(out, x.shape, x.dtype)
         self._ck(self.lib.osg_unary(self.ctx, _NP2DT[x.dtype], UN[kind], x.ptr, y.ptr, x.size, param))
         return y
 
-    def binary(self, kind: str, a: DevBuf, b: DevBuf):
+    def binary(self, kind: str, a: DevBuf, b: DevBuf, out: Optional[DevBuf] = None):
         rank = max(len(a.shape), len(b.shape))
         ash = (1,) * (rank - len(a.shape)) + a.shape
         bsh = (1,) * (rank - len(b.shape)) + b.shape
         osh = tuple(np.broadcast_shapes(ash, bsh))
-        y = self.empty(osh, a.dtype)
-        A = (ctypes.c_long * rank)(*ash)
-        B = (ctypes.c_long * rank)(*bsh)
-        self._ck(self.lib.osg_binary(self.ctx, _NP2DT[a.dtype], BIN[kind], a.ptr, A, b.ptr, B, y.ptr, rank))
+        y = self._out(out, osh, a.dtype)
+        self.binary_at(kind, a.dtype, a.ptr, ash, b.ptr, bsh, y.ptr)
         return y
+
+    def binary_at(self, kind: str, dtype, a_ptr: int, a_shape, b_ptr: int, b_shape, y_ptr: int):
+        """osg_binary on raw device addresses (e.g. an offset into a DevBuf: the entry point's unaligned-operand path); shapes of equal rank"""
+        rank = len(a_shape)
+        assert len(b_shape) == rank
+        A = (ctypes.c_long * rank)(*a_shape)
+        B = (ctypes.c_long * rank)(*b_shape)
+        self._ck(self.lib.osg_binary(self.ctx, _NP2DT[np.dtype(dtype)], BIN[kind], a_ptr, A, b_ptr, B, y_ptr, rank))
 
     def geglu(self, x: DevBuf):
         rows, c2 = int(np.prod(x.shape[:-1])), x.shape[-1]
