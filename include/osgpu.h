@@ -320,6 +320,37 @@ int osg_sampler_prepare(osg_ctx* ctx, const float* x, float* sample, float* time
  * [-clip, clip] (not in the reference; used with random-weight synthetic UNets, which do not denoise, to keep the trajectory finite). */
 int osg_sampler_cfg_euler_a(osg_ctx* ctx, float* x, const float* eps, const float* noise, int prompts, long L, float c_out,
                             float guidance, float sigma, float d_sigma, float sigma_up, float clip);
+/* The update forms of osg_sampler_cfg_multistep: the one-evaluation multistep samplers of src/samplers.h (the ORIGINAL_SAMPLER_ALGORITHMS branch).
+ * den as in osg_sampler_cfg_euler_a; d = (x - den) / sigma; h0 is written, h1..h3 (history entries of the last steps) are read; k0..k4, da, db are
+ * the step's scalars (loop-invariant coefficients computed on the host with the reference's expression tree, each operation rounded to float):
+ *   DPMPP_FIRST  x = (k0*x) - (k1*den);                                         h0 = den   (DPM++ 2M / 2M v2, first and last step: k0 = a, k1 = b)
+ *   DPMPP_2M     x = (k0*x) - (k1*((k2*den) - (k3*h1)));                        h0 = den   (k2 = 1 + 1/(2r), k3 = 1/(2r); h1 may equal h0)
+ *   EULER_D      x = x + (k0*d);                                                h0 = d     (iPNDM family and Taylor3 at order 0: k0 = sigma_{i+1} - sigma_i)
+ *   IPNDM1       x = x + ((k0*((3*d) - h1)) / 2);                               h0 = d
+ *   IPNDM_V1     x = x + ((k0*((k1*d) - (k2*h1))) / 2);                         h0 = d     (k1 = 2 + h_n/h_n_1, k2 = h_n/h_n_1)
+ *   IPNDM2       x = x + ((k0*(((23*d) - (16*h1)) + (5*h2))) / 12);             h0 = d     (iPNDM and iPNDM_v)
+ *   IPNDM3       x = x + ((k0*((((55*d) - (59*h1)) + (37*h2)) - (9*h3))) / 24); h0 = d     (iPNDM and iPNDM_v)
+ *   IPNDM_VO1    x = x + (k0*((k1*d) + (k2*h1)));                               h0 = d     (k1.. = coeff1..)
+ *   IPNDM_VO2    x = x + (k0*(((k1*d) + (k2*h1)) + (k3*h2)));                   h0 = d
+ *   IPNDM_VO3    x = x + (k0*((((k1*d) + (k2*h1)) + (k3*h2)) + (k4*h3)));       h0 = d
+ *   TAYLOR1      d2 = (d - h1)*k1;  x = x + ((k0*d) + (k2*d2));                 h0 = d     (k0 = dt, k1 = 1/dt_prev, k2 = dt*dt/2)
+ *   TAYLOR2      d2 = (d - h1)*k1;  d3 = (d2 - h2)*k1;
+ *                x = x + (((k0*d) + (k2*d2)) + (k3*d3));                        h0 = d     (k3 = dt*dt*dt/6)
+ *   DDIM         x = (float)(((double)x*da) + ((double)den*db))                            (no history) */
+typedef enum {
+    OSG_MS_DPMPP_FIRST = 0, OSG_MS_DPMPP_2M = 1, OSG_MS_EULER_D = 2, OSG_MS_IPNDM1 = 3, OSG_MS_IPNDM_V1 = 4, OSG_MS_IPNDM2 = 5, OSG_MS_IPNDM3 = 6,
+    OSG_MS_IPNDM_VO1 = 7, OSG_MS_IPNDM_VO2 = 8, OSG_MS_IPNDM_VO3 = 9, OSG_MS_TAYLOR1 = 10, OSG_MS_TAYLOR2 = 11, OSG_MS_DDIM = 12, OSG_MS_FORMS = 13
+} osg_multistep_form;
+/* One multistep step with the CFG combine, in place on x:[prompts,L]; eps:[2*prompts,L]; h0..h3:[prompts,L] (NULL where the form does not touch
+ * them; an unknown form or a missing pointer fails).  fp32, every product, sum and IEEE division rounded separately (DDIM: double, one rounding at
+ * the store), i.e. bit-identical to the host loop. */
+int osg_sampler_cfg_multistep(osg_ctx* ctx, int form, float* x, const float* eps, float* h0, const float* h1, const float* h2, const float* h3,
+                              int prompts, long L, float c_out, float guidance, float sigma, float k0, float k1, float k2, float k3, float k4,
+                              double da, double db);
+/* osg_sampler_prepare preceded by DDIM's prescale (src/samplers.h:27-59): x = x * x_scale IN PLACE, then sample[2p] = sample[2p+1] = x[p] * c_in
+ * and timestep[0 .. 2*prompts*t_per_sample) = t -- one launch. */
+int osg_sampler_prepare_rescale(osg_ctx* ctx, float* x, float* sample, float* timestep, int prompts, long L, float x_scale, float c_in, float t,
+                                long t_per_sample);
 
 /* ---- data movement ------------------------------------------------------------------------------------------ */
 /* N-d transpose (XnnPack::transpose, onnxstream.cpp:1748): out.shape[i] = shape[perm[i]]. elem_size in {1,2,4,8}. */

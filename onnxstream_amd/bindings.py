@@ -202,6 +202,32 @@ class Model:
                     clip.ctypes.data_as(fp) if clip is not None else None, ctypes.byref(ms)))
         return ms.value
 
+    def hip_sampler_loop_multistep(self, sample: str, timestep: str, out: str, x, sampler: int, c_in, c_out, t, sigma, order, coef, dcoef,
+                                   guidance: float = 7.0) -> float:
+        """The denoising loop with a one-evaluation multistep sampler (DPM++ 2M / 2M v2, iPNDM, iPNDM_v, iPNDM_vo, Taylor3, DDIM) on the device,
+        one host sync at the end.  sampler: the loop form of model_hip_sampler_loop_multistep (pipeline.Txt2Img.multistep_table makes it and the
+        tables); c_in, c_out, t, sigma: `steps` float32 entries; order: `steps` ints; coef: float32 [steps, 6]; dcoef: float64 [steps, 2].
+        x: float32 [prompts, ...], updated IN PLACE.  Returns the loop's device ms."""
+        import numpy as np
+        f = self._lib.model_hip_sampler_loop_multistep
+        fp, dp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+        f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, ip,
+                      fp, ctypes.c_ulonglong, dp, ctypes.c_ulonglong, ctypes.c_float, ctypes.POINTER(ctypes.c_double)]
+        f.restype = ctypes.c_void_p
+        assert x.dtype == np.float32 and x.flags.c_contiguous
+        arrs = [np.ascontiguousarray(a, np.float32) for a in (c_in, c_out, t, sigma)]
+        steps = len(arrs[0])
+        if any(len(a) != steps for a in arrs) or len(order) != steps:
+            raise OnnxStreamError("hip_sampler_loop_multistep: c_in, c_out, t, sigma and order need one entry per step")
+        order = np.ascontiguousarray(order, np.int32)
+        coef = np.ascontiguousarray(coef, np.float32)
+        dcoef = np.ascontiguousarray(dcoef, np.float64)
+        ms = ctypes.c_double(0)
+        self._err(f(self._h, self._name(sample), self._name(timestep), self._name(out), steps, x.shape[0], int(sampler), x.ctypes.data_as(fp),
+                    *[a.ctypes.data_as(fp) for a in arrs], order.ctypes.data_as(ip), coef.ctypes.data_as(fp), coef.size, dcoef.ctypes.data_as(dp),
+                    dcoef.size, guidance, ctypes.byref(ms)))
+        return ms.value
+
     def set_upcast_substrings(self, subs):
         """Model::m_requires_upcast (a std::function in C++, src/llm.cpp:379-383): ops whose name contains one of `subs` run in fp32.  Works on
         libonnxstream_amd.so (model_hip_set_upcast_substrings) and on the oracle build of the reference (ref_set_upcast_substrings)."""

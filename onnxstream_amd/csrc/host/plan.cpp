@@ -387,6 +387,7 @@ Plan::~Plan() {
     if (graph) be.api.osg_graph_destroy(graph);
     if (samp_x) be.api.osg_free(be.ctx, samp_x);
     if (samp_noise) be.api.osg_free(be.ctx, samp_noise);
+    if (samp_hist) be.api.osg_free(be.ctx, samp_hist);
     if (ring) be.free(ring);
     for (void* p : owned) be.free(p);
     if (arena && !arena_pooled) be.free(arena);

@@ -184,6 +184,20 @@ struct Plan {
     double sampler_loop(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps, int prompts,
                         float* x, const float* noise, const float* c_in, const float* c_out, const float* t, const float* sigma, const float* d_sigma,
                         const float* sigma_up, float guidance, const float* clip);
+    // the same loop with one of the one-evaluation multistep samplers of src/samplers.h (DPM++ 2M / 2M v2, iPNDM, iPNDM_v, iPNDM_vo, Taylor3, DDIM):
+    // per step a prepare launch (DDIM: with its in-place prescale of x), the pass, and one osg_sampler_cfg_multistep launch whose form follows
+    // from `sampler` (OSG_LOOP_* of exports.cpp) and order[i].  coef: [steps, 6] float (k0..k4 of the form, then DDIM's prescale factor),
+    // dcoef: [steps, 2] double (DDIM's da, db); n_coef / n_dcoef are their lengths.  The history ring [H, prompts, L] is allocated once and
+    // reused; order[i] <= i is required, so a call never reads an entry an earlier image left behind.
+    double sampler_loop_multistep(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps, int prompts,
+                                  int sampler, float* x, const float* c_in, const float* c_out, const float* t, const float* sigma, const int* order,
+                                  const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef, float guidance);
+    // the same on Model m's plan, recording its last-pass time (model_hip_sampler_loop_multistep).  A static member of Plan, Model's friend, so that
+    // onnxstream.h -- the header the reference application is compiled against for the drop-in link (oracle/Makefile) -- stays as it is.
+    static double run_sampler_loop_multistep(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name,
+                                             int n_steps, int prompts, int sampler, float* x, const float* c_in, const float* c_out, const float* t,
+                                             const float* sigma, const int* order, const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef,
+                                             float guidance);
     // eager pass with HIP events around every step, `reps` times; "ms<TAB>flops<TAB>bytes<TAB>what" per line (ms = mean)
     std::string profile(int reps);
     // plan introspection for the CPU tests of the host logic (tests/test_planner_cpu.py): one line per step
@@ -265,7 +279,8 @@ struct Plan {
 
     void* samp_x = nullptr;       // sampler_loop state: latents [prompts, L] and the pre-drawn noise [steps, prompts, L], device fp32
     void* samp_noise = nullptr;
-    size_t samp_x_bytes = 0, samp_noise_bytes = 0;
+    void* samp_hist = nullptr;    // sampler_loop_multistep: history ring [H, prompts, L], device fp32
+    size_t samp_x_bytes = 0, samp_noise_bytes = 0, samp_hist_bytes = 0;
 
     osg_graph* graph = nullptr;
     Lowering* lowering = nullptr;  // kept alive: the launch closures capture it

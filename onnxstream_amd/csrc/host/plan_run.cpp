@@ -527,6 +527,98 @@ double Plan::sampler_loop(const std::string& sample_name, const std::string& tim
     return ms;
 }
 
+double Plan::sampler_loop_multistep(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
+                                   int prompts, int sampler, float* x, const float* c_in, const float* c_out, const float* t, const float* sigma,
+                                   const int* order, const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef, float guidance) {
+    static const char* fn = "Model::hip_sampler_loop_multistep: ";
+    if (runs < 1) throw std::runtime_error(std::string(fn) + "run() once first (the context inputs must be resident).");
+    if (stream_weights) throw std::runtime_error(std::string(fn) + "not available in streamed-weights mode.");
+    if (u8) throw std::runtime_error(std::string(fn) + "not available with uint8 arithmetic.");
+    if (prompts <= 0 || 2L * prompts != N) throw std::invalid_argument(std::string(fn) + "the plan's batch must be 2 * prompts (cond, uncond per prompt).");
+    // per sampler: history depth (create_buffers, src/samplers.h:5-24), highest order, and the kernel form of each order
+    static const int forms[6][4] = {
+        {OSG_MS_DPMPP_FIRST, OSG_MS_DPMPP_2M, -1, -1},                    // 0: DPM++ 2M and 2M v2 (they differ in the host coefficients only)
+        {OSG_MS_EULER_D, OSG_MS_IPNDM1, OSG_MS_IPNDM2, OSG_MS_IPNDM3},    // 1: iPNDM
+        {OSG_MS_EULER_D, OSG_MS_IPNDM_V1, OSG_MS_IPNDM2, OSG_MS_IPNDM3},  // 2: iPNDM_v
+        {OSG_MS_EULER_D, OSG_MS_IPNDM_VO1, OSG_MS_IPNDM_VO2, OSG_MS_IPNDM_VO3},  // 3: iPNDM_vo
+        {OSG_MS_EULER_D, OSG_MS_TAYLOR1, OSG_MS_TAYLOR2, -1},             // 4: Taylor3
+        {OSG_MS_DDIM, -1, -1, -1},                                        // 5: DDIM
+    };
+    static const int depth[6] = {1, 4, 4, 4, 3, 0};
+    if (sampler < 0 || sampler >= 6) throw std::invalid_argument(std::string(fn) + "unknown sampler form " + std::to_string(sampler) + ".");
+    if (n_steps < 0 || n_coef != (size_t)n_steps * 6 || n_dcoef != (size_t)n_steps * 2)
+        throw std::invalid_argument(std::string(fn) + "the coefficient tables must hold steps * 6 floats and steps * 2 doubles.");
+    for (int i = 0; i < n_steps; i++)
+        if (order[i] < 0 || order[i] > 3 || order[i] > i || forms[sampler][order[i]] < 0)
+            throw std::invalid_argument(std::string(fn) + "order " + std::to_string(order[i]) + " at step " + std::to_string(i) + " is not available.");
+    FlightGuard flight(in_flight);
+    const In *in_s = nullptr, *in_t = nullptr;
+    for (auto& in : inputs) {
+        if (in.name == sample_name) in_s = &in;
+        if (in.name == timestep_name) in_t = &in;
+    }
+    const Out* out = nullptr;
+    for (auto& o : outputs)
+        if (o.name == out_name) out = &o;
+    if (!in_s || !in_t || !out) throw std::invalid_argument(std::string(fn) + "input/output tensor not found.");
+    if (out->raw16) throw std::invalid_argument(std::string(fn) + "the output is excluded from the fp32 conversion (m_outputs_convert_set).");
+    const long L = vals[in_s->staging].numel(), TL = vals[in_t->staging].numel();
+    if (vals[out->f32val].numel() != L || !vals[out->f32val].batched)
+        throw std::invalid_argument(std::string(fn) + "the output must have the shape of the sample input.");
+    const int H = depth[sampler];
+    const size_t xb = (size_t)prompts * L * sizeof(float), hb = (size_t)H * xb;
+    auto grow = [&](void*& p, size_t& have, size_t need) {
+        if (have >= need) return;
+        if (p) be.check(be.api.osg_free(be.ctx, p), "osg_free");
+        p = nullptr;
+        have = 0;
+        be.check(be.api.osg_malloc(be.ctx, need, &p), "osg_malloc");
+        have = need;
+    };
+    grow(samp_x, samp_x_bytes, xb);
+    if (H) grow(samp_hist, samp_hist_bytes, hb);
+    be.check(be.api.osg_upload(be.ctx, samp_x, x, xb), "osg_upload");
+    // history entry k of step i (k = 0: written now, k >= 1: written k steps ago) lives in ring slot (i - k) mod H: the reference's shift of
+    // sampler_history_buffer (src/samplers.h:695 and alike) becomes a rotation of the pointers
+    auto slot = [&](int i, int k) -> float* { return H ? (float*)samp_hist + (size_t)(((i - k) % H + H) % H) * prompts * L : nullptr; };
+    be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");
+    for (int i = 0; i < n_steps; i++) {
+        const float* k = coef + (size_t)i * 6;
+        if (sampler == 5)
+            be.check(be.api.osg_sampler_prepare_rescale(be.ctx, (float*)samp_x, (float*)ptr(in_s->staging), (float*)ptr(in_t->staging), prompts, L, k[5],
+                                                        c_in[i], t[i], TL),
+                     "osg_sampler_prepare_rescale");
+        else
+            be.check(be.api.osg_sampler_prepare(be.ctx, (const float*)samp_x, (float*)ptr(in_s->staging), (float*)ptr(in_t->staging), prompts, L, c_in[i],
+                                                t[i], TL),
+                     "osg_sampler_prepare");
+        if (graph) be.check(be.api.osg_graph_launch(be.ctx, graph), "osg_graph_launch");
+        else run_steps();
+        const int o = order[i];
+        be.check(be.api.osg_sampler_cfg_multistep(be.ctx, forms[sampler][o], (float*)samp_x, (const float*)ptr(out->f32val), slot(i, 0),
+                                                  o >= 1 ? slot(i, 1) : nullptr, o >= 2 ? slot(i, 2) : nullptr, o >= 3 ? slot(i, 3) : nullptr, prompts, L,
+                                                  c_out[i], guidance, sigma[i], k[0], k[1], k[2], k[3], k[4], dcoef[2 * i], dcoef[2 * i + 1]),
+                 "osg_sampler_cfg_multistep");
+    }
+    float ms = 0;
+    be.check(be.api.osg_timer_stop(be.ctx, &ms), "osg_timer_stop");
+    be.check(be.api.osg_download(be.ctx, x, samp_x, xb), "osg_download");
+    runs += n_steps;
+    m_last_ms = n_steps > 0 ? ms / n_steps : 0;
+    return ms;
+}
+
+double Plan::run_sampler_loop_multistep(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name,
+                                       int n_steps, int prompts, int sampler, float* x, const float* c_in, const float* c_out, const float* t,
+                                       const float* sigma, const int* order, const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef,
+                                       float guidance) {
+    if (!m.m_plan) throw std::runtime_error("Model::hip_sampler_loop_multistep: no plan (call run() first).");
+    const double ms = m.m_plan->sampler_loop_multistep(sample_name, timestep_name, out_name, n_steps, prompts, sampler, x, c_in, c_out, t, sigma, order,
+                                                       coef, n_coef, dcoef, n_dcoef, guidance);
+    m.m_last_ms = m.m_plan->last_ms();
+    return ms;
+}
+
 std::string Plan::info() const {
     std::string out;
     char buf[128];

@@ -4,6 +4,9 @@
 //   osg_sampler_cfg_euler_a <- eps -> denoised (x + eps * c_out), the CFG combine (uncond + g * (cond - uncond), src/sd.cpp:1545-1556) and
 //                              the Euler-Ancestral update (src/samplers.h:1430-1449: the branch the shipped `#define ORIGINAL_SAMPLER_ALGORITHMS 1`,
 //                              samplers.h:66, selects:  x = x + ((x - d) / sigma_i) * (sigma_down - sigma_i) + r * sigma_up)
+//   osg_sampler_cfg_multistep   <- the same CFG combine, then one step of DPM++ 2M / 2M v2, iPNDM / iPNDM_v / iPNDM_vo, Taylor3 or DDIM
+//                                  (src/samplers.h:339-377, :543-582, :688-940, :942-1034, :1078-1100) with a history ring per prompt
+//   osg_sampler_prepare_rescale <- osg_sampler_prepare after DDIM's in-place prescale of x (prescale_sample, src/samplers.h:27-59)
 // fp32 throughout, in the reference's operation order with every multiply and add rounded separately (no fma contraction), so the device
 // loop reproduces the host loop bit for bit (tests/test_pipeline.py).
 #include "osg_common.h"
@@ -50,6 +53,134 @@ __global__ __launch_bounds__(256) void sampler_cfg_euler_a_kernel(float* __restr
     x[i] = nx;
 }
 
+// The multistep samplers of src/samplers.h (ORIGINAL_SAMPLER_ALGORITHMS branch): the same CFG combine as above, then one of the update forms
+// of include/osgpu.h (osg_multistep_form), each its own straight-line instantiation.  h0 receives this step's history entry (the denoised
+// latent for DPM++, the derivative d otherwise); h1..h3 are the entries of the previous steps (ring slots chosen by the host, never copied).
+// For DPM++ 2M h1 == h0 (one slot, read before it is overwritten), so the history pointers carry no __restrict__.
+template <int F>
+__global__ __launch_bounds__(256) void sampler_cfg_multistep_kernel(float* __restrict__ x, const float* __restrict__ eps, float* h0, const float* h1,
+                                                                    const float* h2, const float* h3, int prompts, long L, float c_out, float guidance,
+                                                                    float sigma, float k0, float k1, float k2, float k3, float k4, double da, double db) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)prompts * L) return;
+    const long p = i / L, e = i - p * L;
+    const float xv = x[i];
+    const float pc = eps[(2 * p) * L + e] * c_out, pu = eps[(2 * p + 1) * L + e] * c_out;
+    const float den_c = pc + xv;
+    const float den_u = pu + xv;
+    const float gd = guidance * (den_c - den_u);
+    const float den = den_u + gd;
+    if constexpr (F == OSG_MS_DDIM) {
+        const double ax = (double)xv * da;
+        const double bd = (double)den * db;
+        x[i] = (float)(ax + bd);
+    } else if constexpr (F == OSG_MS_DPMPP_FIRST || F == OSG_MS_DPMPP_2M) {
+        float dv = den;
+        if constexpr (F == OSG_MS_DPMPP_2M) {
+            const float u = k2 * den;
+            const float w = k3 * h1[i];
+            dv = u - w;
+        }
+        const float ax = k0 * xv;
+        const float bd = k1 * dv;
+        h0[i] = den;
+        x[i] = ax - bd;
+    } else {
+        const float d = (xv - den) / sigma;
+        float s;
+        if constexpr (F == OSG_MS_EULER_D) {
+            s = k0 * d;
+        } else if constexpr (F == OSG_MS_IPNDM1) {
+            const float t = 3.f * d;
+            const float u = t - h1[i];
+            const float v = k0 * u;
+            s = v / 2.f;
+        } else if constexpr (F == OSG_MS_IPNDM_V1) {
+            const float t = k1 * d;
+            const float w = k2 * h1[i];
+            const float u = t - w;
+            const float v = k0 * u;
+            s = v / 2.f;
+        } else if constexpr (F == OSG_MS_IPNDM2) {
+            const float t = 23.f * d;
+            const float w1 = 16.f * h1[i];
+            const float w2 = 5.f * h2[i];
+            const float u = t - w1;
+            const float u2 = u + w2;
+            const float v = k0 * u2;
+            s = v / 12.f;
+        } else if constexpr (F == OSG_MS_IPNDM3) {
+            const float t = 55.f * d;
+            const float w1 = 59.f * h1[i];
+            const float w2 = 37.f * h2[i];
+            const float w3 = 9.f * h3[i];
+            const float u = t - w1;
+            const float u2 = u + w2;
+            const float u3 = u2 - w3;
+            const float v = k0 * u3;
+            s = v / 24.f;
+        } else if constexpr (F == OSG_MS_IPNDM_VO1) {
+            const float t = k1 * d;
+            const float w = k2 * h1[i];
+            const float u = t + w;
+            s = k0 * u;
+        } else if constexpr (F == OSG_MS_IPNDM_VO2) {
+            const float t = k1 * d;
+            const float w1 = k2 * h1[i];
+            const float w2 = k3 * h2[i];
+            const float u = t + w1;
+            const float u2 = u + w2;
+            s = k0 * u2;
+        } else if constexpr (F == OSG_MS_IPNDM_VO3) {
+            const float t = k1 * d;
+            const float w1 = k2 * h1[i];
+            const float w2 = k3 * h2[i];
+            const float w3 = k4 * h3[i];
+            const float u = t + w1;
+            const float u2 = u + w2;
+            const float u3 = u2 + w3;
+            s = k0 * u3;
+        } else if constexpr (F == OSG_MS_TAYLOR1) {
+            const float dd = d - h1[i];
+            const float d2 = dd * k1;
+            const float t = k0 * d;
+            const float w = k2 * d2;
+            s = t + w;
+        } else {
+            static_assert(F == OSG_MS_TAYLOR2, "unknown multistep form");
+            const float dd = d - h1[i];
+            const float d2 = dd * k1;
+            const float dd3 = d2 - h2[i];
+            const float d3 = dd3 * k1;
+            const float t = k0 * d;
+            const float w2 = k2 * d2;
+            const float w3 = k3 * d3;
+            const float u = t + w2;
+            s = u + w3;
+        }
+        h0[i] = d;
+        x[i] = xv + s;
+    }
+}
+
+// osg_sampler_prepare with DDIM's prescale (src/samplers.h:27-59) folded in: x *= x_scale in place first, the UNet input is the rescaled x
+__global__ __launch_bounds__(256) void sampler_prepare_rescale_kernel(float* __restrict__ x, float* __restrict__ sample, float* __restrict__ timestep,
+                                                                      int prompts, long L, float x_scale, float c_in, float t, long t_per_sample) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const long total = (long)prompts * L;
+    if (i < total) {
+        const long p = i / L, e = i - p * L;
+        const float xs = x[i] * x_scale;
+        x[i] = xs;
+        const float v = xs * c_in;
+        sample[(2 * p) * L + e] = v;
+        sample[(2 * p + 1) * L + e] = v;
+    }
+    if (i < 2L * prompts * t_per_sample) timestep[i] = t;
+}
+
 }  // namespace
 
 extern "C" {
@@ -70,6 +201,46 @@ int osg_sampler_cfg_euler_a(osg_ctx* ctx, float* x, const float* eps, const floa
     const long total = (long)prompts * L;
     hipLaunchKernelGGL(sampler_cfg_euler_a_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->compute, x, eps, noise, prompts, L, c_out,
                        guidance, sigma, d_sigma, sigma_up, clip);
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int osg_sampler_prepare_rescale(osg_ctx* ctx, float* x, float* sample, float* timestep, int prompts, long L, float x_scale, float c_in, float t,
+                                long t_per_sample) {
+    if (prompts <= 0 || L <= 0) return 0;
+    const long total = (long)prompts * L;
+    const long n = total > 2L * prompts * t_per_sample ? total : 2L * prompts * t_per_sample;
+    hipLaunchKernelGGL(sampler_prepare_rescale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->compute, x, sample, timestep, prompts, L,
+                       x_scale, c_in, t, t_per_sample);
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int osg_sampler_cfg_multistep(osg_ctx* ctx, int form, float* x, const float* eps, float* h0, const float* h1, const float* h2, const float* h3,
+                              int prompts, long L, float c_out, float guidance, float sigma, float k0, float k1, float k2, float k3, float k4,
+                              double da, double db) {
+    if (form < 0 || form >= OSG_MS_FORMS) OSG_FAIL(ctx, "osg_sampler_cfg_multistep: unknown form " + std::to_string(form));
+    const int need = form == OSG_MS_DDIM ? 0 : form == OSG_MS_IPNDM3 || form == OSG_MS_IPNDM_VO3 ? 4
+                   : form == OSG_MS_IPNDM2 || form == OSG_MS_IPNDM_VO2 || form == OSG_MS_TAYLOR2 ? 3
+                   : form == OSG_MS_DPMPP_FIRST || form == OSG_MS_EULER_D ? 1 : 2;    // history pointers the form touches: h0 .. h(need-1)
+    const float* hs[4] = {h0, h1, h2, h3};
+    for (int k = 0; k < need; k++)
+        if (!hs[k]) OSG_FAIL(ctx, "osg_sampler_cfg_multistep: form " + std::to_string(form) + " needs history pointer h" + std::to_string(k));
+    if (prompts <= 0 || L <= 0) return 0;
+    const long total = (long)prompts * L;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+#define OSG_MS_CASE(F)                                                                                                                              \
+    case F:                                                                                                                                         \
+        hipLaunchKernelGGL(sampler_cfg_multistep_kernel<F>, grid, block, 0, ctx->compute, x, eps, h0, h1, h2, h3, prompts, L, c_out, guidance,   \
+                           sigma, k0, k1, k2, k3, k4, da, db);                                                                                      \
+        break;
+    switch (form) {
+        OSG_MS_CASE(OSG_MS_DPMPP_FIRST) OSG_MS_CASE(OSG_MS_DPMPP_2M) OSG_MS_CASE(OSG_MS_EULER_D) OSG_MS_CASE(OSG_MS_IPNDM1)
+        OSG_MS_CASE(OSG_MS_IPNDM_V1) OSG_MS_CASE(OSG_MS_IPNDM2) OSG_MS_CASE(OSG_MS_IPNDM3) OSG_MS_CASE(OSG_MS_IPNDM_VO1)
+        OSG_MS_CASE(OSG_MS_IPNDM_VO2) OSG_MS_CASE(OSG_MS_IPNDM_VO3) OSG_MS_CASE(OSG_MS_TAYLOR1) OSG_MS_CASE(OSG_MS_TAYLOR2)
+        OSG_MS_CASE(OSG_MS_DDIM)
+    }
+#undef OSG_MS_CASE
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }

@@ -11,6 +11,7 @@ Out of scope (host glue of the app): tokenizer, text enc
 """
 from __future__ import annotations
 
+import math
 from typing import Callable, Dict, List, Optional
 
 import numpy as np
@@ -38,6 +39,62 @@ def _libm_float_fn(name):
 
 
 expf, logf = _libm_float_fn("exp"), _libm_float_fn("log")
+expm1f, sqrtf = _libm_float_fn("expm1"), _libm_float_fn("sqrt")
+
+# the samplers of the reference's --sampler (src/sd.cpp:41-63) that sample() and sample_device() run: the default Euler-Ancestral, Euler, and the
+# one-evaluation, noise-free multistep samplers of src/samplers.h (the ORIGINAL_SAMPLER_ALGORITHMS branch)
+SAMPLERS = ("euler_a", "euler", "dpm++2m", "dpm++2mv2", "ipndm", "ipndm_v", "ipndm_vo", "taylor3", "ddim")
+# multistep sampler -> loop form of model_hip_sampler_loop_multistep (exports.cpp)
+MULTISTEP = {"dpm++2m": 0, "dpm++2mv2": 0, "ipndm": 1, "ipndm_v": 2, "ipndm_vo": 3, "taylor3": 4, "ddim": 5}
+# loop form -> (history depth as src/samplers.h create_buffers, the osg_multistep_form of each order); the table of Plan::sampler_loop_multistep
+_MS_LOOP = {0: (1, (0, 1)), 1: (4, (2, 3, 5, 6)), 2: (4, (2, 4, 5, 6)), 3: (4, (2, 7, 8, 9)), 4: (3, (2, 10, 11)), 5: (0, (12,))}
+
+
+def _check_sampler(sampler: str) -> None:
+    if sampler not in SAMPLERS:
+        raise ValueError(f"unknown sampler {sampler!r}; valid names: {', '.join(SAMPLERS)}")
+
+
+def multistep_update(form: int, x: np.ndarray, den: np.ndarray, hist, sigma, k, dk) -> np.ndarray:
+    """One step of osg_multistep_form `form` (include/osgpu.h) on the host, in the kernel's operation order: every fp32 operation rounded on its
+    own, DDIM in float64 with one rounding at the end.  hist = [h0, h1, h2, h3] (arrays or None); h0 is overwritten.  Returns the new x."""
+    k0, k1, k2, k3, k4 = (f32(v) for v in k[:5])
+    if form == 12:
+        return ((x.astype(np.float64) * float(dk[0])) + (den.astype(np.float64) * float(dk[1]))).astype(f32)
+    if form in (0, 1):
+        dv = den if form == 0 else (k2 * den) - (k3 * hist[1])
+        nx = (k0 * x) - (k1 * dv)
+        hist[0][...] = den
+        return nx.astype(f32)
+    d = (x - den) / f32(sigma)
+    h1, h2, h3 = hist[1], hist[2], hist[3]
+    if form == 2:
+        s = k0 * d
+    elif form == 3:
+        s = (k0 * ((f32(3) * d) - h1)) / f32(2)
+    elif form == 4:
+        s = (k0 * ((k1 * d) - (k2 * h1))) / f32(2)
+    elif form == 5:
+        s = (k0 * (((f32(23) * d) - (f32(16) * h1)) + (f32(5) * h2))) / f32(12)
+    elif form == 6:
+        s = (k0 * ((((f32(55) * d) - (f32(59) * h1)) + (f32(37) * h2)) - (f32(9) * h3))) / f32(24)
+    elif form == 7:
+        s = k0 * ((k1 * d) + (k2 * h1))
+    elif form == 8:
+        s = k0 * (((k1 * d) + (k2 * h1)) + (k3 * h2))
+    elif form == 9:
+        s = k0 * ((((k1 * d) + (k2 * h1)) + (k3 * h2)) + (k4 * h3))
+    elif form == 10:
+        d2 = (d - h1) * k1
+        s = (k0 * d) + (k2 * d2)
+    elif form == 11:
+        d2 = (d - h1) * k1
+        d3 = (d2 - h2) * k1
+        s = ((k0 * d) + (k2 * d2)) + (k3 * d3)
+    else:
+        raise ValueError(f"unknown multistep form {form}")
+    hist[0][...] = d
+    return (x + s).astype(f32)
 
 
 def log_sigmas_table() -> np.ndarray:
@@ -193,13 +250,27 @@ class Txt2Img:
         (src/samplers.h:1431-1449, ORIGINAL_SAMPLER_ALGORITHMS):  x += ((x - d) / sigma_i) * (sigma_down - sigma_i) + r * sigma_up,
         every operation rounded to float on its own.  init_latent: N(0,1) start (default: numpy stream; the reference draws
         randn_4_w_h(seed % 1000), :1595) -- it is scaled by sigma[0] here as :1611-1612 does; step_noise(i): the ancestral noise of step i.
-        sampler="euler": the plain Euler step of the same branch (src/samplers.h:116-126): x += (x - d) / sigma_i * (sigma_{i+1} - sigma_i), no noise."""
-        if sampler not in ("euler_a", "euler"):
-            raise ValueError("sampler must be 'euler_a' (the reference's default) or 'euler'")
+        sampler="euler": the plain Euler step of the same branch (src/samplers.h:116-126): x += (x - d) / sigma_i * (sigma_{i+1} - sigma_i), no noise.
+        The multistep samplers of MULTISTEP (DPM++ 2M / 2M v2, iPNDM, iPNDM_v, iPNDM_vo, Taylor3, DDIM) take their per-step scalars from
+        multistep_table() and step with multistep_update(), the host restatement of the device kernel; they draw no noise."""
+        _check_sampler(sampler)
         sig = sigma_schedule(steps, self.log_sigmas)
         rng = np.random.default_rng(seed)     # the reference draws mt19937 normals; any N(0,1) stream is equivalent for the harness
         x0 = rng.standard_normal(latent_shape, dtype=f32) if init_latent is None else np.asarray(init_latent, f32).reshape(latent_shape)
         x = (x0 * f32(sig[0])).astype(f32)
+        if sampler in MULTISTEP:
+            loop, order, coef, dcoef = self.multistep_table(sig, sampler)
+            depth, forms = _MS_LOOP[loop]
+            ring = [np.zeros(x.shape, f32) for _ in range(depth)]
+            for i in range(steps):
+                if loop == 5:         # DDIM's prescale_sample (src/samplers.h:27-59), before the denoiser sees x
+                    x = (x * coef[i, 5]).astype(f32)
+                den = self.denoise(x, float(sig[i]), cond, uncond)
+                hist = [ring[(i - k) % depth] if depth and k <= order[i] else None for k in range(4)]
+                x = multistep_update(forms[order[i]], x, den, hist, sig[i], coef[i], dcoef[i])
+                if on_step:
+                    on_step(i, x)
+            return x
         for i in range(steps):
             den = self.denoise(x, float(sig[i]), cond, uncond)
             if sampler == "euler":
@@ -234,13 +305,104 @@ class Txt2Img:
             s_up[i] = sigma_up
         return c_in, c_out, ts, s_arr, d_sigma, s_up
 
+    def multistep_table(self, sig: np.ndarray, sampler: str):
+        """Per-step scalars of a multistep sampler, as the reference's process_sample computes them (src/samplers.h, ORIGINAL_SAMPLER_ALGORITHMS;
+        the loop-invariant per-element coefficients hoisted with the same expression tree, every operation rounded to float; sigma_reshaper and
+        sigma_reshaper_sharp are the identity outside Turbo mode).  Returns (loop form, order [steps] int32, coef [steps, 6] float32 = k0..k4 of
+        the step's osg_multistep_form and DDIM's prescale factor of x, dcoef [steps, 2] float64 = DDIM's (a, b))."""
+        _check_sampler(sampler)
+        if sampler not in MULTISTEP:
+            raise ValueError(f"{sampler!r} is not a multistep sampler; those are: {', '.join(MULTISTEP)}")
+        steps = len(sig) - 1
+        order = np.zeros(steps, np.int32)
+        coef = np.zeros((steps, 6), f32)
+        coef[:, 5] = 1
+        dcoef = np.zeros((steps, 2), np.float64)
+        one, two = f32(1), f32(2)
+        dt_prev = None
+        for i in range(steps):
+            s, s1 = f32(sig[i]), f32(sig[i + 1])
+            sp = f32(sig[i - 1]) if i else None
+            if sampler in ("dpm++2m", "dpm++2mv2"):               # src/samplers.h:339-377, :543-582
+                if i == 0 or s1 == 0:
+                    with np.errstate(divide="ignore"):
+                        coef[i, :2] = f32(s1 / s), expm1f(f32(logf(s1) - logf(s)))       # log(0) = -inf, expm1(-inf) = -1 on the last step
+                    continue
+                t, t_next = f32(-logf(s)), f32(-logf(s1))
+                h = f32(t_next - t)
+                h_last = f32(t + logf(sp))
+                if sampler == "dpm++2m":
+                    b = expm1f(f32(-h))
+                    r = f32(h_last / h)
+                else:
+                    h_min = h if h < h_last else h_last                   # std::min / std::max
+                    h_max = h if h_last < h else h_last
+                    r = f32(h_max / h_min)
+                    b = expm1f(f32(-f32(f32(h_max + h_min) / two)))
+                inv = f32(one / f32(two * r))
+                order[i] = 1
+                coef[i, :4] = f32(s1 / s), b, f32(one + inv), inv
+            elif sampler in ("ipndm", "ipndm_v", "ipndm_vo"):          # src/samplers.h:688-940
+                h_n = f32(s1 - s)
+                o = order[i] = min(i, 3)
+                coef[i, 0] = h_n
+                if o == 0 or sampler == "ipndm" or (sampler == "ipndm_v" and o >= 2):     # forms that take h_n alone
+                    continue
+                h_n_1 = f32(s - sp)
+                q = f32(h_n / h_n_1)
+                if sampler == "ipndm_v":                                  # o == 1
+                    coef[i, 1:3] = f32(two + q), q
+                    continue
+                c1 = f32(f32(two + q) / two)
+                c2 = f32(f32(-q) / two)
+                if o == 1:
+                    coef[i, 1:3] = c1, c2
+                    continue
+                h_n_2 = f32(f32(sig[i - 1]) - f32(sig[i - 2]))
+                hh = f32(h_n + h_n_1)
+                temp = f32(f32(one - f32(f32(f32(h_n / f32(f32(3) * hh)) * f32(h_n * hh)) / f32(h_n_1 * f32(h_n_1 + h_n_2)))) / two)
+                r12 = f32(one + f32(h_n_1 / h_n_2))
+                if o == 2:
+                    coef[i, 1:4] = f32(c1 + temp), f32(c2 - f32(r12 * temp)), f32(f32(temp * h_n_1) / h_n_2)
+                    continue
+                h_n_3 = f32(f32(sig[i - 2]) - f32(sig[i - 3]))
+                hhh = f32(hh + h_n_2)
+                p = f32(f32(f32(one - f32(h_n / f32(f32(3) * hh))) / two)
+                        + f32(f32(f32(one - f32(h_n / f32(two * hh))) * h_n) / f32(f32(6) * hhh)))
+                num = f32(f32(h_n * hh) * hhh)
+                den = f32(f32(h_n_1 * f32(h_n_1 + h_n_2)) * f32(f32(h_n_1 + h_n_2) + h_n_3))
+                temp2 = f32(f32(p * num) / den)
+                g = f32(f32(h_n_1 * f32(h_n_1 + h_n_2)) / f32(h_n_2 * f32(h_n_2 + h_n_3)))
+                q12 = f32(h_n_1 / h_n_2)
+                coef[i, 1] = f32(f32(c1 + temp) + temp2)
+                coef[i, 2] = f32(f32(c2 - f32(r12 * temp)) - f32(f32(f32(one + q12) + g) * temp2))
+                coef[i, 3] = f32(f32(f32(temp * h_n_1) / h_n_2) + f32(f32(f32(q12 + f32(g * f32(one + f32(h_n_2 / h_n_3))))) * temp2))
+                coef[i, 4] = f32(f32(f32(f32(-temp2) * g) * h_n_1) / h_n_2)
+            elif sampler == "taylor3":                                    # src/samplers.h:942-987; sampler_history_dt = the previous dt
+                dt = f32(s1 - s)
+                o = order[i] = min(i, 2)
+                coef[i, 0] = dt
+                if o:                                                     # (at i = 0 the reference's 1 / dt_prev reads an unset float: unused)
+                    dd = f32(dt * dt)
+                    coef[i, 1:4] = f32(one / dt_prev), f32(dd / two), f32(f32(dd * dt) / f32(6))
+                dt_prev = dt
+            else:                                                         # ddim, src/samplers.h:1078-1100 and prescale_sample :27-59
+                root = sqrtf(f32(f32(s * s) + one))
+                coef[i, 5] = f32(root / s) if i == 0 else root
+                sn2 = float(f32(s1 * s1))
+                alpha = 1.0 / (sn2 + 1.0)
+                a = math.sqrt(1.0 - alpha) / float(s)
+                dcoef[i] = a, math.sqrt(alpha) - a
+        return MULTISTEP[sampler], order, coef, dcoef
+
     def sample_device(self, cond, uncond, steps: int = 20, seed: int = 42, latent_shape=(1, 4, 64, 64), guidance: float = 7.0,
                       init_latent: Optional[np.ndarray] = None, step_noise: Optional[Callable[[int], np.ndarray]] = None,
                       sampler: str = "euler_a") -> np.ndarray:
         """sample() with the whole loop enqueued on the GPU (HIP backend only): per step a scaling kernel fills the UNet's input staging,
         the captured pass is launched, and one kernel does eps -> denoised, the CFG combine and the Euler-Ancestral update -- no host
         round trip until the last step.  Same schedule, same random stream, same fp32 operation order as sample(): the two agree bit
-        for bit.  cond / uncond: one context each, or lists with one entry per prompt (latent_shape[0] prompts)."""
+        for bit.  The multistep samplers (MULTISTEP) run their update kernel (osg_sampler_cfg_multistep) with a history ring on the device.  cond / uncond: one context each, or lists with one entry per prompt (latent_shape[0] prompts)."""
+        _check_sampler(sampler)
         if not self.batched:
             raise RuntimeError("sample_device needs the HIP backend (batched=True)")
         n, P = self.names, latent_shape[0]
@@ -250,10 +412,11 @@ class Txt2Img:
         rng = np.random.default_rng(seed)
         x0 = rng.standard_normal(latent_shape, dtype=f32) if init_latent is None else np.asarray(init_latent, f32).reshape(latent_shape)
         x = np.ascontiguousarray(x0 * f32(sig[0]), f32)
-        noise = np.empty((steps,) + tuple(latent_shape), f32)
-        c_in, c_out, ts, s_arr, d_sigma, s_up = self.loop_scalars(sig, sampler)
-        for i in range(steps):
-            noise[i] = rng.standard_normal(latent_shape, dtype=f32) if step_noise is None else np.asarray(step_noise(i), f32).reshape(latent_shape)
+        c_in, c_out, ts, s_arr, d_sigma, s_up = self.loop_scalars(sig, "euler" if sampler in MULTISTEP else sampler)
+        if sampler not in MULTISTEP:
+            noise = np.empty((steps,) + tuple(latent_shape), f32)
+            for i in range(steps):
+                noise[i] = rng.standard_normal(latent_shape, dtype=f32) if step_noise is None else np.asarray(step_noise(i), f32).reshape(latent_shape)
         key = (id(self.unet), P)
         if self._dev_ready.get(key):
             for p in range(P):      # plan + captured pass exist: only the contexts change between images
@@ -266,6 +429,11 @@ class Txt2Img:
                 else:
                     self.denoise(x, float(sig[0]), conds[0], unconds[0], guidance)
             self._dev_ready[key] = True
+        if sampler in MULTISTEP:
+            loop, order, coef, dcoef = self.multistep_table(sig, sampler)
+            self.last_loop_ms = self.unet.hip_sampler_loop_multistep(n["sample"], n["timestep"], n["out"], x, loop, c_in, c_out, ts, s_arr, order, coef,
+                                                                     dcoef, guidance)
+            return x
         self.last_loop_ms = self.unet.hip_sampler_loop(n["sample"], n["timestep"], n["out"], x, noise, c_in, c_out, ts, s_arr, d_sigma, s_up, guidance)
         return x
 
