@@ -15,22 +15,8 @@
 // v_mfma_f32_16x16x32_f16, one RNE rounding): XnnPack::convolution, reference src/onnxstream.cpp:1292-1534.
 #include "osg_conv3x3_kernel.h"
 
-namespace {
-
-template <int W_>
-int launch3_bn(osg_ctx* ctx, GemmParams& p, int bn, int nl) {
-    if (nl == 8) {   // 8 loader waves (768 threads): a measured candidate only (osg_tune.h) -- the same arithmetic, twice the DMA issue slots
-        // (where the wider stages leave the LDS ring too short -- W = 8 with BN = 160 -- the 4-loader kernel runs instead)
-        if (bn == 80) { if constexpr (Geo<W_, 80, 8>::OK) return launch3<W_, 80, 4, 1, 0, 8>(ctx, p); }
-        else if (bn == 160) { if constexpr (Geo<W_, 160, 8>::OK) return launch3<W_, 160, 2, 2, 0, 8>(ctx, p); }
-        else { if constexpr (Geo<W_, 128, 8>::OK) return launch3<W_, 128, 2, 2, 0, 8>(ctx, p); }
-    }
-    if (bn == 80) return launch3<W_, 80, 4, 1>(ctx, p);
-    if (bn == 160) return launch3<W_, 160, 2, 2>(ctx, p);
-    return launch3<W_, 128, 2, 2>(ctx, p);
-}
-
-}  // namespace
+template <>
+int osg_mm::launch3_unit<0>(int entry, osg_ctx* ctx, GemmParams& p) { return launch3_in_unit<0>(entry, ctx, p); }
 
 int osg_conv3x3_supported(int N, int H, int W, int Cin, int Cout) {
     if (!(W == 64 || W == 32 || W == 16 || W == 8)) return 0;
@@ -93,8 +79,12 @@ std::vector<std::pair<double, std::pair<int, int>>> osg_conv3x3_rank(const osg_c
     return out;
 }
 
-// launch one configuration (reduce kernel included); p must have passed osg_conv3x3_prepare
+// launch one configuration (reduce kernel included); p must have passed osg_conv3x3_prepare.  The request resolves to an instantiation first (osg_gemm_routes.h
+// resolve3: 8 loader waves only where the ring stays deep enough, uint8 codes with 160 columns at W = 64 run 80), the split is sized for the tile that runs.
 int osg_conv3x3_launch(osg_ctx* ctx, GemmParams p, int bn, int s, int nl, int fold) {
+    const int entry = resolve3(p.W, bn, nl, p.w8 != 0);
+    if (entry < 0) OSG_FAIL(ctx, "osg_conv3x3: no kernel takes this image width");
+    bn = kV3Entries[entry].bn;
     const int slabs = p.Cin / 64;
     if (s < 1) s = 1;
     const int sl = (slabs + s - 1) / s;
@@ -109,13 +99,7 @@ int osg_conv3x3_launch(osg_ctx* ctx, GemmParams p, int bn, int s, int nl, int fo
         p.partial = (float*)ctx->ws;
     }
     p.n_major = (double)p.N * p.K * 2.0 > (double)p.a_bytes_l;
-    int rc;
-    if (p.w8) rc = osg_conv3x3_w8_tile(ctx, p, bn);   // (uint8 weight codes: osg_conv3x3_w8.hip, 4 loader waves)
-    else if (p.W == 64) rc = launch3_bn<64>(ctx, p, bn, nl);
-    else if (p.W == 32) rc = launch3_bn<32>(ctx, p, bn, nl);
-    else if (p.W == 16) rc = launch3_bn<16>(ctx, p, bn, nl);
-    else rc = launch3_bn<8>(ctx, p, bn, nl);
-    if (rc) return rc;
+    if (const int rc = kV3Entries[entry].wq ? launch3_unit<1>(entry, ctx, p) : launch3_unit<0>(entry, ctx, p)) return rc;
     if (p.splits > 1 && !p.fold_acc) return launch_splitk_reduce(ctx, p, 1);
     return 0;
 }

@@ -3,6 +3,7 @@
 #pragma once
 #include "osg_gemm_common.h"
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdlib>
 #include <type_traits>
@@ -396,7 +397,6 @@ int launch3(osg_ctx* ctx, GemmParams& p) {
     }
     p.mt = (p.M + 127) / 128;
     p.nt = (p.N + BN - 1) / BN;
-    if (MODE != 0) p.fold_acc = 0;
     p.no_epre = osg_mm::no_epi_prefetch();
     p.kdbg = kdbg_buffer(ctx, (long)p.mt * p.nt * p.splits);
     const osg_mm::StatSink sinks_in[2] = {p.sink[0], p.sink[1]};
@@ -410,6 +410,22 @@ int launch3(osg_ctx* ctx, GemmParams& p) {
     p.sink[0] = sinks_in[0]; p.sink[1] = sinks_in[1];
     OSG_LAUNCH_CHECK(ctx);
     return 0;
+}
+
+// the launchers of the kV3Entries (osg_gemm_routes.h) translation unit UNIT instantiates, indexed by entry (nullptr: another unit's)
+using V3Launch = int (*)(osg_ctx*, GemmParams&);
+template <int UNIT, int I>
+constexpr V3Launch v3_launcher() {
+    constexpr V3Entry e = kV3Entries[I];
+    if constexpr (v3_unit(e) == UNIT) return launch3<e.w, e.bn, e.wgm, e.wgn, 0, e.nlw, e.wq>;
+    else return nullptr;
+}
+template <int UNIT, size_t... I>
+constexpr std::array<V3Launch, kV3Count> v3_launchers(std::index_sequence<I...>) { return {v3_launcher<UNIT, (int)I>()...}; }
+template <int UNIT>
+int launch3_in_unit(int entry, osg_ctx* ctx, GemmParams& p) {
+    static constexpr std::array<V3Launch, kV3Count> table = v3_launchers<UNIT>(std::make_index_sequence<kV3Count>{});
+    return table[entry](ctx, p);
 }
 
 }  // namespace

@@ -216,6 +216,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
 
 }  // namespace
 #include "osg_gemm2.h"
+template <>
+int osg_mm::launch_v2_unit<0>(int entry, osg_ctx* ctx, GemmParams& p, int batch) { return launch_v2_in_unit<0>(entry, ctx, p, batch); }
 namespace {
 
 // The SD / SDXL conv_in and the VAE decoder's first convolution (3x3, Cin = 4: K = 36) on the matrix cores: the vector kernel this replaced (round 4) spent 288 FMAs + 288
@@ -383,10 +385,7 @@ int launch_cfg(osg_ctx* ctx, const GemmParams& p, int batch) {
 // and bounds every configuration (a 128x128x64 k-tile moves 32 KiB for 515 MFMA cycles), so the model is: k-tile time =
 // max(MFMA, bytes / 23) (+ ~450 exposed cycles when a block is alone on its CU), whole rounds of tiles over the CU slots,
 // a fixed fill + epilogue per round, and the extra pass of a split-K reduce.
-struct V2Choice { int cfg, nst, splits, ks = 1, fold = 0, spec = 0; };   // ks = 2: two wave groups on alternating k-tiles (gemm2_kernel KS); fold: split-K finished by splitk_fold_acc (no reduce launch); spec: 4 loader waves beside the 4 math waves (gemm2_kernel SPEC; round 6: the 128x128 and 128x160 tiles with a 4-stage ring)
-static const int kV2BM[8] = {128, 128, 64, 64, 128, 128, 64, 64}, kV2BN[8] = {128, 64, 64, 128, 160, 80, 80, 160};   // (64x128 and the round-6 tiles 4 .. 7 of osg_gemm_wide.hip: measured candidates only)
 // every legal (tile, stages, splits) with its modelled cost in cycles, cheapest first
-struct V2Form { bool conv = false, ln1 = false, ln2 = false, geglu = false, rowstats = false, w8 = false; };   // what the launch needs of an instantiation (the round-6 tiles hold a subset)
 static std::vector<std::pair<double, V2Choice>> rank_v2(const osg_ctx* ctx, int M, int N, int K, int batch, bool allow_split, V2Form form = V2Form{}) {
     const double cus = ctx->num_cu;
     const int kt = K / 64;
@@ -394,14 +393,9 @@ static std::vector<std::pair<double, V2Choice>> rank_v2(const osg_ctx* ctx, int 
     static const bool no_wide = getenv("OSG_TUNE_NO_WIDE") != nullptr;   // (A/B runs: the candidate set of round 5)
     for (int c = 0; c < (ctx->autotune ? (no_wide ? 4 : 8) : 3); c++)
         for (int nst = 8; nst >= 2; nst -= 2) {
+            if (!v2_holds(form, c, nst)) continue;                            // (an instantiation for the form: osg_gemm_routes.h)
             // 6 / 8 stages (every tile of a short-K GEMM in flight at once): only as a measured candidate, only where the ring fits the LDS
-            if (form.w8) {
-                if (!osg_mm::w8_tile_has(c, nst, form.conv) || (form.geglu && c >= 5)) continue;   // (the WQ = 1 instantiations, osg_gemm_w8.hip)
-                if ((nst == 6 || nst == 8) && !ctx->autotune) continue;
-            } else if (c < 4) {
-                if (nst == 6 && (!ctx->autotune || c == 0)) continue;
-                if (nst == 8 && (!ctx->autotune || c != 2)) continue;
-            } else if (!osg_mm::wide_tile_has(c, nst, form.conv, form.ln1, form.ln2, form.geglu, form.rowstats)) continue;
+            if ((nst == 6 || nst == 8) && !ctx->autotune) continue;
             if (c >= 4 && N % 80 != 0) continue;              // (the 80 / 160-column tiles are for the widths they divide)
             const int bnp = (kV2BN[c] + 31) / 32 * 32;
             const double tiles = (double)((M + kV2BM[c] - 1) / kV2BM[c]) * ((N + kV2BN[c] - 1) / kV2BN[c]) * batch;
@@ -451,9 +445,21 @@ static osg_tune::Key tune_key(const osg_ctx* ctx, int kind, const GemmParams& p,
 // a launch may be repeated for timing only when it does not consume its own output
 static bool tune_safe(const GemmParams& p) { return (const void*)p.C != (const void*)p.A && (const void*)p.C != (const void*)p.residual; }
 
-// launch one configuration (reduce kernel included)
+// what a launch needs of an instantiation (osg_gemm_routes.h)
+static V2Form v2_form(const GemmParams& p, bool conv) {
+    V2Form f;
+    f.conv = conv; f.ln1 = p.ln_c1 && !p.rs_in; f.ln2 = p.ln_c1 && p.rs_in; f.geglu = p.act == OSG_ACT_GEGLU; f.rowstats = p.rs_out != nullptr; f.w8 = p.w8 != 0;
+    f.nch = v2_nch(p.rs_np);
+    return f;
+}
+
+// launch one configuration: resolve it to an instantiation (osg_gemm_routes.h resolve_v2), size split-K for the tile that runs, launch, then the reduce launch
+// unless the split is folded in the kernel
 template <bool CONV>
 int launch_v2_choice(osg_ctx* ctx, GemmParams p, int batch, V2Choice ch) {
+    const V2Route r = resolve_v2(ch, v2_form(p, CONV));
+    if (r.entry < 0) OSG_FAIL(ctx, "osg_gemm: no kernel takes this form (LayerNorm or row statistics with uint8 weight codes, LayerNorm in a convolution)");
+    const V2Entry& e = kV2Entries[r.entry];
     const int ktiles = p.K / 64;
     int kt_per = (ktiles + ch.splits - 1) / ch.splits;
     p.splits = (ktiles + kt_per - 1) / kt_per;
@@ -462,104 +468,16 @@ int launch_v2_choice(osg_ctx* ctx, GemmParams p, int batch, V2Choice ch) {
     p.fold_acc = 0;
     if (p.splits > 1) {
         size_t need = (size_t)batch * p.splits * p.M * p.N * sizeof(float);
-        if (ch.fold && ch.ks == 1 && ch.cfg != 0 && ch.cfg != 4 && ch.cfg != 7) {
-            // finished inside the kernel by the last k-slice workgroup of each tile (osg_gemm_common.h splitk_fold_acc); the launch falls back to the reduce
-            // launch where the fold does not apply
-            const long n_tiles = (long)batch * ((p.M + kV2BM[ch.cfg] - 1) / kV2BM[ch.cfg]) * ((p.N + kV2BN[ch.cfg] - 1) / kV2BN[ch.cfg]);
-            need = std::max(need, osg_mm::splitk_fold_route(ctx, p, n_tiles, kV2BM[ch.cfg], kV2BN[ch.cfg]));
-        }
+        // finished inside the kernel by the last k-slice workgroup of each tile (osg_gemm_common.h splitk_fold_acc) where the route allows it, else by the reduce launch
+        if (r.fold) need = std::max(need, osg_mm::splitk_fold_route(ctx, p, (long)batch * ((p.M + e.bm - 1) / e.bm) * ((p.N + e.bn - 1) / e.bn), e.bm, e.bn));
         if (osg_ensure_workspace(ctx, need)) return 1;
         p.partial = (float*)ctx->ws;
     }
     // split the operand with more unique bytes across the XCDs (each private L2 then streams its slice from HBM once)
     const double a_unique = CONV ? (double)p.a_bytes : (double)p.M * p.K * 2.0;
     p.n_major = (double)p.N * p.K * (p.w8 ? 1.0 : 2.0) > a_unique;
-    int rc;
-    if (p.w8) {   // uint8 weight codes: the WQ = 1 instantiations (osg_gemm_w8.hip); a (tile, ring) they do not hold falls back to the 64x64 / 128x128 tile with 4 stages
-        if (ch.fold && (ch.cfg == 0 || ch.cfg == 4 || ch.cfg == 7)) p.fold_acc = 0;
-        rc = osg_mm::launch_v2_w8(ctx, p, batch, ch.cfg, ch.nst, CONV);
-        if (rc == -2) {
-            const int c2 = kV2BM[ch.cfg] == 128 ? 0 : 2;
-            if (c2 == 0) p.fold_acc = 0;
-            rc = osg_mm::launch_v2_w8(ctx, p, batch, c2, 4, CONV);
-        }
-        if (rc == -2) OSG_FAIL(ctx, "osg_gemm_w8: no kernel takes this form with uint8 weight codes");
-        if (rc) return rc;
-        if (p.splits > 1 && !p.fold_acc) return launch_splitk_reduce(ctx, p, batch);
-        return 0;
-    }
-    if (ch.cfg >= 4) {   // the round-6 tiles (osg_gemm_wide.hip); a form they do not hold falls back to the 64x64 / 128x128 tile of the same ring
-        rc = osg_mm::launch_v2_wide(ctx, p, batch, ch.cfg, ch.nst, CONV, ch.spec);
-        if (rc != -2) {
-            if (rc) return rc;
-            if (p.splits > 1 && !p.fold_acc) return launch_splitk_reduce(ctx, p, batch);
-            return 0;
-        }
-        ch.cfg = kV2BM[ch.cfg] == 128 ? 0 : 2; ch.nst = ch.nst == 2 ? 2 : 4; ch.ks = 1; ch.spec = 0;
-        if (p.fold_acc && ch.cfg == 0) p.fold_acc = 0;
-    }
-    if (p.ln_c1 && ch.cfg == 3) ch.cfg = 2;   // (the folded-LayerNorm variants exist for the first three tiles only)
-    if (ch.ks == 2 && (ch.cfg == 1 || ch.cfg == 2) && !(p.ln_c1 && !p.rs_in)) {
-        // two wave groups on alternating k-tiles: 64x64 (2- or 4-stage ring) and 128x64 (2 stages)
-        const bool t64 = ch.cfg == 2, deep = t64 && ch.nst >= 4;
-        if constexpr (!CONV) {
-            if (p.ln_c1) {
-                const int nch = p.rs_np >> 1;
-#define OSG_KS_LN2(NCH_)                                                                                                                        \
-    rc = !t64 ? launch_v2<128, 64, 2, false, 0, 0, 2, NCH_, 2>(ctx, p, batch)                                                                   \
-              : deep ? launch_v2<64, 64, 4, false, 0, 0, 2, NCH_, 2>(ctx, p, batch) : launch_v2<64, 64, 2, false, 0, 0, 2, NCH_, 2>(ctx, p, batch)
-                if (nch <= 5) OSG_KS_LN2(5);
-                else if (nch <= 10) OSG_KS_LN2(10);
-                else OSG_KS_LN2(20);
-#undef OSG_KS_LN2
-                return rc;
-            }
-        }
-        rc = !t64 ? launch_v2<128, 64, 2, CONV, 0, 0, 0, 5, 2>(ctx, p, batch)
-                  : deep ? launch_v2<64, 64, 4, CONV, 0, 0, 0, 5, 2>(ctx, p, batch) : launch_v2<64, 64, 2, CONV, 0, 0, 0, 5, 2>(ctx, p, batch);
-        if (rc) return rc;
-        if (p.splits > 1) return launch_splitk_reduce(ctx, p, batch);
-        return 0;
-    }
-    if constexpr (!CONV) {
-        if (ch.spec && ch.cfg == 0 && ch.nst == 4 && !(p.ln_c1 && !p.rs_in)) {   // 128x128, four loader waves (round 6)
-            p.fold_acc = 0;
-            if (p.ln_c1) {
-                const int nch = p.rs_np >> 1;
-                if (nch <= 5) rc = launch_v2<128, 128, 4, false, 0, 1, 2, 5>(ctx, p, batch);
-                else if (nch <= 10) rc = launch_v2<128, 128, 4, false, 0, 1, 2, 10>(ctx, p, batch);
-                else rc = launch_v2<128, 128, 4, false, 0, 1, 2, 20>(ctx, p, batch);
-            } else rc = launch_v2<128, 128, 4, false, 0, 1>(ctx, p, batch);
-            if (rc) return rc;
-            if (p.splits > 1) return launch_splitk_reduce(ctx, p, batch);
-            return 0;
-        }
-        if (p.ln_c1 && p.rs_in) {   // LayerNorm folded into the GEMM, row statistics handed over by the producer of A
-            const int nch = p.rs_np >> 1;
-#define OSG_LN2(NCH_)                                                                                                                                \
-    do {                                                                                                                                             \
-        if (ch.cfg == 0) rc = ch.nst == 4 ? launch_v2<128, 128, 4, false, 0, 0, 2, NCH_>(ctx, p, batch) : launch_v2<128, 128, 2, false, 0, 0, 2, NCH_>(ctx, p, batch); \
-        else if (ch.cfg == 1) rc = ch.nst == 4 ? launch_v2<128, 64, 4, false, 0, 0, 2, NCH_>(ctx, p, batch) : launch_v2<128, 64, 2, false, 0, 0, 2, NCH_>(ctx, p, batch); \
-        else rc = ch.nst == 4 ? launch_v2<64, 64, 4, false, 0, 0, 2, NCH_>(ctx, p, batch) : launch_v2<64, 64, 2, false, 0, 0, 2, NCH_>(ctx, p, batch);   \
-    } while (0)
-            if (nch <= 5) OSG_LN2(5);
-            else if (nch <= 10) OSG_LN2(10);
-            else OSG_LN2(20);
-#undef OSG_LN2
-            return rc;
-        }
-        if (p.ln_c1) {   // ... row statistics accumulated beside the MFMAs
-            if (ch.cfg == 0) rc = ch.nst == 4 ? launch_v2<128, 128, 4, false, 0, 0, 1>(ctx, p, batch) : launch_v2<128, 128, 2, false, 0, 0, 1>(ctx, p, batch);
-            else if (ch.cfg == 1) rc = ch.nst == 4 ? launch_v2<128, 64, 4, false, 0, 0, 1>(ctx, p, batch) : launch_v2<128, 64, 2, false, 0, 0, 1>(ctx, p, batch);
-            else rc = ch.nst == 4 ? launch_v2<64, 64, 4, false, 0, 0, 1>(ctx, p, batch) : launch_v2<64, 64, 2, false, 0, 0, 1>(ctx, p, batch);
-            return rc;
-        }
-    }
-    if (ch.cfg == 0) rc = ch.nst == 4 ? launch_v2<128, 128, 4, CONV>(ctx, p, batch) : launch_v2<128, 128, 2, CONV>(ctx, p, batch);
-    else if (ch.cfg == 1) rc = ch.nst == 6 ? launch_v2<128, 64, 6, CONV>(ctx, p, batch) : ch.nst == 4 ? launch_v2<128, 64, 4, CONV>(ctx, p, batch) : launch_v2<128, 64, 2, CONV>(ctx, p, batch);
-    else if (ch.cfg == 3) rc = ch.nst == 6 ? launch_v2<64, 128, 6, CONV>(ctx, p, batch) : ch.nst == 4 ? launch_v2<64, 128, 4, CONV>(ctx, p, batch) : launch_v2<64, 128, 2, CONV>(ctx, p, batch);
-    else rc = ch.nst == 8 ? launch_v2<64, 64, 8, CONV>(ctx, p, batch) : ch.nst == 6 ? launch_v2<64, 64, 6, CONV>(ctx, p, batch) : ch.nst == 4 ? launch_v2<64, 64, 4, CONV>(ctx, p, batch) : launch_v2<64, 64, 2, CONV>(ctx, p, batch);
-    if (rc) return rc;
+    static constexpr int (*units[4])(int, osg_ctx*, GemmParams&, int) = {launch_v2_unit<0>, launch_v2_unit<1>, launch_v2_unit<2>, launch_v2_unit<3>};
+    if (const int rc = units[v2_unit(e)](r.entry, ctx, p, batch)) return rc;
     if (p.splits > 1 && !p.fold_acc) return launch_splitk_reduce(ctx, p, batch);
     return 0;
 }
@@ -575,11 +493,9 @@ int run_gemm_v2(osg_ctx* ctx, GemmParams p, int batch, const V2Choice* forced) {
         const osg_tune::Key key = tune_key(ctx, CONV ? 2 : 0, p, batch);
         osg_tune::Choice tc;
         if (osg_tune::lookup(key, &tc)) {
-            ch = {tc.cfg & 7, tc.nst, tc.splits, (tc.cfg & 8) ? 2 : 1, (tc.cfg & 16) ? 1 : 0, (tc.cfg & 32) ? 1 : 0};
+            ch = tune_choice(tc.cfg, tc.nst, tc.splits);
         } else {
-            V2Form form;
-            form.conv = CONV; form.ln1 = p.ln_c1 && !p.rs_in; form.ln2 = p.ln_c1 && p.rs_in; form.geglu = p.act == OSG_ACT_GEGLU; form.rowstats = p.rs_out != nullptr; form.w8 = p.w8 != 0;
-            auto ranked = rank_v2(ctx, p.M, p.N, p.K, batch, allow_split, form);
+            auto ranked = rank_v2(ctx, p.M, p.N, p.K, batch, allow_split, v2_form(p, CONV));
             ch = ranked.empty() ? V2Choice{0, 4, 1} : ranked[0].second;
             if (!ctx->capturing && tune_safe(p) && !ranked.empty() && !osg_tune::frozen()) {
                 float best = -1.f;
@@ -591,9 +507,9 @@ int run_gemm_v2(osg_ctx* ctx, GemmParams p, int batch, const V2Choice* forced) {
                     if (us >= 0.f && (best < 0.f || us < best)) { best = us; ch = cand.second; }
                 }
                 if (best < 0.f) OSG_FAIL(ctx, "osg_gemm: autotune could not time any configuration");
-                osg_tune::store(key, osg_tune::Choice{0, ch.cfg | (ch.ks == 2 ? 8 : 0) | (ch.fold ? 16 : 0) | (ch.spec ? 32 : 0), ch.nst, ch.splits, 0, best});
+                osg_tune::store(key, osg_tune::Choice{0, tune_cfg(ch), ch.nst, ch.splits, 0, best});
             } else if (osg_tune::frozen())
-                osg_tune::remember(key, osg_tune::Choice{0, ch.cfg | (ch.ks == 2 ? 8 : 0) | (ch.fold ? 16 : 0) | (ch.spec ? 32 : 0), ch.nst, ch.splits, 0, -1.f});
+                osg_tune::remember(key, osg_tune::Choice{0, tune_cfg(ch), ch.nst, ch.splits, 0, -1.f});
         }
     } else {
         if (p.w8) {
@@ -1059,7 +975,7 @@ static int conv2d_route(osg_ctx* ctx, GemmParams& p, int N, int Cin, int Cout, i
                             const int s3 = c.second.second % 1000;
                             const float us = osg_tune::time_us(ctx, [&] { return osg_conv3x3_launch(ctx, p, c.second.first, s3, nl, fold3); });
                             if (dump3) fprintf(stderr, "[tune] conv3x3 N*H*W=%d Cin=%d Cout=%d W=%d: halo bn=%d splits=%d loaders=%d -> %.2f us\n", p.M, p.Cin, p.N, p.W, c.second.first, c.second.second, nl, us);
-                            if (us >= 0.f && (best < 0.f || us < best)) { best = us; tc = osg_tune::Choice{1, fold3 ? 16 : 0, nl, s3, c.second.first, us}; }
+                            if (us >= 0.f && (best < 0.f || us < best)) { best = us; tc = osg_tune::Choice{1, tune_cfg(V2Choice{0, nl, s3, 1, fold3}), nl, s3, c.second.first, us}; }
                         }
                     V2Form form3;
                     form3.conv = true; form3.w8 = p.w8 != 0;
@@ -1068,15 +984,15 @@ static int conv2d_route(osg_ctx* ctx, GemmParams& p, int N, int Cin, int Cout, i
                     for (auto& c : r2) {
                         const V2Choice ch = c.second;
                         const float us = osg_tune::time_us(ctx, [&] { return run_gemm<true>(ctx, p, 1, &ch); });
-                        if (us >= 0.f && (best < 0.f || us < best)) { best = us; tc = osg_tune::Choice{0, ch.cfg | (ch.ks == 2 ? 8 : 0) | (ch.fold ? 16 : 0), ch.nst, ch.splits, 0, us}; }
+                        if (us >= 0.f && (best < 0.f || us < best)) { best = us; tc = osg_tune::Choice{0, tune_cfg(ch), ch.nst, ch.splits, 0, us}; }
                     }
                     if (best < 0.f) OSG_FAIL(ctx, "osg_conv2d_nhwc: autotune could not time any configuration");
                     osg_tune::store(key, tc);
                 } else if (osg_tune::frozen())
                     osg_tune::remember(key, tc);
             }
-            if (tc.family == 1) return osg_conv3x3_launch(ctx, p, tc.bn, tc.splits, tc.nst == 8 ? 8 : 4, (tc.cfg & 16) ? 1 : 0);
-            const V2Choice ch{tc.cfg & 7, tc.nst, tc.splits, (tc.cfg & 8) ? 2 : 1, (tc.cfg & 16) ? 1 : 0};
+            const V2Choice ch = tune_choice(tc.cfg, tc.nst, tc.splits);
+            if (tc.family == 1) return osg_conv3x3_launch(ctx, p, tc.bn, tc.splits, tc.nst == 8 ? 8 : 4, ch.fold);
             return run_gemm<true>(ctx, p, 1, &ch);
         }
     }

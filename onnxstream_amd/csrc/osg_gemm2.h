@@ -1,8 +1,9 @@
-// libosgpu: the direct-to-LDS pipelined contraction kernel (gemm2_kernel) and its launcher, shared by the translation units that instantiate it
-// (osg_gemm.hip: the 128x128 / 128x64 / 64x64 / 64x128 tiles; osg_gemm_wide.hip, round 6: the 160- and 80-column tiles).
+// libosgpu: the direct-to-LDS pipelined contraction kernel (gemm2_kernel) and its launcher, shared by the translation units that instantiate it -- each the
+// entries of osg_gemm_routes.h that v2_unit assigns to it (osg_gemm.hip, osg_gemm_wide.hip, osg_gemm_w8.hip, osg_gemm_w8_conv.hip).
 #pragma once
 #include "osg_gemm_common.h"
 #include "osg_tune.h"
+#include <array>
 #include <type_traits>
 
 #ifndef OSG_GEMM_PIN
@@ -346,7 +347,6 @@ int launch_v2(osg_ctx* ctx, GemmParams& p, int batch) {
     }
     p.mt = (p.M + BM - 1) / BM;
     p.nt = (p.N + BN - 1) / BN;
-    if (KS == 2 || SPEC || LN != 0 || MODE != 0) p.fold_acc = 0;   // (the in-kernel split-K fold is the plain kernel's: a 256-thread protocol)
     dim3 grid((unsigned)(p.mt * p.nt * batch * p.splits));
     p.grid = (int)grid.x;
     p.no_epre = osg_mm::no_epi_prefetch();
@@ -364,6 +364,22 @@ int launch_v2(osg_ctx* ctx, GemmParams& p, int batch) {
     p.sink[0] = sinks_in[0]; p.sink[1] = sinks_in[1];
     OSG_LAUNCH_CHECK(ctx);
     return 0;
+}
+
+// the launchers of the kV2Entries (osg_gemm_routes.h) translation unit UNIT instantiates, indexed by entry (nullptr: another unit's)
+using V2Launch = int (*)(osg_ctx*, GemmParams&, int);
+template <int UNIT, int I>
+constexpr V2Launch v2_launcher() {
+    constexpr V2Entry e = kV2Entries[I];
+    if constexpr (v2_unit(e) == UNIT) return launch_v2<e.bm, e.bn, e.nst, e.conv != 0, 0, e.spec, e.ln, e.nch, e.ks, e.wgn, e.wq>;
+    else return nullptr;
+}
+template <int UNIT, size_t... I>
+constexpr std::array<V2Launch, kV2Count> v2_launchers(std::index_sequence<I...>) { return {v2_launcher<UNIT, (int)I>()...}; }
+template <int UNIT>
+int launch_v2_in_unit(int entry, osg_ctx* ctx, GemmParams& p, int batch) {
+    static constexpr std::array<V2Launch, kV2Count> table = v2_launchers<UNIT>(std::make_index_sequence<kV2Count>{});
+    return table[entry](ctx, p, batch);
 }
 
 }  // namespace

@@ -3,6 +3,7 @@
 #include <utility>
 #include <vector>
 #include "osg_common.h"
+#include "osg_gemm_routes.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -867,9 +868,15 @@ __device__ __forceinline__ bool splitk_fold_acc(const GemmParams& p, f32x4 (&acc
 }
 
 int launch_splitk_reduce(osg_ctx* ctx, const GemmParams& p, int batch);   // osg_gemm.hip
-// osg_gemm_wide.hip (round 6): tiles 4 .. 7 of the direct-to-LDS kernel -- 128 x 160, 128 x 80, 64 x 80, 64 x 160; -2 = no such instantiation
-int launch_v2_wide(osg_ctx* ctx, GemmParams& p, int batch, int tile, int nst, bool conv, int spec = 0);   // spec: four loader waves (tile 4, 4-stage ring)
-bool wide_tile_has(int tile, int nst, bool conv, bool ln1, bool ln2, bool geglu, bool rowstats);
+// launch entry `entry` of kV2Entries / kV3Entries (osg_gemm_routes.h): defined by the translation unit v2_unit / v3_unit names, which instantiates its entries
+template <int UNIT> int launch_v2_unit(int entry, osg_ctx* ctx, GemmParams& p, int batch);
+template <> int launch_v2_unit<0>(int entry, osg_ctx* ctx, GemmParams& p, int batch);   // osg_gemm.hip
+template <> int launch_v2_unit<1>(int entry, osg_ctx* ctx, GemmParams& p, int batch);   // osg_gemm_wide.hip
+template <> int launch_v2_unit<2>(int entry, osg_ctx* ctx, GemmParams& p, int batch);   // osg_gemm_w8.hip
+template <> int launch_v2_unit<3>(int entry, osg_ctx* ctx, GemmParams& p, int batch);   // osg_gemm_w8_conv.hip
+template <int UNIT> int launch3_unit(int entry, osg_ctx* ctx, GemmParams& p);
+template <> int launch3_unit<0>(int entry, osg_ctx* ctx, GemmParams& p);                // osg_conv3x3.hip
+template <> int launch3_unit<1>(int entry, osg_ctx* ctx, GemmParams& p);                // osg_conv3x3_w8.hip
 // the statistics a StatSink asks for, from the stored output (rows ldc apart) -- for the launches whose epilogue does not serve sinks (osg_norm.hip)
 int launch_colstats(osg_ctx* ctx, const f16* C, long ldc, int M, int N, int rows_per_image, const StatSink* sinks);
 long long* kdbg_buffer(osg_ctx* ctx, long workgroups);   // osg_ctx.hip: NULL unless OSG_KDBG is set
@@ -904,10 +911,3 @@ int osg_conv3x3_prepare(osg_ctx* ctx, osg_mm::GemmParams& p);
 std::vector<std::pair<double, std::pair<int, int>>> osg_conv3x3_rank(const osg_ctx* ctx, const osg_mm::GemmParams& p);
 int osg_conv3x3_launch(osg_ctx* ctx, osg_mm::GemmParams p, int bn, int splits, int loader_waves = 4, int fold = 0);   // fold: a 2 .. 4-way split finished by splitk_fold_acc
 int osg_conv3x3_supported(int N, int H, int W, int Cin, int Cout);
-// osg_conv3x3_w8.hip: the WQ = 1 instantiations of the halo kernel (uint8 weight codes, 4 loader waves); p.W in {64, 32, 16, 8}, bn in {80, 128, 160}
-int osg_conv3x3_w8_tile(osg_ctx* ctx, osg_mm::GemmParams& p, int bn);
-namespace osg_mm {
-// osg_gemm_w8.hip: the WQ = 1 instantiations of gemm2_kernel; -2 when the (tile, ring, form) asked for has none (tiles as kV2BM / kV2BN of osg_gemm.hip)
-int launch_v2_w8(osg_ctx* ctx, GemmParams& p, int batch, int tile, int nst, bool conv);
-bool w8_tile_has(int tile, int nst, bool conv);
-}

@@ -214,6 +214,12 @@ def test_160_column_tiles_geglu_layer_norm_fold_and_convolution(gpu, monkeypatch
         monkeypatch.setenv("OSG_GEMM_CFG", str(tile))
         got = gpu.conv2d_nhwc(dx, dwc, dbc, 2, (1, 1, 1, 1)).numpy()
         assert np.array_equal(got, base), (tile, rel_max(got, base.astype(np.float64)))
+    # 64 x 80 with a 2-stage ring is no convolution instantiation: the 64 x 64 tile runs, and a folded split is sized for it (osg_gemm_routes.h resolve_v2)
+    monkeypatch.setenv("OSG_GEMM_SPLITS", "2"); monkeypatch.setenv("OSG_GEMM_FOLD", "0"); monkeypatch.setenv("OSG_GEMM_CFG", "2")
+    base = gpu.conv2d_nhwc(dx, dwc, dbc, 2, (1, 1, 1, 1)).numpy()
+    monkeypatch.setenv("OSG_GEMM_NST", "2"); monkeypatch.setenv("OSG_GEMM_FOLD", "1"); monkeypatch.setenv("OSG_GEMM_CFG", "6")
+    got = gpu.conv2d_nhwc(dx, dwc, dbc, 2, (1, 1, 1, 1)).numpy()
+    assert np.array_equal(got.view(np.uint16), base.view(np.uint16))
 
 
 def test_two_wave_groups_conv_and_folded_layer_norm(gpu, monkeypatch):
@@ -405,6 +411,29 @@ def test_conv3x3_w8_halo_kernel(gpu, N, H, Cin, Cout, bn, splits, monkeypatch):
         assert np.array_equal(dense.numpy(), y.numpy())
         wv = wide.numpy()
         assert np.array_equal(wv[..., 32:32 + Cout], y.numpy()) and not wv[..., :32].any() and not wv[..., 32 + Cout:].any()
+
+
+@pytest.mark.timeout(180, method="thread")
+def test_conv3x3_w8_halo_kernel_folds_the_tile_it_runs(gpu, monkeypatch):
+    """uint8 codes with 160 columns at W = 64 run the 80-column tile (osg_gemm_routes.h resolve3): a split folded in the kernel is sized for that tile and gives the
+    bits of the reduce launch"""
+    rng = np.random.default_rng(64160)
+    N, H, Cin, Cout = 1, 64, 128, 320
+    x = rnd(rng, (N, H, H, Cin))
+    q, scale, zp, wd = _quant(rng, (Cout, 3, 3, Cin), (9 * Cin) ** -0.5)
+    bias, res = rnd(rng, (Cout,), 0.1), rnd(rng, (N, H, H, Cout))
+    dx, dq, db, dr = gpu.to_dev(x), gpu.to_dev(q), gpu.to_dev(bias), gpu.to_dev(res)
+    monkeypatch.setenv("OSG_CONV3X3_BN", "160"); monkeypatch.setenv("OSG_CONV3X3_SPLITS", "2")
+
+    def conv(fold):
+        monkeypatch.setenv("OSG_CONV3X3_FOLD", fold)
+        y = gpu.empty((N, H, H, Cout), f16)
+        gpu._ck(gpu.lib.osg_conv2d_nhwc_w8(gpu.ctx, dx.ptr, dq.ptr, scale, zp, db.ptr, 2, None, 0, dr.ptr, y.ptr, N, H, H, Cin, Cout, 3, 3, 1, 1, 1, 1, 1, 1, 0))
+        return y.numpy()
+    want = conv("0")
+    assert rel_max(want, ref.conv2d_nhwc(x, wd, bias, (1, 1), (1,) * 4).astype(np.float64) + res.astype(np.float64)) <= 1e-3
+    for _ in range(2):
+        assert np.array_equal(conv("1").view(np.uint16), want.view(np.uint16))
 
 
 def test_gemm_batched(gpu):
