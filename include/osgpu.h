@@ -199,6 +199,13 @@ int osg_gemm_ln(osg_ctx* ctx, const void* x, const void* w_nk_folded, const floa
  * every 32-column slot of every row: the hand-over to an osg_gemm_ln that normalises this output.  N % 32 == 0, K % 64 == 0. */
 int osg_gemm_rowstats(osg_ctx* ctx, const void* A, const void* B_nk, const void* bias, osg_dtype bias_dtype, const void* residual, void* C,
                       int M, int N, int K, osg_act act, float* rowstats);
+/* What the most recent contraction call on ctx ran (a host-side record, no device work; a tuner's timed candidates count as calls):
+ *   out[0] family: 0 gemm2_kernel, 1 conv3x3_kernel, 2 gemm_kernel (round 1), 3 conv_cin4_mfma_kernel; -1 none yet
+ *   out[1] instantiation: the index into kV2Entries (family 0) / kV3Entries (family 1) of osg_gemm_routes.h; family 2: tile | vec << 2 | conv << 3, tile
+ *          0 = 128 x 128, 1 = 128 x 64, 2 = 64 x 64; family 3: 0
+ *   out[2] the k-slices that ran;  out[3] 1 = the split was folded in the kernel
+ *   out[4] the reduce kernel that finished the split: 0 none, 1 splitk_reduce_kernel, 2 / 3 splitk_reduce4_kernel<4 / 8>, 4 / 5 splitk_reduce_stats_kernel<4 / 8> */
+int osg_last_route(const osg_ctx* ctx, int out[5]);
 
 /* Fused attention == the reference's AttentionFusedOps pseudo-op (onnxstream.cpp:6696-6929):
  * for each of `heads` items: O = softmax(scale * Q K^T) V, with Q:[heads,Tq,D], K given TRANSPOSED as the reference

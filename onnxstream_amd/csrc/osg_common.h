@@ -22,6 +22,8 @@ struct osg_ctx {
     struct PendingSink { long long* table = nullptr; int groups = 0, cpg = 0, ch_off = 0; } pending_sink[2];
     int pending_hw = 0;
     bool tuning = false, sink_fused = false;
+    // what the most recent contraction launch ran (osg_last_route): family, instantiation, k-slices, folded in the kernel, reduce kernel
+    int last_route[5] = {-1, -1, 0, 0, 0};
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
     // pinned double-buffered staging for host->device streaming (weights provider path)
     static constexpr int kStages = 2;
@@ -58,6 +60,12 @@ inline bool osg_first_on_device(unsigned long long& mask) {
     if ((mask >> dev) & 1ull) return false;
     mask |= 1ull << dev;
     return true;
+}
+
+// record what a contraction launch runs (osg_last_route); the reduce kernel, if one follows, is added by launch_splitk_reduce
+inline void osg_set_route(osg_ctx* ctx, int family, int instantiation, int splits, int fold) {
+    int* r = ctx->last_route;
+    r[0] = family; r[1] = instantiation; r[2] = splits; r[3] = fold; r[4] = 0;
 }
 
 struct osg_graph {

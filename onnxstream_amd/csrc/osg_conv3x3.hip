@@ -100,6 +100,7 @@ int osg_conv3x3_launch(osg_ctx* ctx, GemmParams p, int bn, int s, int nl, int fo
     }
     p.n_major = (double)p.N * p.K * 2.0 > (double)p.a_bytes_l;
     if (const int rc = kV3Entries[entry].wq ? launch3_unit<1>(entry, ctx, p) : launch3_unit<0>(entry, ctx, p)) return rc;
+    osg_set_route(ctx, 1, entry, p.splits, p.fold_acc);
     if (p.splits > 1 && !p.fold_acc) return launch_splitk_reduce(ctx, p, 1);
     return 0;
 }

@@ -234,6 +234,11 @@ int osg_set_autotune(osg_ctx* c, int on) {
 const char* osg_last_error(const osg_ctx* c) { return c ? c->err.c_str() : "null context"; }
 const char* osg_device_name(const osg_ctx* c) { return c ? c->name.c_str() : ""; }
 void* osg_stream(const osg_ctx* c) { return c ? (void*)c->compute : nullptr; }
+int osg_last_route(const osg_ctx* c, int out[5]) {
+    if (!c || !out) return 1;
+    for (int i = 0; i < 5; i++) out[i] = c->last_route[i];
+    return 0;
+}
 
 int osg_malloc(osg_ctx* c, size_t bytes, void** dptr) {
     if (c->capturing) OSG_FAIL(c, "osg_malloc inside graph capture");

@@ -478,6 +478,7 @@ int launch_v2_choice(osg_ctx* ctx, GemmParams p, int batch, V2Choice ch) {
     p.n_major = (double)p.N * p.K * (p.w8 ? 1.0 : 2.0) > a_unique;
     static constexpr int (*units[4])(int, osg_ctx*, GemmParams&, int) = {launch_v2_unit<0>, launch_v2_unit<1>, launch_v2_unit<2>, launch_v2_unit<3>};
     if (const int rc = units[v2_unit(e)](r.entry, ctx, p, batch)) return rc;
+    osg_set_route(ctx, 0, r.entry, p.splits, p.fold_acc);
     if (p.splits > 1 && !p.fold_acc) return launch_splitk_reduce(ctx, p, batch);
     return 0;
 }
@@ -586,6 +587,7 @@ int run_gemm(osg_ctx* ctx, GemmParams p, int batch, const V2Choice* forced = nul
     else rc = OSG_DISPATCH(64, 64);
 #undef OSG_DISPATCH
     if (rc) return rc;
+    osg_set_route(ctx, 2, cfg | (vec ? 4 : 0) | (CONV ? 8 : 0), splits, 0);
     if (splits > 1) return launch_splitk_reduce(ctx, p, batch);
     return 0;
 }
@@ -716,6 +718,7 @@ int osg_mm::launch_splitk_reduce(osg_ctx* ctx, const GemmParams& p, int batch) {
                                p.rb_rows, p.rb_ld, ldc_, p.C2, p.ldc2, p.sink[0], p.sink[1], p.sink_hw, imgs, per_xcd);
         OSG_LAUNCH_CHECK(ctx);
         ctx->sink_fused = true;
+        ctx->last_route[4] = p.splits <= 4 ? 4 : 5;
         return 0;
     }
     if (!scalar_only && p.N % 4 == 0 && (ldc_ & 3) == 0 && (p.ldc2 & 3) == 0 && (p.strideC & 3) == 0 && (p.rb_ld & 3) == 0 && (((uintptr_t)p.C | (uintptr_t)p.C2 | (uintptr_t)p.residual | (uintptr_t)p.rowbias) & 7) == 0 &&
@@ -728,11 +731,13 @@ int osg_mm::launch_splitk_reduce(osg_ctx* ctx, const GemmParams& p, int batch) {
             hipLaunchKernelGGL(splitk_reduce4_kernel<8>, dim3(blocks), dim3(256), 0, ctx->compute, p.partial, p.C, p.bias, p.bias_f32, p.residual, MN, p.N, p.splits, batch, p.strideC,
                                p.act, p.rowbias, p.rb_rows, p.rb_ld, ldc_, p.C2, p.ldc2);
         OSG_LAUNCH_CHECK(ctx);
+        ctx->last_route[4] = p.splits <= 4 ? 2 : 3;
         return 0;
     }
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->compute, p.partial, p.C,
                        p.bias, p.bias_f32, p.residual, MN, p.N, p.splits, batch, p.strideC, p.act, p.rowbias, p.rb_rows, p.rb_ld, p.ldc ? p.ldc : (long)p.N, p.C2, p.ldc2);
     OSG_LAUNCH_CHECK(ctx);
+    ctx->last_route[4] = 1;
     return 0;
 }
 
@@ -944,6 +949,7 @@ static int conv2d_route(osg_ctx* ctx, GemmParams& p, int N, int Cin, int Cout, i
         }
         hipLaunchKernelGGL(conv_cin4_mfma_kernel, dim3((p.M + 31) / 32), dim3(256), smem, ctx->compute, p);
         OSG_LAUNCH_CHECK(ctx);
+        osg_set_route(ctx, 3, 0, 1, 0);
         return 0;
     }
     // a 1x1 / stride 1 / no-pad convolution IS a plain GEMM over the pixels
