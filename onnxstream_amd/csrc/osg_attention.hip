@@ -619,6 +619,7 @@ int launch_attn2(osg_ctx* ctx, const AttnParams& p, int batch) {
     }
     const int nqb = qt2 ? (p.Tq + 127) / 128 : (p.Tq + 63) / 64;
     dim3 grid((unsigned)((long)nqb * batch * p.heads));
+    osg_set_kernel(ctx, 0, 2, D, NST, qt2 ? 2 : 1, 64, (int)grid.x);
     if (qt2) hipLaunchKernelGGL(k2, grid, dim3(256), smem, ctx->compute, p, nqb);
     else hipLaunchKernelGGL(k1, grid, dim3(256), smem, ctx->compute, p, nqb);
     OSG_LAUNCH_CHECK(ctx);
@@ -637,12 +638,14 @@ int launch_attn(osg_ctx* ctx, const AttnParams& p, int batch) {
     const bool wide = kWide && force_bkv == 128;
     if (p.Tq >= 1024 && force_qt != 1 && (blocks128 >= 2L * ctx->num_cu || force_qt == 2)) {
         dim3 grid((p.Tq + 127) / 128, batch * p.heads);
+        osg_set_kernel(ctx, 0, 1, DP, DT, 2, wide ? 128 : 64, (int)(grid.x * grid.y));
         if constexpr (kWide) {
             if (wide) hipLaunchKernelGGL((attn_kernel<DP, DT, 2, 128>), grid, dim3(256), 0, ctx->compute, p);
             else hipLaunchKernelGGL((attn_kernel<DP, DT, 2, 64>), grid, dim3(256), 0, ctx->compute, p);
         } else hipLaunchKernelGGL((attn_kernel<DP, DT, 2, 64>), grid, dim3(256), 0, ctx->compute, p);
     } else {
         dim3 grid((p.Tq + 63) / 64, batch * p.heads);
+        osg_set_kernel(ctx, 0, 1, DP, DT, 1, wide ? 128 : 64, (int)(grid.x * grid.y));
         if constexpr (kWide) {
             if (wide) hipLaunchKernelGGL((attn_kernel<DP, DT, 1, 128>), grid, dim3(256), 0, ctx->compute, p);
             else hipLaunchKernelGGL((attn_kernel<DP, DT, 1, 64>), grid, dim3(256), 0, ctx->compute, p);

@@ -24,6 +24,8 @@ struct osg_ctx {
     bool tuning = false, sink_fused = false;
     // what the most recent contraction launch ran (osg_last_route): family, instantiation, k-slices, folded in the kernel, reduce kernel
     int last_route[5] = {-1, -1, 0, 0, 0};
+    // what the most recent attention / normalisation launch ran (osg_last_kernel): family, then the family's fields (include/osgpu.h)
+    int last_kernel[8] = {-1, 0, 0, 0, 0, 0, 0, 0};
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
     // pinned double-buffered staging for host->device streaming (weights provider path)
     static constexpr int kStages = 2;
@@ -66,6 +68,12 @@ inline bool osg_first_on_device(unsigned long long& mask) {
 inline void osg_set_route(osg_ctx* ctx, int family, int instantiation, int splits, int fold) {
     int* r = ctx->last_route;
     r[0] = family; r[1] = instantiation; r[2] = splits; r[3] = fold; r[4] = 0;
+}
+
+// record what an attention / normalisation entry point launches (osg_last_kernel): plain host stores at launch time, nothing on the stream
+inline void osg_set_kernel(osg_ctx* ctx, int family, int a = 0, int b = 0, int c = 0, int d = 0, int e = 0, int f = 0, int g = 0) {
+    int* r = ctx->last_kernel;
+    r[0] = family; r[1] = a; r[2] = b; r[3] = c; r[4] = d; r[5] = e; r[6] = f; r[7] = g;
 }
 
 struct osg_graph {

@@ -240,6 +240,12 @@ int osg_last_route(const osg_ctx* c, int out[5]) {
     return 0;
 }
 
+int osg_last_kernel(const osg_ctx* c, int out[8]) {
+    if (!c || !out) return 1;
+    for (int i = 0; i < 8; i++) out[i] = c->last_kernel[i];
+    return 0;
+}
+
 int osg_malloc(osg_ctx* c, size_t bytes, void** dptr) {
     if (c->capturing) OSG_FAIL(c, "osg_malloc inside graph capture");
     OSG_HIP(c, hipSetDevice(c->device));

@@ -766,6 +766,7 @@ int osg_instance_norm(osg_ctx* ctx, osg_dtype dtype, const void* x, const float*
     if (rows <= 0 || L <= 0) return 0;
     if (n_scale <= 0) n_scale = 1;
     int threads = L >= 8192 ? 1024 : 256;
+    osg_set_kernel(ctx, 3, threads, (int)dtype);
     if (dtype == OSG_F16)
         hipLaunchKernelGGL(instance_norm_kernel<f16>, dim3(rows), dim3(threads), 0, ctx->compute, (const f16*)x, scale, bias, (f16*)y, L,
                            n_scale, eps);
@@ -797,6 +798,7 @@ int osg_group_norm_stats_nhwc(osg_ctx* ctx, const void* x, const void* gamma, co
         const int R = 256 / cv;
         constexpr int U = 4;
         const unsigned blocks = (unsigned)((HW + (long)R * U - 1) / ((long)R * U));
+        osg_set_kernel(ctx, 1, 6, 0, 256, 0, 1, (int)blocks);
         hipLaunchKernelGGL((gn_apply_stats_kernel<U>), dim3(blocks, N), dim3(256), 0, ctx->compute, (const f16*)x, (const long long*)stat_table, (f16*)y, HW, C, (int)act,
                            (const f16*)gamma, (const f16*)beta, G, eps);
         OSG_LAUNCH_CHECK(ctx);
@@ -806,6 +808,7 @@ int osg_group_norm_stats_nhwc(osg_ctx* ctx, const void* x, const void* gamma, co
     long slabs = HW / ((long)R * 4);
     if (slabs < 1) slabs = 1;
     if (slabs > 4096) slabs = 4096;
+    osg_set_kernel(ctx, 1, 5, 0, 256, 0, 1, (int)slabs);
     hipLaunchKernelGGL((gn_apply_kernel<f16, 2>), dim3((unsigned)slabs, N), dim3(256), G * 2 * sizeof(float), ctx->compute, (const f16*)x, (const float*)nullptr, (f16*)y,
                        HW, C, (int)act, (int)slabs, (const float*)stat_table, (const f16*)gamma, (const f16*)beta, G, 1, eps);
     OSG_LAUNCH_CHECK(ctx);
@@ -826,6 +829,7 @@ int osg_group_norm_nhwc(osg_ctx* ctx, osg_dtype dtype, const void* x, const void
     GnClusterPlan cp0;
     if (dtype == OSG_F16 && gn_slab_plan(HW, C, G, &sp) && !(sp.nv >= cl_min_nv && ctx->tickets && gn_cluster_plan(HW, C, G, N, ctx->num_cu, &cp0))) {
         const dim3 grid(G / sp.gb, N), block(sp.nt);
+        osg_set_kernel(ctx, 1, 0, sp.nv, sp.nt, sp.gb, 1);
 #define OSG_GN_SLAB(NV_)                                                                                                             \
     hipLaunchKernelGGL((gn_slab_kernel<NV_, false>), grid, block, 0, ctx->compute, (const f16*)x, (const f16*)gamma, (const f16*)beta, (f16*)y, \
                        (int)HW, C, C / G, sp.gb, eps, (int)act, 1, (double*)nullptr, (int*)nullptr, 0, osg_mm::kdbg_buffer(ctx, (long)grid.x * grid.y), \
@@ -844,6 +848,7 @@ int osg_group_norm_nhwc(osg_ctx* ctx, osg_dtype dtype, const void* x, const void
     if (dtype == OSG_F16 && ctx->tickets && gn_cluster_plan(HW, C, G, N, ctx->num_cu, &cp)) {
         if (osg_ensure_workspace(ctx, (size_t)N * G * cp.S * 2 * sizeof(double))) return 1;
         const dim3 grid(G / cp.gb, N, cp.S), block(cp.nt);
+        osg_set_kernel(ctx, 1, 1, cp.nv, cp.nt, cp.gb, cp.S);
         int* cnt = ctx->tickets + osg_ctx::kTickets / 2;   // (the lower half belongs to the split-K tickets)
         const int gn_wait = getenv("OSG_GN_CLUSTER_WAIT") ? atoi(getenv("OSG_GN_CLUSTER_WAIT")) : 20000;   // 10 ns ticks; 0 = nobody waits (tests: every block goes solo)
 #define OSG_GN_CL(NV_)                                                                                                               \
@@ -876,6 +881,7 @@ int osg_group_norm_nhwc(osg_ctx* ctx, osg_dtype dtype, const void* x, const void
     if (slabs_l < 1) slabs_l = 1;
     if (slabs_l > 4096) slabs_l = 4096;
     const int slabs = (int)slabs_l;
+    osg_set_kernel(ctx, 1, dtype != OSG_F16 ? 4 : (long)slabs * N <= 1024 ? 2 : 3, 0, 256, 0, S, slabs);
     if (dtype == OSG_F16) {
         hipLaunchKernelGGL(gn_stats_kernel<f16>, dim3(S, N), dim3(256), (G * 2 + 2 * 256 * 8) * sizeof(float), ctx->compute, (const f16*)x, part, HW, C, G, S);
         OSG_LAUNCH_CHECK(ctx);
@@ -909,6 +915,7 @@ int osg_layer_norm(osg_ctx* ctx, osg_dtype dtype, const void* x, const void* gam
     if (dtype == OSG_F16 && C % 8 == 0 && C <= 64 * 8 * 4) {
         dim3 grid((unsigned)((rows + 3) / 4)), block(256);
         int nv = (C + 511) / 512;
+        osg_set_kernel(ctx, 2, nv, (int)dtype);
 #define OSG_LN(NV) hipLaunchKernelGGL((layer_norm_kernel<f16, NV>), grid, block, 0, ctx->compute, (const f16*)x, (const f16*)gamma, \
                                       (const f16*)beta, (f16*)y, rows, C, eps)
         if (nv == 1) OSG_LN(1);
@@ -917,9 +924,11 @@ int osg_layer_norm(osg_ctx* ctx, osg_dtype dtype, const void* x, const void* gam
         else OSG_LN(4);
 #undef OSG_LN
     } else if (dtype == OSG_F16) {
+        osg_set_kernel(ctx, 2, 0, (int)dtype);
         hipLaunchKernelGGL(layer_norm_generic_kernel<f16>, dim3((unsigned)rows), dim3(256), 0, ctx->compute, (const f16*)x,
                            (const f16*)gamma, (const f16*)beta, (f16*)y, C, eps);
     } else if (dtype == OSG_F32) {
+        osg_set_kernel(ctx, 2, 0, (int)dtype);
         hipLaunchKernelGGL(layer_norm_generic_kernel<float>, dim3((unsigned)rows), dim3(256), 0, ctx->compute, (const float*)x,
                            (const float*)gamma, (const float*)beta, (float*)y, C, eps);
     } else

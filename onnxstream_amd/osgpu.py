@@ -24,7 +24,7 @@ EXPORTS = [
     "osg_device_count", "osg_init", "osg_destroy", "osg_last_error", "osg_device_name", "osg_stream", "osg_set_autotune", "osg_tune_misses",
     "osg_malloc", "osg_free", "osg_upload", "osg_upload_sync", "osg_host_register", "osg_host_unregister", "osg_upload_pinned", "osg_upload_pinned_async", "osg_copy_fence", "osg_download", "osg_copy", "osg_memset", "osg_sync",
     "osg_graph_begin", "osg_graph_end", "osg_graph_launch", "osg_graph_destroy", "osg_timer_start", "osg_timer_stop",
-    "osg_conv2d_nhwc", "osg_conv2d_nhwc_rb", "osg_conv2d_nhwc_v", "osg_gemm", "osg_gemm_ln", "osg_gemm_rowstats", "osg_last_route", "osg_gemm_w8", "osg_conv2d_nhwc_w8", "osg_gemm_w8_v", "osg_conv2d_nhwc_w8_v", "osg_transpose_kn_to_nk", "osg_attention", "osg_attention_strided", "osg_sdpa", "osg_rms_norm", "osg_rope",
+    "osg_conv2d_nhwc", "osg_conv2d_nhwc_rb", "osg_conv2d_nhwc_v", "osg_gemm", "osg_gemm_ln", "osg_gemm_rowstats", "osg_last_route", "osg_last_kernel", "osg_gemm_w8", "osg_conv2d_nhwc_w8", "osg_gemm_w8_v", "osg_conv2d_nhwc_w8_v", "osg_transpose_kn_to_nk", "osg_attention", "osg_attention_strided", "osg_sdpa", "osg_rms_norm", "osg_rope",
     "osg_instance_norm", "osg_group_norm_nhwc", "osg_layer_norm", "osg_reduce_mean_last", "osg_softmax_last",
     "osg_unary", "osg_binary", "osg_geglu", "osg_transpose", "osg_copy_2d", "osg_concat2", "osg_resize_nearest", "osg_gather_rows",
     "osg_maxpool_nhwc", "osg_convert", "osg_sampler_prepare", "osg_sampler_cfg_euler_a", "osg_sampler_cfg_multistep", "osg_sampler_prepare_rescale",
@@ -109,6 +109,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.osg_gemm_ln.argtypes = [vp, vp, vp, vp, vp, cf, vp, vp, vp, ci, ci, ci, ci]
     lib.osg_gemm_rowstats.argtypes = [vp, vp, vp, vp, ci, vp, vp, ci, ci, ci, ci, vp]
     lib.osg_last_route.argtypes = [vp, ctypes.POINTER(ci)]
+    lib.osg_last_kernel.argtypes = [vp, ctypes.POINTER(ci)]
     lib.osg_sampler_prepare.argtypes = [vp, vp, vp, vp, ci, cl, cf, cf, cl]
     lib.osg_sampler_cfg_euler_a.argtypes = [vp, vp, vp, vp, ci, cl, cf, cf, cf, cf, cf, cf]
     lib.osg_sampler_cfg_multistep.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, cl, cf, cf, cf, cf, cf, cf, cf, cf, ctypes.c_double, ctypes.c_double]
@@ -166,10 +167,19 @@ class DevBuf:
             self.gpu._ck(self.gpu.lib.osg_download(self.gpu.ctx, out.ctypes.data, self.ptr + lo * row * self.dtype.itemsize, out.nbytes))
         return out
 
+    def view(self, offset: int, shape) -> "DevBuf":
+        """`shape` elements of this buffer from element `offset` on, as a DevBuf that owns nothing (an out= between guard bands); valid while self is"""
+        v = DevBuf.__new__(DevBuf)
+        v.gpu, v.shape, v.dtype = self.gpu, tuple(int(s) for s in shape), self.dtype
+        v.nbytes = int(np.prod(v.shape, dtype=np.int64)) * self.dtype.itemsize
+        assert 0 <= offset and offset * self.dtype.itemsize + v.nbytes <= self.nbytes, (offset, shape, self.shape)
+        v.ptr, v.base = self.ptr + offset * self.dtype.itemsize, self
+        return v
+
     def free(self):
-        if self.ptr:
+        if self.ptr and getattr(self, "base", None) is None:
             self.gpu.lib.osg_free(self.gpu.ctx, self.ptr)
-            self.ptr = None
+        self.ptr = None
 
     def __del__(self):
         try:
@@ -214,6 +224,12 @@ class Gpu:
         """osg_last_route: (family, instantiation, k-slices, folded, reduce kernel) of the most recent contraction call"""
         r = (ctypes.c_int * 5)()
         self._ck(self.lib.osg_last_route(self.ctx, r))
+        return tuple(r)
+
+    def last_kernel(self):
+        """osg_last_kernel: what the most recent attention / GroupNorm / LayerNorm / InstanceNorm call launched (eight fields, include/osgpu.h)"""
+        r = (ctypes.c_int * 8)()
+        self._ck(self.lib.osg_last_kernel(self.ctx, r))
         return tuple(r)
 
     def to_dev(self, arr: np.ndarray, staged: bool = False) -> DevBuf:
@@ -332,10 +348,10 @@ class Gpu:
         self._ck(self.lib.osg_transpose_kn_to_nk(self.ctx, _NP2DT[w.dtype], w.ptr, o.ptr, k, n))
         return o
 
-    def attention(self, q: DevBuf, k: DevBuf, v: DevBuf, scale: float, k_is_dt: bool):
+    def attention(self, q: DevBuf, k: DevBuf, v: DevBuf, scale: float, k_is_dt: bool, out: Optional[DevBuf] = None):
         heads, tq, d = q.shape
         tkv = v.shape[1]
-        o = self.empty(q.shape, q.dtype)
+        o = self._out(out, q.shape, q.dtype)
         self._ck(self.lib.osg_attention(self.ctx, _NP2DT[q.dtype], q.ptr, k.ptr, v.ptr, o.ptr, heads, tq, tkv, d, scale, int(k_is_dt)))
         return o
 
@@ -348,6 +364,10 @@ class Gpu:
         self._ck(self.lib.osg_attention_strided(self.ctx, F16, q.ptr, c, d, tq * c, k.ptr, c, d, tkv * c, v.ptr, c, d, tkv * c, o.ptr, c, d,
                                                 tq * c, bsz, heads, tq, tkv, d, scale))
         return o
+
+    def attention_strided(self, q, k, v, o, batch: int, heads: int, tq: int, tkv: int, d: int, scale: float):
+        """osg_attention_strided on raw operands: q, k, v, o = (device address, token stride, head stride, batch stride), strides in elements"""
+        self._ck(self.lib.osg_attention_strided(self.ctx, F16, *q, *k, *v, *o, batch, heads, tq, tkv, d, scale))
 
     def tblock_kv_pack(self, k: DevBuf, v: DevBuf, heads: int):
         """k, v: [imgs, Tk, heads*D] -> (kp [imgs, heads, 80, DP], vtp [imgs, heads, DP, 80]) for tblock_tail.  Goes through the multi-job entry point the
@@ -429,10 +449,10 @@ class Gpu:
         self._ck(self.lib.osg_sdpa(self.ctx, _NP2DT[q.dtype], q.ptr, k.ptr, v.ptr, self._p(mask), o.ptr, bsz, hq, hkv, tq, tkv, d, scale))
         return o
 
-    def instance_norm(self, x: DevBuf, scale: Optional[DevBuf], bias: Optional[DevBuf], eps: float):
+    def instance_norm(self, x: DevBuf, scale: Optional[DevBuf], bias: Optional[DevBuf], eps: float, out: Optional[DevBuf] = None):
         rows, L = int(np.prod(x.shape[:-1])), x.shape[-1]
-        y = self.empty(x.shape, x.dtype)
-        ns = scale.size if scale is not None else 1
+        y = self._out(out, x.shape, x.dtype)
+        ns = scale.size if scale is not None else bias.size if bias is not None else 1
         self._ck(self.lib.osg_instance_norm(self.ctx, _NP2DT[x.dtype], x.ptr, self._p(scale), self._p(bias), y.ptr, rows, L, ns, eps))
         return y
 
@@ -440,21 +460,21 @@ class Gpu:
         """osg_set_stat_sinks: arm the NEXT conv2d_nhwc / conv2d_nhwc_view launch (tables: int64 [N][groups][2], zeroed by the caller)."""
         self._ck(self.lib.osg_set_stat_sinks(self.ctx, self._p(t0), groups0, cpg0, off0, self._p(t1), groups1, cpg1, off1, rows_per_image))
 
-    def group_norm_stats_nhwc(self, x: DevBuf, gamma: DevBuf, beta: DevBuf, groups: int, eps: float, table: DevBuf, act=ACT_NONE):
+    def group_norm_stats_nhwc(self, x: DevBuf, gamma: DevBuf, beta: DevBuf, groups: int, eps: float, table: DevBuf, act=ACT_NONE, out: Optional[DevBuf] = None):
         n, h, w, c = x.shape
-        y = self.empty(x.shape, x.dtype)
+        y = self._out(out, x.shape, x.dtype)
         self._ck(self.lib.osg_group_norm_stats_nhwc(self.ctx, x.ptr, gamma.ptr, beta.ptr, y.ptr, n, h * w, c, groups, eps, act, table.ptr))
         return y
 
-    def group_norm_nhwc(self, x: DevBuf, gamma: DevBuf, beta: DevBuf, groups: int, eps: float, act=ACT_NONE):
+    def group_norm_nhwc(self, x: DevBuf, gamma: DevBuf, beta: DevBuf, groups: int, eps: float, act=ACT_NONE, out: Optional[DevBuf] = None):
         n, h, w, c = x.shape
-        y = self.empty(x.shape, x.dtype)
+        y = self._out(out, x.shape, x.dtype)
         self._ck(self.lib.osg_group_norm_nhwc(self.ctx, _NP2DT[x.dtype], x.ptr, gamma.ptr, beta.ptr, y.ptr, n, h * w, c, groups, eps, act))
         return y
 
-    def layer_norm(self, x: DevBuf, gamma: DevBuf, beta: DevBuf, eps: float):
+    def layer_norm(self, x: DevBuf, gamma: DevBuf, beta: DevBuf, eps: float, out: Optional[DevBuf] = None):
         rows, c = int(np.prod(x.shape[:-1])), x.shape[-1]
-        y = self.empty(x.shape, x.dtype)
+        y = self._out(out, x.shape, x.dtype)
         self._ck(self.lib.osg_layer_norm(self.ctx, _NP2DT[x.dtype], x.ptr, gamma.ptr, beta.ptr, y.ptr, rows, c, eps))
         return y
 
