@@ -374,6 +374,26 @@ int osg_sampler_cfg_multistep(osg_ctx* ctx, int form, float* x, const float* eps
 int osg_sampler_prepare_rescale(osg_ctx* ctx, float* x, float* sample, float* timestep, int prompts, long L, float x_scale, float c_in, float t,
                                 long t_per_sample);
 
+/* ---- latents -> image on the device: what surrounds the VAE decoder pass ------------------------------------------ */
+/* The tile grid both entry points share (Txt2Img.decode_tiled, after sd_tiled_decoder src/sd.cpp:1258-1346): along an axis of n latent pixels the
+ * tile origins are min(k * (3*tile/4), n - tile) for k = 0 .. until n - tile is reached; T = Ty * Tx tiles per image in raster order (y outer, x
+ * inner), tile k of image p is sample p*T + k.  tile == H == W is the untiled decoder (T = 1).  H, W >= tile >= 1 (tile >= 2 unless H == W == tile). */
+/* slice_and_inf plus the latent scaling (src/sd.cpp:1261-1279, :2363, :2401-2418; untiled: decoder_solver :1193-1194):
+ *   tiles[p*T + k][c][y][x] = latents[p][c][oy_k + y][ox_k + x] * factor         one fp32 multiply, rounded once
+ * latents: device fp32 [images, 4, H, W]; tiles: device fp32 [images*T, 4, tile, tile] (the VAE plan's input staging). */
+int osg_decode_gather(osg_ctx* ctx, const float* latents, float* tiles, int images, int H, int W, int tile, float factor);
+/* blend plus substract_mean_normalize plus Mat::to_pixels (src/sd.cpp:1300-1326, :2449-2478, :322-364; untiled: decoder_solver :1251-1253).
+ * tiles: device fp32 [images*T, 3, up*tile, up*tile], the decoder's NCHW output.  For every output pixel, with d = 0 at the start, the tiles that
+ * cover it are folded in raster order:
+ *   f = qy * qx      qy = ly / ramp if the tile's y origin != 0 and its local row ly < ramp, else 1; qx alike; ramp = 2*tile*up/8
+ *   d = s*f + d*(1 - f)
+ * and then img = (d + 1) * 127.5.  Every quotient, product, sum and difference is rounded to fp32 on its own (no fma), f == 1 goes through the same
+ * arithmetic, so the result equals the host fold of Txt2Img.decode_tiled bit for bit (a NaN where the host has a NaN: inf * 0).
+ * image  (may be NULL): device fp32 [images, 3, up*H, up*W] <- img
+ * pixels (may be NULL): device uint8 [images, up*H, up*W, 3] <- (int)min(max(img, 0), 255): clamped in float, then truncated toward zero -- what
+ *   to_pixels' min(max((int)v, 0), 255) gives for every v whose (int) is defined; +inf gives 255, -inf gives 0 and NaN gives 0 (fmaxf(NaN, 0) = 0). */
+int osg_decode_blend(osg_ctx* ctx, const float* tiles, float* image, unsigned char* pixels, int images, int H, int W, int tile, int up);
+
 /* ---- data movement ------------------------------------------------------------------------------------------ */
 /* N-d transpose (XnnPack::transpose, onnxstream.cpp:1748): out.shape[i] = shape[perm[i]]. elem_size in {1,2,4,8}. */
 int osg_transpose(osg_ctx* ctx, int elem_size, const void* x, void* y, int rank, const long* shape, const int* perm);

@@ -228,6 +228,32 @@ class Model:
                     dcoef.size, guidance, ctypes.byref(ms)))
         return ms.value
 
+    def hip_decode(self, in_name: str, out_name: str, latents, factor: float, image=None, pixels=None) -> float:
+        """Latents -> image on the device (model_hip_decode): the latents are uploaded, scaled by `factor` and cut into the decoder's tiles, the
+        resident pass runs, the tiles are blended and (y + 1) * 127.5 applied -- one call, one host sync.  latents: float32 [images, 4, h, w].
+        image: a C-contiguous float32 array [images, 3, u*h, u*w] to fill, or None; pixels: a C-contiguous uint8 array [images, u*h, u*w, 3] to
+        fill, or None (what is None is neither made nor downloaded); a buffer of another size than the decode writes is refused.  The tile size and u are those of the resident plan, which must have been
+        built by a run() with images * tiles pushes (pipeline.Txt2Img.decode_device does all of this).  Returns the device ms."""
+        import numpy as np
+        f = self._lib.model_hip_decode
+        fp = ctypes.POINTER(ctypes.c_float)
+        f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, fp, fp,
+                      ctypes.c_ulonglong, ctypes.POINTER(ctypes.c_ubyte), ctypes.c_ulonglong, ctypes.POINTER(ctypes.c_double)]
+        f.restype = ctypes.c_void_p
+        lat = np.ascontiguousarray(latents, np.float32)
+        if lat.ndim != 4 or lat.shape[1] != 4:
+            raise OnnxStreamError("hip_decode: latents must be [images, 4, h, w]")
+        P, _, h, w = lat.shape
+        for a, dt, what in ((image, np.float32, "image"), (pixels, np.uint8, "pixels")):      # (the library checks the sizes: u is the plan's to know)
+            if a is not None and (a.dtype != dt or not a.flags.c_contiguous or not a.flags.writeable):
+                raise OnnxStreamError(f"hip_decode: {what} must be a writeable C-contiguous {np.dtype(dt).name} array of images * 3 * (u*h) * (u*w) elements")
+        ms = ctypes.c_double(0)
+        self._err(f(self._h, self._name(in_name), self._name(out_name), P, h, w, float(factor), lat.ctypes.data_as(fp),
+                    image.ctypes.data_as(fp) if image is not None else None, image.size if image is not None else 0,
+                    pixels.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)) if pixels is not None else None, pixels.size if pixels is not None else 0,
+                    ctypes.byref(ms)))
+        return ms.value
+
     def set_upcast_substrings(self, subs):
         """Model::m_requires_upcast (a std::function in C++, src/llm.cpp:379-383): ops whose name contains one of `subs` run in fp32.  Works on
         libonnxstream_amd.so (model_hip_set_upcast_substrings) and on the oracle build of the reference (ref_set_upcast_substrings)."""

@@ -353,6 +353,21 @@ char* model_hip_sampler_loop_multistep(Handle* h, char* sample_name, char* times
         return dup_cstr(e.what());
     }
 }
+// latents -> image on the device (decoder_solver / sd_tiled_decoder / sdxl_decoder around the VAE pass, src/sd.cpp:1174-1346, :2357-2516, and Mat::to_pixels
+// :340-364): latents [images, 4, h, w] fp32 host -> image [images, 3, u*h, u*w] fp32 and / or pixels [images, u*h, u*w, 3] uint8, either may be NULL (not
+// made, not downloaded).  The tile size and u come from the plan's input / output shapes; the plan must have been built by a run() with images * tiles pushes
+// (tiles: origins 0, 3t/4, ... and a last one flush with the border, per axis).  image_elems / pixels_elems: the elements the two buffers hold -- a buffer of
+// another size than the decode writes is refused, since u is the plan's to know.  *ms (may be NULL) receives the device time from gather to blend.
+char* model_hip_decode(Handle* h, char* in_name, char* out_name, int images, int lat_h, int lat_w, float factor, const float* latents, float* image,
+                       unsigned long long image_elems, unsigned char* pixels, unsigned long long pixels_elems, double* ms) {
+    try {
+        const double v = Plan::run_decode(h->model, in_name, out_name, images, lat_h, lat_w, factor, latents, image, (size_t)image_elems, pixels, (size_t)pixels_elems);
+        if (ms) *ms = v;
+        return nullptr;
+    } catch (const std::exception& e) {
+        return dup_cstr(e.what());
+    }
+}
 // steps and arena placement of the current plan (malloc'ed text, free with model_free_buffer); "ERROR: ..." on error
 char* model_hip_plan_info(Handle* h) {
     try {

@@ -388,6 +388,9 @@ Plan::~Plan() {
     if (samp_x) be.api.osg_free(be.ctx, samp_x);
     if (samp_noise) be.api.osg_free(be.ctx, samp_noise);
     if (samp_hist) be.api.osg_free(be.ctx, samp_hist);
+    if (dec_lat) be.api.osg_free(be.ctx, dec_lat);
+    if (dec_img) be.api.osg_free(be.ctx, dec_img);
+    if (dec_pix) be.api.osg_free(be.ctx, dec_pix);
     if (ring) be.free(ring);
     for (void* p : owned) be.free(p);
     if (arena && !arena_pooled) be.free(arena);

@@ -198,6 +198,16 @@ struct Plan {
                                              int n_steps, int prompts, int sampler, float* x, const float* c_in, const float* c_out, const float* t,
                                              const float* sigma, const int* order, const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef,
                                              float guidance);
+    // latents -> image without leaving the device (the VAE decoder plan): upload the latents [images, 4, H, W], osg_decode_gather cuts and scales the
+    // tiles into the input staging, the pass (captured, or eager while no graph exists), osg_decode_blend folds the tiles and makes the fp32 image
+    // [images, 3, u*H, u*W] and / or the packed uint8 image [images, u*H, u*W, 3]; only the one(s) asked for (non-NULL) come back.  Tile size t and
+    // upscale factor u are the plan's own input / output shapes; the plan's batch must be images * tiles.  Returns the device ms from gather to blend.
+    // image_elems / pixels_elems: what the caller's buffers hold; a non-NULL buffer of another size than the decode writes is refused (the caller cannot know u).
+    double decode_tiles(const std::string& in_name, const std::string& out_name, int images, int H, int W, float factor, const float* latents, float* image,
+                        size_t image_elems, uint8_t* pixels, size_t pixels_elems);
+    // the same on Model m's plan (model_hip_decode); a static member for the reason given at run_sampler_loop_multistep
+    static double run_decode(Model& m, const std::string& in_name, const std::string& out_name, int images, int H, int W, float factor, const float* latents,
+                             float* image, size_t image_elems, uint8_t* pixels, size_t pixels_elems);
     // eager pass with HIP events around every step, `reps` times; "ms<TAB>flops<TAB>bytes<TAB>what" per line (ms = mean)
     std::string profile(int reps);
     // plan introspection for the CPU tests of the host logic (tests/test_planner_cpu.py): one line per step
@@ -281,6 +291,10 @@ struct Plan {
     void* samp_noise = nullptr;
     void* samp_hist = nullptr;    // sampler_loop_multistep: history ring [H, prompts, L], device fp32
     size_t samp_x_bytes = 0, samp_noise_bytes = 0, samp_hist_bytes = 0;
+    void* dec_lat = nullptr;      // decode_tiles state: latents [images, 4, H, W] fp32, image [images, 3, uH, uW] fp32, pixels [images, uH, uW, 3] uint8
+    void* dec_img = nullptr;
+    void* dec_pix = nullptr;
+    size_t dec_lat_bytes = 0, dec_img_bytes = 0, dec_pix_bytes = 0;
 
     osg_graph* graph = nullptr;
     Lowering* lowering = nullptr;  // kept alive: the launch closures capture it

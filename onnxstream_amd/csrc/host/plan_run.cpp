@@ -619,6 +619,86 @@ double Plan::run_sampler_loop_multistep(Model& m, const std::string& sample_name
     return ms;
 }
 
+double Plan::decode_tiles(const std::string& in_name, const std::string& out_name, int images, int H, int W, float factor, const float* latents,
+                          float* image, size_t image_elems, uint8_t* pixels, size_t pixels_elems) {
+    static const char* fn = "Model::hip_decode: ";
+    if (runs < 1) throw std::runtime_error(std::string(fn) + "run() once first (the plan must have run a pass of this batch).");
+    if (stream_weights) throw std::runtime_error(std::string(fn) + "not available in streamed-weights mode.");
+    if (u8) throw std::runtime_error(std::string(fn) + "not available with uint8 arithmetic.");
+    const In* in = nullptr;
+    for (auto& i : inputs)
+        if (i.name == in_name) in = &i;
+    const Out* out = nullptr;
+    for (auto& o : outputs)
+        if (o.name == out_name) out = &o;
+    if (!in || !out) throw std::invalid_argument(std::string(fn) + "input/output tensor not found.");
+    if (out->raw16) throw std::invalid_argument(std::string(fn) + "the output is excluded from the fp32 conversion (m_outputs_convert_set).");
+    // tile size and upscale factor are the plan's own: input [1, 4, t, t] fp32, output [1, 3, u*t, u*t]
+    const auto& is = in->shape;
+    const auto& os = out->shape;
+    if (in->host_type != TensorDataType::float32 || is.size() != 4 || is[0] != 1 || is[1] != 4 || is[2] != is[3] || is[2] < 1)
+        throw std::invalid_argument(std::string(fn) + "the input must be a float32 tensor [1, 4, t, t].");
+    if (os.size() != 4 || os[0] != 1 || os[1] != 3 || os[2] != os[3] || !vals[out->f32val].batched)
+        throw std::invalid_argument(std::string(fn) + "the output must be a tensor [1, 3, s, s] per sample.");
+    const long t = (long)is[2], s = (long)os[2];
+    if (s < t || s % t)
+        throw std::invalid_argument(std::string(fn) + "the output's spatial size " + std::to_string(s) + " is not an integer multiple of the tile " + std::to_string(t) + ".");
+    const long up = s / t;
+    if (images < 1) throw std::invalid_argument(std::string(fn) + "needs at least one image.");
+    if (H < t || W < t)
+        throw std::invalid_argument(std::string(fn) + "latents of " + std::to_string(H) + " x " + std::to_string(W) + " are smaller than the tile " + std::to_string(t) + ".");
+    if (t < 2 && (H != t || W != t)) throw std::invalid_argument(std::string(fn) + "a tile of 1 cannot be stepped over larger latents.");
+    // the tile grid of osg_decode_gather / osg_decode_blend (include/osgpu.h): origins min(k * (3t/4), n - t)
+    auto along = [&](long n) { const long step = t * 3 / 4; return n == t ? 1L : (n - t + step - 1) / step + 1; };
+    const long T = along(H) * along(W);
+    if ((long)images * T != N)
+        throw std::invalid_argument(std::string(fn) + "the plan's batch is " + std::to_string(N) + ", the decode needs images * tiles = " + std::to_string(images) + " * " +
+                                    std::to_string(T) + " = " + std::to_string((long)images * T) + " samples.");
+    const size_t lb = (size_t)images * 4 * H * W * sizeof(float), px = (size_t)images * 3 * (H * up) * (W * up);
+    if (image && image_elems != px)
+        throw std::invalid_argument(std::string(fn) + "the image buffer holds " + std::to_string(image_elems) + " elements, the decode writes " + std::to_string(px) +
+                                    " (upscale factor " + std::to_string(up) + ").");
+    if (pixels && pixels_elems != px)
+        throw std::invalid_argument(std::string(fn) + "the pixel buffer holds " + std::to_string(pixels_elems) + " elements, the decode writes " + std::to_string(px) +
+                                    " (upscale factor " + std::to_string(up) + ").");
+    if (!image && !pixels) return 0.0;
+    FlightGuard flight(in_flight);
+    auto grow = [&](void*& p, size_t& have, size_t need) {
+        if (have >= need) return;
+        if (p) be.check(be.api.osg_free(be.ctx, p), "osg_free");
+        p = nullptr;
+        have = 0;
+        be.check(be.api.osg_malloc(be.ctx, need, &p), "osg_malloc");
+        have = need;
+    };
+    grow(dec_lat, dec_lat_bytes, lb);
+    if (image) grow(dec_img, dec_img_bytes, px * sizeof(float));
+    if (pixels) grow(dec_pix, dec_pix_bytes, px);
+    be.check(be.api.osg_upload(be.ctx, dec_lat, latents, lb), "osg_upload");
+    be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");
+    be.check(be.api.osg_decode_gather(be.ctx, (const float*)dec_lat, (float*)ptr(in->staging), images, H, W, (int)t, factor), "osg_decode_gather");
+    if (graph) be.check(be.api.osg_graph_launch(be.ctx, graph), "osg_graph_launch");
+    else run_steps();
+    be.check(be.api.osg_decode_blend(be.ctx, (const float*)ptr(out->f32val), image ? (float*)dec_img : nullptr, pixels ? (unsigned char*)dec_pix : nullptr, images, H, W,
+                                     (int)t, (int)up),
+             "osg_decode_blend");
+    float ms = 0;
+    be.check(be.api.osg_timer_stop(be.ctx, &ms), "osg_timer_stop");
+    if (image) be.check(be.api.osg_download(be.ctx, image, dec_img, px * sizeof(float)), "osg_download");
+    if (pixels) be.check(be.api.osg_download(be.ctx, pixels, dec_pix, px), "osg_download");
+    runs++;
+    m_last_ms = ms;
+    return ms;
+}
+
+double Plan::run_decode(Model& m, const std::string& in_name, const std::string& out_name, int images, int H, int W, float factor, const float* latents,
+                        float* image, size_t image_elems, uint8_t* pixels, size_t pixels_elems) {
+    if (!m.m_plan) throw std::runtime_error("Model::hip_decode: no plan (call run() first).");
+    const double ms = m.m_plan->decode_tiles(in_name, out_name, images, H, W, factor, latents, image, image_elems, pixels, pixels_elems);
+    m.m_last_ms = m.m_plan->last_ms();
+    return ms;
+}
+
 std::string Plan::info() const {
     std::string out;
     char buf[128];

@@ -28,6 +28,7 @@ EXPORTS = [
     "osg_instance_norm", "osg_group_norm_nhwc", "osg_layer_norm", "osg_reduce_mean_last", "osg_softmax_last",
     "osg_unary", "osg_binary", "osg_geglu", "osg_transpose", "osg_copy_2d", "osg_concat2", "osg_resize_nearest", "osg_gather_rows",
     "osg_maxpool_nhwc", "osg_convert", "osg_sampler_prepare", "osg_sampler_cfg_euler_a", "osg_sampler_cfg_multistep", "osg_sampler_prepare_rescale",
+    "osg_decode_gather", "osg_decode_blend",
     "osg_range_push", "osg_range_pop", "osg_marker_record", "osg_copy_wait_marker", "osg_timer_mark", "osg_timer_between", "osg_set_stat_sinks", "osg_group_norm_stats_nhwc", "osg_qu8_conv2d_nhwc", "osg_qu8_conv2d_nhwc_t", "osg_qu8_conv_tap_sums", "osg_qu8_gemm", "osg_qu8_lut", "osg_qu8_binary", "osg_qu8_instance_norm", "osg_qu8_instance_norm_nhwc", "osg_qu8_affine_act", "osg_qu8_norm_affine_act_nhwc", "osg_qu8_softmax_last", "osg_kdbg_read",
     "osg_tblock_tail_supported", "osg_tblock_tail", "osg_tblock_kv_pack_elems", "osg_tblock_kv_pack_jobs", "osg_tblock_pack_weight", 
 ]
@@ -114,6 +115,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.osg_sampler_cfg_euler_a.argtypes = [vp, vp, vp, vp, ci, cl, cf, cf, cf, cf, cf, cf]
     lib.osg_sampler_cfg_multistep.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, cl, cf, cf, cf, cf, cf, cf, cf, cf, ctypes.c_double, ctypes.c_double]
     lib.osg_sampler_prepare_rescale.argtypes = [vp, vp, vp, vp, ci, cl, cf, cf, cf, cl]
+    lib.osg_decode_gather.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf]
+    lib.osg_decode_blend.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci]
     lib.osg_set_stat_sinks.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, ci]
     lib.osg_group_norm_stats_nhwc.argtypes = [vp, vp, vp, vp, vp, ci, ctypes.c_long, ci, ci, cf, ci, vp]
     lib.osg_qu8_conv2d_nhwc.argtypes = [vp, vp, cf, ci, vp, cf, ci, vp, cf, ci, vp] + [ci] * 13
@@ -566,6 +569,35 @@ class Gpu:
         y = self.empty(x.shape, dtype)
         self._ck(self.lib.osg_convert(self.ctx, _NP2DT[x.dtype], _NP2DT[np.dtype(dtype)], x.ptr, y.ptr, x.size, scale, zero_point))
         return y
+
+    # ---- latents -> image around the VAE decoder pass ----
+    @staticmethod
+    def decode_tiles_along(n: int, tile: int) -> int:
+        """number of tile origins along an axis of n latent pixels (0, 3*tile/4, ..., the last one flush with the border)"""
+        step = tile * 3 // 4
+        return 1 if n == tile else (n - tile + step - 1) // step + 1
+
+    def decode_gather(self, latents: DevBuf, tile: int, factor: float, out: Optional[DevBuf] = None) -> DevBuf:
+        """osg_decode_gather: latents [P,4,H,W] float32 -> the scaled tiles [P*T,4,tile,tile]"""
+        P, c, H, W = latents.shape
+        assert c == 4 and latents.dtype == np.float32
+        T = self.decode_tiles_along(H, tile) * self.decode_tiles_along(W, tile)
+        y = self._out(out, (P * T, 4, tile, tile), np.float32)
+        self._ck(self.lib.osg_decode_gather(self.ctx, latents.ptr, y.ptr, P, H, W, tile, factor))
+        return y
+
+    def decode_blend(self, tiles: DevBuf, images: int, H: int, W: int, tile: int, want: str = "both", image: Optional[DevBuf] = None,
+                     pixels: Optional[DevBuf] = None):
+        """osg_decode_blend: decoder outputs [P*T,3,up*tile,up*tile] float32 -> (image [P,3,up*H,up*W] float32 or None, pixels [P,up*H,up*W,3]
+        uint8 or None); want = "f32" | "u8" | "both" """
+        assert want in ("f32", "u8", "both") and tiles.dtype == np.float32 and tiles.shape[1] == 3 and tiles.shape[2] % tile == 0
+        up = tiles.shape[2] // tile
+        T = self.decode_tiles_along(H, tile) * self.decode_tiles_along(W, tile)
+        assert tiles.shape == (images * T, 3, up * tile, up * tile), (tiles.shape, images, T, up, tile)
+        img = self._out(image, (images, 3, up * H, up * W), np.float32) if want != "u8" else None
+        pix = self._out(pixels, (images, up * H, up * W, 3), np.uint8) if want != "f32" else None
+        self._ck(self.lib.osg_decode_blend(self.ctx, tiles.ptr, self._p(img), self._p(pix), images, H, W, tile, up))
+        return img, pix
 
     # ---- uint8 arithmetic (a uint8 tensor = codes DevBuf + (scale, zero_point)) ----
     def qu8_conv_tap_sums(self, w: DevBuf) -> DevBuf:

@@ -145,6 +145,58 @@ def load_latents(path: str, h: int = 64, w: int = 64) -> np.ndarray:
     return v.reshape(1, 4, h, w).astype(f32)
 
 
+def tile_origins(n: int, tile: int) -> List[int]:
+    """Origins of the decoder tiles along an axis of n latent pixels (sd_tiled_decoder's loop, src/sd.cpp:1328-1340, for any n and tile): 0, step,
+    2 * step, ... with step = 3 * tile / 4, and a last one flush with the border -- [0, 24, 32] for (64, 32), [0, 24, 28] for (60, 32), where three
+    tiles overlap."""
+    if n < tile or tile < 1 or (tile < 2 and n != tile):
+        raise ValueError(f"no tiles of {tile} over {n} latent pixels")
+    step, o, v = (tile * 3) // 4, [], 0
+    while True:
+        v = min(v, n - tile)
+        o.append(v)
+        if v == n - tile:
+            return o
+        v += step
+
+
+def blend_fold(tiles: np.ndarray, H: int, W: int, tile: int, up: int) -> np.ndarray:
+    """The blend of decode_tiled() stated per OUTPUT PIXEL, as osg_decode_blend computes it (include/osgpu.h): tiles [P*T, C, up*tile, up*tile] (tile k of
+    image p = entry p*T + k, raster order) -> image [P, C, up*H, up*W].  Every pixel starts from d = 0 and folds the tiles that cover it in raster order:
+    f = qy * qx with qy = ly / ramp where the tile's y origin != 0 and its local row ly < ramp (else 1), qx alike, ramp = 2 * tile * up / 8;
+    d = s * f + d * (1 - f); at the end (d + 1) * 127.5.  Every operation is rounded to float32 on its own; f == 1 goes through the same arithmetic."""
+    tiles = np.asarray(tiles, f32)
+    oy, ox = tile_origins(H, tile), tile_origins(W, tile)
+    T, ts, ramp = len(oy) * len(ox), tile * up, 2 * tile * up // 8
+    P, C = tiles.shape[0] // T, tiles.shape[1]
+    if tiles.shape != (P * T, C, ts, ts):
+        raise ValueError(f"blend_fold: {tiles.shape} is not [P * {T}, C, {ts}, {ts}]")
+    Y, X = np.arange(H * up)[:, None], np.arange(W * up)[None, :]
+    d = np.zeros((P, C, H * up, W * up), f32)
+    s = np.zeros_like(d)
+    with np.errstate(invalid="ignore", divide="ignore"):     # (inf * 0 is a NaN on the device too; ramp = 0 below 4 output pixels per tile: no ramp)
+        for ky, y0 in enumerate(oy):
+            ly = Y - y0 * up
+            qy = np.where((ky != 0) & (ly < ramp), ly.astype(f32) / f32(ramp), f32(1.0)).astype(f32)
+            for kx, x0 in enumerate(ox):
+                lx = X - x0 * up
+                qx = np.where((kx != 0) & (lx < ramp), lx.astype(f32) / f32(ramp), f32(1.0)).astype(f32)
+                f = (qy * qx).astype(f32)
+                s[:, :, y0 * up:y0 * up + ts, x0 * up:x0 * up + ts] = tiles[ky * len(ox) + kx::T]
+                cover = (ly >= 0) & (ly < ts) & (lx >= 0) & (lx < ts)
+                d = np.where(cover, s * f + d * (f32(1.0) - f), d)
+        return ((d + f32(1.0)) * f32(127.5)).astype(f32)
+
+
+def to_pixels(img: np.ndarray) -> np.ndarray:
+    """Mat::to_pixels (src/sd.cpp:340-364): float image [..., 3, h, w] -> packed 8-bit RGB [..., h, w, 3], each value min(max((int)v, 0), 255) --
+    truncated toward zero, then clamped.  Clamping in float first gives the same for every v whose (int) is defined and settles the rest as
+    osg_decode_blend does: +inf -> 255, -inf -> 0, NaN -> 0."""
+    v = np.asarray(img, f32)
+    v = np.where(np.isnan(v), f32(0.0), np.clip(v, f32(0.0), f32(255.0)))
+    return np.ascontiguousarray(np.moveaxis(v.astype(np.int32).astype(np.uint8), -3, -1))
+
+
 class Txt2Img:
     def __init__(self, library: str, unet_dir: str, vae_dir: Optional[str], batched: bool = True, device: int = 0,
                  names: Dict[str, str] = None, fusion: Optional[int] = None, threads: int = 0, autotune: Optional[bool] = None):
@@ -170,6 +222,9 @@ class Txt2Img:
         self._configured: Dict[int, bool] = {}
         self._dev_ready: Dict[tuple, bool] = {}
         self.last_loop_ms = 0.0
+        self._vae_dir = vae_dir
+        self._dec_ready = None        # decode_device: (key, upscale factor, plans built) of the decoder plan that is resident and captured
+        self.last_decode_ms = 0.0
 
     def close(self):
         self.unet.close()
@@ -437,30 +492,23 @@ class Txt2Img:
         self.last_loop_ms = self.unet.hip_sampler_loop(n["sample"], n["timestep"], n["out"], x, noise, c_in, c_out, ts, s_arr, d_sigma, s_up, guidance)
         return x
 
-    def decode(self, latents: np.ndarray) -> np.ndarray:
-        """decoder_solver: latents * 5.48998 -> VAE decoder -> (y + 1) * 127.5 (src/sd.cpp:1174-1256)."""
-        z = (latents * f32(5.48998)).astype(f32)
+    def decode(self, latents: np.ndarray, factor: float = 5.48998) -> np.ndarray:
+        """decoder_solver: latents * 5.48998 -> VAE decoder -> (y + 1) * 127.5 (src/sd.cpp:1174-1256).  factor: the latent scaling (SDXL: 7.67754,
+        src/sd.cpp:2359-2361).  The untiled case of blend_fold(); decode_device() computes the same bits on the device."""
+        z = (latents * f32(factor)).astype(f32)
         ys = self._run(self.vae, [{self.names["vae_in"]: z[i:i + 1]} for i in range(z.shape[0])], self.names["vae_out"])
         return ((np.concatenate(ys) + f32(1.0)) * f32(127.5)).astype(f32)
 
-    def decode_tiled(self, latents: np.ndarray, tile: int = 32, names=("latent_sample", "out_image")) -> np.ndarray:
+    def decode_tiled(self, latents: np.ndarray, tile: int = 32, names=("latent_sample", "out_image"), factor: float = 5.48998) -> np.ndarray:
         """sd_tiled_decoder (src/sd.cpp:1258-1346): a VAE graph built for `tile` x `tile` latents is run over overlapping tiles
-        (origins 0, 0.75*tile, ... and a last one flush with the border: 0/24/32 for 64-wide latents) and the 8x upscaled tiles are
+        (origins 0, 0.75*tile, ... and a last one flush with the border: 0/24/32 for 64-wide latents, tile_origins()) and the 8x upscaled tiles are
         blended with linear ramps over the first tile/2 * 8... = 64 output pixels of every non-border edge.  self.vae must be the
-        tile-sized decoder.  With the HIP backend all tiles run as ONE batched pass."""
-        z = (latents * f32(5.48998)).astype(f32)
+        tile-sized decoder.  With the HIP backend all tiles run as ONE batched pass.  factor: the latent scaling (SDXL: 7.67754, src/sd.cpp:2359-2361).
+        One image per call.  blend_fold() states the same blend per output pixel; decode_device() computes the same bits on the device."""
+        z = (latents * f32(factor)).astype(f32)
         _, _, H, W = z.shape
-        step, ramp = (tile * 3) // 4, tile * 2           # 24 latent pixels, 64 output pixels for tile = 32
-
-        def origins(n):
-            o, v = [], 0
-            while True:
-                v = min(v, n - tile)
-                o.append(v)
-                if v == n - tile:
-                    return o
-                v += step
-        oy, ox = origins(H), origins(W)
+        ramp = tile * 2                                  # 64 output pixels for tile = 32
+        oy, ox = tile_origins(H, tile), tile_origins(W, tile)
         pushes = [{names[0]: np.ascontiguousarray(z[:, :, y:y + tile, x:x + tile])} for y in oy for x in ox]
         outs = self._run(self.vae, pushes, names[1])
         up = outs[0].shape[-1] // tile                   # 8 for the SD decoders
@@ -482,5 +530,50 @@ class Txt2Img:
                 k += 1
         return ((res + f32(1.0)) * f32(127.5)).astype(f32)
 
+    def _declared_shape(self, name: str) -> List[int]:
+        """the shape the decoder's model.txt declares for activation `name`: the tile size must be known before a plan exists, and the model_* C API has no
+        shape query.  (vae_dir ends with a separator, as everywhere in this class: the constructor reads vae_dir + "model.txt".)"""
+        import re
+        with open(self._vae_dir + "model.txt") as fh:
+            m = re.search(r"[:;]" + re.escape(Model.mangle_name(name)) + r"\(([0-9,]+)\)", fh.read())
+        if not m:
+            raise ValueError(f"decode_device: {name!r} has no declared shape in {self._vae_dir}model.txt")
+        return [int(v) for v in m.group(1).split(",")]
+
+    def decode_device(self, latents: np.ndarray, factor: float = 5.48998, names=None, want: str = "f32", tile: Optional[int] = None):
+        """decode() / decode_tiled() with everything but one 16-64 KB upload per image on the GPU (HIP backend only): osg_decode_gather scales the latents
+        and cuts the tiles straight into the decoder's input staging, the captured pass runs, osg_decode_blend folds the tiles, applies (y + 1) * 127.5
+        and packs the 8-bit pixels; only what `want` names comes back.  latents: [images, 4, H, W]; names: (input, output) of the decoder graph
+        (default: this object's vae_in / vae_out; the tiled decoders are fed as ("latent_sample", "out_image")); the tile size is the graph's own
+        input size (model.txt) unless `tile` gives it -- equal to H and W it is the untiled decoder.  want: "f32" -> the image decode() / decode_tiled()
+        return, bit for bit, [images, 3, u*H, u*W]; "u8" -> to_pixels() of it, [images, u*H, u*W, 3] uint8; "both" -> (image, pixels).
+        The first call per (images, H, W) plans and captures with two ordinary batched runs; later calls are one model_hip_decode each."""
+        if want not in ("f32", "u8", "both"):
+            raise ValueError(f"unknown want {want!r}; valid: f32, u8, both")
+        if not self.batched or self.vae is None:
+            raise RuntimeError("decode_device needs the HIP backend (batched=True) and a VAE decoder")
+        lat = np.ascontiguousarray(latents, f32)
+        P, _, H, W = lat.shape
+        in_name, out_name = names if names else (self.names["vae_in"], self.names["vae_out"])
+        t = int(tile) if tile else self._declared_shape(in_name)[-1]
+        oy, ox = tile_origins(H, t), tile_origins(W, t)
+        key = (in_name, out_name, P, H, W, t)
+        if not self._dec_ready or self._dec_ready[0] != key or self._dec_ready[2] != self.vae.hip_plans_built():
+            z = (lat * f32(factor)).astype(f32)
+            pushes = [{in_name: np.ascontiguousarray(z[p:p + 1, :, y:y + t, x:x + t])} for p in range(P) for y in oy for x in ox]
+            for _ in range(2):          # run() #1 plans and runs eagerly, #2 captures the pass
+                outs = self._run(self.vae, pushes, out_name)
+            self._dec_ready = (key, outs[0].shape[-1] // t, self.vae.hip_plans_built())
+        up = self._dec_ready[1]
+        image = np.empty((P, 3, H * up, W * up), f32) if want != "u8" else None
+        pixels = np.empty((P, H * up, W * up, 3), np.uint8) if want != "f32" else None
+        self.last_decode_ms = self.vae.hip_decode(in_name, out_name, lat, factor, image, pixels)
+        return (image, pixels) if want == "both" else image if want == "f32" else pixels
+
     def txt2img(self, cond: np.ndarray, uncond: np.ndarray, steps: int = 20, seed: int = 42, latent_shape=(1, 4, 64, 64)) -> np.ndarray:
         return self.decode(self.sample(cond, uncond, steps, seed, latent_shape))
+
+    def txt2img_device(self, cond, uncond, steps: int = 20, seed: int = 42, latent_shape=(1, 4, 64, 64), sampler: str = "euler_a",
+                       factor: float = 5.48998, names=None, want: str = "f32", tile: Optional[int] = None):
+        """txt2img() on the device: sample_device() then decode_device() -- two host syncs per image batch"""
+        return self.decode_device(self.sample_device(cond, uncond, steps, seed, latent_shape, sampler=sampler), factor, names, want, tile)
