@@ -222,6 +222,13 @@ int osg_last_route(const osg_ctx* ctx, int out[5]);
  *   InstanceNorm: out[1] threads per block;  out[2] the osg_dtype */
 int osg_last_kernel(const osg_ctx* ctx, int out[8]);
 
+/* The hot kernels take what their first memory requests depend on as leading scalar kernel parameters (preloaded into scalar registers at wave start), some of them
+ * narrower than the host-side fields: a contraction the row pitch of A as 32 bits and the number of k-slices in 16, an attention launch its six key / value strides
+ * as 32 bits and heads / heads per key-value head in 16 each.  These are the checks every such launch runs first, on their own (no launch): 0 = the values fit,
+ * 1 (and osg_last_error) = the launch would be refused. */
+int osg_gemm_kernarg_check(osg_ctx* ctx, long lda, int splits);
+int osg_attention_kernarg_check(osg_ctx* ctx, long kv_stride, int heads, int kv_div);
+
 /* Fused attention == the reference's AttentionFusedOps pseudo-op (onnxstream.cpp:6696-6929):
  * for each of `heads` items: O = softmax(scale * Q K^T) V, with Q:[heads,Tq,D], K given TRANSPOSED as the reference
  * receives it (k_is_dt=1: [heads,D,Tkv], :6792,6814) or natural [heads,Tkv,D] (k_is_dt=0), V:[heads,Tkv,D], O:[heads,Tq,D].

@@ -19,6 +19,12 @@ LIB_GPU = os.path.join(ROOT, "libosgpu.so")
 LIB_HOST = os.environ.get("OSA_LIB_HOST") or os.path.join(ROOT, "libonnxstream_amd.so")   # (OSA_LIB_HOST: A/B runs against another build of the host library, tools/r3_ab_r2.sh)
 ORACLE_REF = os.path.join(REPO, "oracle", "_ref", "libonnxstream_ref.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+# Kernel-argument preload: gfx950 hands a kernel's first 14 argument dwords to every wave in user SGPRs, so the prologue of a launch does not start with a scalar load
+# from the argument segment.  hipcc asks for 16 user SGPRs (2 of them the segment pointer); only leading scalar / pointer parameters are preloaded,
+# which is why the hot kernels take theirs flat.  OSG_NO_KERNARG_PRELOAD=1 builds the control library of the A/B runs (same sources, no preload) beside the real one.
+NO_PRELOAD = os.environ.get("OSG_NO_KERNARG_PRELOAD", "") not in ("", "0")
+PRELOAD_FLAGS = [] if NO_PRELOAD else ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+LIB_GPU_BUILT = os.path.join(ROOT, "libosgpu_nopreload.so") if NO_PRELOAD else LIB_GPU
 
 
 def _newer(target, deps):
@@ -39,14 +45,14 @@ def _run(cmd, **kw):
 def build_gpu(force=False, verbose=False):
     srcs = sorted(glob.glob(os.path.join(CSRC, "osg_*.hip")))
     hdrs = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(INC, "osgpu.h")]
-    objdir = os.path.join(CSRC, "build")
+    objdir = os.path.join(CSRC, "build", "nopreload") if NO_PRELOAD else os.path.join(CSRC, "build")
     os.makedirs(objdir, exist_ok=True)
     objs, procs = [], []
     for s in srcs:
         o = os.path.join(objdir, os.path.basename(s)[:-4] + ".o")
         objs.append(o)
         if force or _newer(o, [s] + hdrs):
-            cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-amdgpu-mfma-vgpr-form", "-I" + INC, "-I" + CSRC, "-c", s, "-o", o]
+            cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-amdgpu-mfma-vgpr-form"] + PRELOAD_FLAGS + ["-I" + INC, "-I" + CSRC, "-c", s, "-o", o]
             procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)))
     for cmd, p in procs:
         out, _ = p.communicate()
@@ -55,9 +61,9 @@ def build_gpu(force=False, verbose=False):
             raise RuntimeError("build failed: " + " ".join(cmd))
         if verbose and out:
             print(out)
-    if force or procs or _newer(LIB_GPU, objs):
-        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_GPU] + objs)
-    return LIB_GPU
+    if force or procs or _newer(LIB_GPU_BUILT, objs):
+        _run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_GPU_BUILT] + objs)
+    return LIB_GPU_BUILT
 
 
 def build_host(force=False):

@@ -316,10 +316,14 @@ __device__ __forceinline__ attn2_hx4 attn2_tr_read(unsigned lds_addr) {
 }
 
 template <int D, int QT, int NST>
-__global__ __launch_bounds__(256) void attn2_kernel(AttnParams pk, int nqb) {
-    const AttnParams p = pk;
-    osg_pin_all(p.q, p.k, p.v, p.o, p.q_tok, p.q_head, p.q_batch, p.k_tok, p.k_head, p.k_batch, p.v_tok, p.v_head, p.v_batch, p.o_tok, p.o_head, p.o_batch, p.heads, p.Tq, p.Tkv,
-                p.scale_log2e, p.mask, p.inv_scale, p.kv_div, nqb, (int)gridDim.x);
+__global__ __launch_bounds__(256) void attn2_kernel(const void* k, const void* v, int k_tok, int k_head, int k_batch, int v_tok, int v_head, int v_batch, int Tkv, int nqb, int grid,
+                                                    unsigned heads_kvdiv, AttnParams pk) {
+    // what the first K / V DMA request depends on arrives in user SGPRs (kernel-argument preload: 14 dwords; attn2_pack checks the 32-bit strides and the two
+    // 16-bit counts on the host); the query side and the output, which the requests do not wait for, in one batch of scalar loads behind them
+    AttnParams p = pk;
+    p.k = (const f16*)k; p.v = (const f16*)v; p.k_tok = k_tok; p.k_head = k_head; p.k_batch = k_batch; p.v_tok = v_tok; p.v_head = v_head; p.v_batch = v_batch; p.Tkv = Tkv;
+    p.heads = (int)(heads_kvdiv & 0xffffu); p.kv_div = (int)(heads_kvdiv >> 16);
+    osg_pin_all(p.q, p.o, p.q_tok, p.q_head, p.q_batch, p.o_tok, p.o_head, p.o_batch, p.Tq, p.scale_log2e, p.mask, p.inv_scale);
     constexpr int DCH = D / 8;                  // 16-byte chunks per K / V row
     constexpr int RSC = DCH + ((6 - DCH % 4) % 4);   // ... of the LDS image: the next count = 2 (mod 4), see the header
     constexpr int ROWB = RSC * 16;              // bytes per row of the LDS image
@@ -346,7 +350,7 @@ __global__ __launch_bounds__(256) void attn2_kernel(AttnParams pk, int nqb) {
     // flat workgroup index -> (image, head, query block): a contiguous run of indices per XCD (workgroup b runs on XCD b % 8)
     int L;
     {
-        const int total = gridDim.x, bid = blockIdx.x, x = bid & 7, i = bid >> 3, q = total >> 3, r = total & 7;
+        const int total = grid, bid = blockIdx.x, x = bid & 7, i = bid >> 3, q = total >> 3, r = total & 7;   // (grid = gridDim.x, without the trip to the hidden arguments)
         L = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + i;
     }
     const int bh = L / nqb, qb = L - bh * nqb;
@@ -602,6 +606,18 @@ __global__ __launch_bounds__(256) void attn2_kernel(AttnParams pk, int nqb) {
     }
 }
 
+// host side of attn2_kernel's leading parameters: 1 (and ctx->err) where a K / V stride does not fit 32 bits or a head count its 16-bit field
+int attn2_pack(osg_ctx* ctx, const AttnParams& p, int (&st)[6], unsigned* heads_kvdiv) {
+    const long s[6] = {p.k_tok, p.k_head, p.k_batch, p.v_tok, p.v_head, p.v_batch};
+    for (int i = 0; i < 6; i++) {
+        if (s[i] < 0 || s[i] > 0x7fffffffL) OSG_FAIL(ctx, "attention launch: a key / value stride does not fit the 32-bit kernel parameter");
+        st[i] = (int)s[i];
+    }
+    if (p.heads < 1 || p.heads > 0xffff || p.kv_div < 1 || p.kv_div > 0xffff) OSG_FAIL(ctx, "attention launch: heads and heads per key / value head must fit their 16-bit kernel parameter fields");
+    *heads_kvdiv = (unsigned)p.heads | ((unsigned)p.kv_div << 16);
+    return 0;
+}
+
 template <int D, int NST>
 int launch_attn2(osg_ctx* ctx, const AttnParams& p, int batch) {
     static const int force_qt = getenv("OSG_ATTN_QT") ? atoi(getenv("OSG_ATTN_QT")) : 0;
@@ -620,8 +636,11 @@ int launch_attn2(osg_ctx* ctx, const AttnParams& p, int batch) {
     const int nqb = qt2 ? (p.Tq + 127) / 128 : (p.Tq + 63) / 64;
     dim3 grid((unsigned)((long)nqb * batch * p.heads));
     osg_set_kernel(ctx, 0, 2, D, NST, qt2 ? 2 : 1, 64, (int)grid.x);
-    if (qt2) hipLaunchKernelGGL(k2, grid, dim3(256), smem, ctx->compute, p, nqb);
-    else hipLaunchKernelGGL(k1, grid, dim3(256), smem, ctx->compute, p, nqb);
+    int st[6];
+    unsigned hk;
+    if (attn2_pack(ctx, p, st, &hk)) return 1;
+    if (qt2) hipLaunchKernelGGL(k2, grid, dim3(256), smem, ctx->compute, (const void*)p.k, (const void*)p.v, st[0], st[1], st[2], st[3], st[4], st[5], p.Tkv, nqb, (int)grid.x, hk, p);
+    else hipLaunchKernelGGL(k1, grid, dim3(256), smem, ctx->compute, (const void*)p.k, (const void*)p.v, st[0], st[1], st[2], st[3], st[4], st[5], p.Tkv, nqb, (int)grid.x, hk, p);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -723,6 +742,15 @@ int osg_attention(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, c
     }
     return osg_attention_strided(ctx, dtype, q, D, (long)Tq * D, 0, kk, D, (long)Tkv * D, 0, v, D, (long)Tkv * D, 0, o, D, (long)Tq * D, 0,
                                  1, heads, Tq, Tkv, D, scale);
+}
+
+int osg_attention_kernarg_check(osg_ctx* ctx, long kv_stride, int heads, int kv_div) {
+    AttnParams p = {};
+    p.k_tok = p.k_head = p.k_batch = p.v_tok = p.v_head = p.v_batch = kv_stride;
+    p.heads = heads; p.kv_div = kv_div;
+    int st[6];
+    unsigned hk;
+    return attn2_pack(ctx, p, st, &hk);
 }
 
 }  // extern "C"

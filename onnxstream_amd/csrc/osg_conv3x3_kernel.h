@@ -180,6 +180,9 @@ __device__ __forceinline__ void conv3x3_body(const GemmParams& p) {
     }
 
     // ============================================== MATH waves ==================================================================
+    // (the loader waves above run on preloaded arguments alone; what the epilogue prefetch reads comes from the struct, in one batch of scalar loads)
+    OSG_PIN(p.bias); OSG_PIN(p.residual); OSG_PIN(p.rowbias); OSG_PIN(p.rb_ld); OSG_PIN(p.rb_rows); OSG_PIN(p.bias_f32); OSG_PIN(p.act); OSG_PIN(p.no_epre);
+    if constexpr (WQ) { OSG_PIN(p.wq_sc); OSG_PIN(p.wq_zp); OSG_PIN(p.w_zp); }
     const int wm0 = (wave / WGN) * WM;
     const int wn0 = (wave % WGN) * WN;
     f32x4 acc[TM][TN];
@@ -375,13 +378,16 @@ __device__ __forceinline__ void conv3x3_body(const GemmParams& p) {
 }
 
 template <int W_, int BN, int WGM, int WGN, int MODE, int NLW, int WQ = 0>
-__global__ __launch_bounds__(256 + 64 * NLW) void conv3x3_kernel(GemmParams pk) {
-    // the fields the first DMA requests / the epilogue prefetch depend on, in ONE batch of scalar loads at entry (GemmParams, round 6)
+__global__ __launch_bounds__(256 + 64 * NLW) void conv3x3_kernel(const void* A, const void* Bt, int M, int N, int K, int k_per_split, unsigned a_bytes, unsigned b_bytes, int grid,
+                                                                 int H, int Cin, unsigned sp_nm, GemmParams pk) {
+    // what the tile walk and the loader waves' first DMA requests depend on arrives in user SGPRs (kernel-argument preload, osg_gemm_common.h kernarg_pack): 14 dwords;
+    // the fields the epilogue prefetch depends on in ONE batch of scalar loads at entry (GemmParams, round 6)
     GemmParams p = pk;
-    OSG_PIN(p.A); OSG_PIN(p.Bt); OSG_PIN(p.kdbg); OSG_PIN(p.M); OSG_PIN(p.N); OSG_PIN(p.K); OSG_PIN(p.splits); OSG_PIN(p.k_per_split); OSG_PIN(p.a_bytes); OSG_PIN(p.b_bytes);
-    OSG_PIN(p.mt); OSG_PIN(p.nt); OSG_PIN(p.n_major); OSG_PIN(p.grid); OSG_PIN(p.H); OSG_PIN(p.Cin);
-    OSG_PIN(p.bias); OSG_PIN(p.residual); OSG_PIN(p.rowbias); OSG_PIN(p.rb_ld); OSG_PIN(p.rb_rows); OSG_PIN(p.bias_f32); OSG_PIN(p.act); OSG_PIN(p.no_epre);
-    if constexpr (WQ) { OSG_PIN(p.wq_sc); OSG_PIN(p.wq_zp); OSG_PIN(p.w_zp); }
+    p.A = (const f16*)A; p.Bt = (const f16*)Bt; p.M = M; p.N = N; p.K = K; p.k_per_split = k_per_split; p.a_bytes = a_bytes; p.b_bytes = b_bytes; p.grid = grid; p.H = H; p.Cin = Cin;
+    p.splits = (int)(sp_nm & ((1u << kPackSplitsBits) - 1)); p.n_major = (sp_nm & kPackNMajor) != 0;
+    p.mt = (M + 127) / 128; p.nt = (N + BN - 1) / BN;
+    p.kdbg = nullptr;
+    if (OSG_UNLIKELY(sp_nm & kPackKdbg)) p.kdbg = kernarg_rare(pk.kdbg);
     conv3x3_body<W_, BN, WGM, WGN, MODE, NLW, WQ>(p);
 }
 
@@ -406,8 +412,12 @@ int launch3(osg_ctx* ctx, GemmParams& p) {
         else p.sink[0].table = p.sink[1].table = nullptr;
     }
     p.grid = p.mt * p.nt * p.splits;
-    hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(256 + 64 * NLW), smem, ctx->compute, p);
+    int lda32;
+    unsigned sp_nm;
+    const int bad = kernarg_pack(ctx, 0, p.splits, p.n_major, p.kdbg != nullptr, false, &lda32, &sp_nm);
+    if (!bad) hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(256 + 64 * NLW), smem, ctx->compute, (const void*)p.A, (const void*)p.Bt, p.M, p.N, p.K, p.k_per_split, p.a_bytes, p.b_bytes, p.grid, p.H, p.Cin, sp_nm, p);
     p.sink[0] = sinks_in[0]; p.sink[1] = sinks_in[1];
+    if (bad) return 1;
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }

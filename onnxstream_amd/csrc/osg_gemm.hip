@@ -895,6 +895,12 @@ int osg_conv2d_nhwc_w8(osg_ctx* ctx, const void* x, const void* wq_ohwi, float w
                                 Cin, Cout, KH, KW, sh, sw, pt, pl, pb, pr, act);
 }
 
+int osg_gemm_kernarg_check(osg_ctx* ctx, long lda, int splits) {
+    int lda32;
+    unsigned sp_nm;
+    return osg_mm::kernarg_pack(ctx, lda, splits, 0, false, false, &lda32, &sp_nm);
+}
+
 }  // extern "C"
 
 static int conv2d_v(osg_ctx* ctx, const W8Quant& q, const void* x, const void* w, const void* bias, osg_dtype bias_dtype,

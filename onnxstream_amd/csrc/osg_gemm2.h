@@ -7,7 +7,7 @@
 #include <type_traits>
 
 #ifndef OSG_GEMM_PIN
-#define OSG_GEMM_PIN 1      // the kernel-argument fields of the prologue pulled in one batch at entry (GemmParams); 0 = as before (A/B)
+#define OSG_GEMM_PIN 1      // the kernel-argument fields of the prologue that do not arrive preloaded pulled in one batch at entry (GemmParams); 0 = where first used (A/B)
 #endif
 
 namespace {
@@ -49,18 +49,25 @@ using namespace osg_mm;
 // operations (osg_gemm_common.h w8_frag); the B stage is half as large, half the DMA requests, half the bytes through the LDS port per k-tile.  The accumulators
 // are scaled once, before any epilogue (w8_scale_acc): split-K slabs, GEGLU, statistics sinks see finished f32 values.  Not with LN (gamma folds into f16 weights).
 template <int BM, int BN, int NST, bool CONV, int MODE = 0, int SPEC = 0, int LN = 0, int NCH = 5, int KS = 1, int WGN = 2, int WQ = 0>
-__global__ __launch_bounds__((SPEC || KS == 2) ? 512 : 256) void gemm2_kernel(GemmParams pk) {
-    // the fields the first DMA request depends on, in ONE batch of scalar loads (GemmParams); everything below reads the register copy
+__global__ __launch_bounds__((SPEC || KS == 2) ? 512 : 256) void gemm2_kernel(const void* A, const void* Bt, int M, int N, int K, int k_per_split, unsigned a_bytes, unsigned b_bytes,
+                                                                              int grid, int lda, unsigned sp_nm, GemmParams pk) {
+    // the tile mapping and the DMA addressing of both operands arrive in user SGPRs (kernel-argument preload, osg_gemm_common.h kernarg_pack): 13 dwords, no scalar
+    // load in front of the first DMA request of an unbatched GEMM; the struct's copies of these fields are never read.  (void pointers: c++filt, which the tools and
+    // the artifact test read kernel names through, does not know the mangling of _Float16)
     GemmParams p = pk;
+    p.A = (const f16*)A; p.Bt = (const f16*)Bt; p.M = M; p.N = N; p.K = K; p.k_per_split = k_per_split; p.a_bytes = a_bytes; p.b_bytes = b_bytes; p.grid = grid; p.lda = lda;
+    p.splits = (int)(sp_nm & ((1u << kPackSplitsBits) - 1)); p.n_major = (sp_nm & kPackNMajor) != 0;
+    p.mt = (M + BM - 1) / BM; p.nt = (N + BN - 1) / BN;
+    p.kdbg = nullptr;
+    if (OSG_UNLIKELY(sp_nm & kPackKdbg)) p.kdbg = kernarg_rare(pk.kdbg);
+    // the convolution geometry (CONV) and the uint8 operands (WQ), which the first requests do depend on, in ONE batch of scalar loads here; the operands of the
+    // epilogue prefetch in a second batch BEHIND the prologue's DMA requests (below): everything reads the register copy
 #if OSG_GEMM_PIN
-    OSG_PIN(p.A); OSG_PIN(p.Bt); OSG_PIN(p.kdbg); OSG_PIN(p.lda); OSG_PIN(p.strideA); OSG_PIN(p.strideB); OSG_PIN(p.M); OSG_PIN(p.N); OSG_PIN(p.K);
-    OSG_PIN(p.splits); OSG_PIN(p.k_per_split); OSG_PIN(p.a_bytes); OSG_PIN(p.b_bytes); OSG_PIN(p.mt); OSG_PIN(p.nt); OSG_PIN(p.n_major); OSG_PIN(p.grid);
     if constexpr (CONV) {
         OSG_PIN(p.H); OSG_PIN(p.W); OSG_PIN(p.Cin); OSG_PIN(p.Ho); OSG_PIN(p.Wo); OSG_PIN(p.KW); OSG_PIN(p.sh); OSG_PIN(p.sw); OSG_PIN(p.pt); OSG_PIN(p.pl);
     }
-    OSG_PIN(p.bias); OSG_PIN(p.residual); OSG_PIN(p.rowbias); OSG_PIN(p.rb_ld); OSG_PIN(p.strideC); OSG_PIN(p.ln_c1); OSG_PIN(p.rs_in); OSG_PIN(p.rb_rows);
-    OSG_PIN(p.bias_f32); OSG_PIN(p.act); OSG_PIN(p.no_epre); OSG_PIN(p.rs_np);
     if constexpr (WQ) { OSG_PIN(p.wq_sc); OSG_PIN(p.wq_zp); OSG_PIN(p.w_zp); }
+    if constexpr (LN == 2) { OSG_PIN(p.rs_in); OSG_PIN(p.rs_np); }
 #endif
     static_assert(KS == 1 || (KS == 2 && !SPEC && MODE == 0 && LN != 1), "KS = 2: plain kernel only (row statistics come from the producer, LN = 2, or not at all)");
     static_assert(WGN == 1 || WGN == 2, "wave grid: 2 x 2 or 4 x 1");
@@ -117,8 +124,14 @@ __global__ __launch_bounds__((SPEC || KS == 2) ? 512 : 256) void gemm2_kernel(Ge
     const int nkt = (kend - kbeg) >> 6;
     const int nsteps = (nkt + KS - 1) / KS;         // (KS = 2: group 1 may run one dummy, zero-filled tile at the end)
 
-    __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A + (long)zb * p.strideA), 0, p.a_bytes, 0x00020000);
-    __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)(p.Bt + (long)zb * p.strideB), 0, p.b_bytes, 0x00020000);
+    const f16* Ab = p.A;
+    const f16* Bb = p.Bt;
+    if (OSG_UNLIKELY(sp_nm & kPackBatch)) {         // (an unbatched launch -- every GEMM of the UNet pass -- does not wait for the strides)
+        Ab += (long)zb * kernarg_rare(pk.strideA);
+        Bb += (long)zb * kernarg_rare(pk.strideB);
+    }
+    __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, 0, p.a_bytes, 0x00020000);
+    __amdgpu_buffer_rsrc_t rsB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, 0, p.b_bytes, 0x00020000);
 
     // ---- per-lane source addressing (constant over the k loop) -------------------------------------------------------------
     const int rsub = lane >> 3;                     // row inside the 8-row group one wave-load covers
@@ -219,18 +232,24 @@ __global__ __launch_bounds__((SPEC || KS == 2) ? 512 : 256) void gemm2_kernel(Ge
         asm volatile("" ::: "memory");
     }
 
-    // epilogue operands of this wave's outputs: requested now, home by the end of the k loop (osg_gemm_common.h epi_prefetch).  They are OLDER than
-    // every tile load in the wave's in-order vector-memory queue, so the counted waits of the loop cover them.
     constexpr bool EPRE = TM * TN <= 8;    // (64x64 / 128x64 / 64x128 tiles; the 128x128 tile keeps its on-demand loads: no registers to spare)
     W8Ops<WQ ? TN : 1, true> w8;
     if constexpr (WQ) { if (math) w8_prefetch<TN, true>(p, w8, n0, wn0, lane); }
-    EpiOps<TM, TN, CONV, EPRE> epre;
-    epre.have = false;
-    if (math && !p.ln_c1 && grp == 0) epi_prefetch<TM, TN, CONV, EPRE>(p, epre, m0, n0, wm0, wn0, lane, zb);
     if (loads) {
 #pragma unroll
         for (int s2 = 0; s2 < NST - 1; s2++) issue_tile(s2);
     }
+    // epilogue operands of this wave's outputs: requested now, home by the end of the k loop (osg_gemm_common.h epi_prefetch).  Behind the prologue's tile requests,
+    // which depend on preloaded arguments only, while these wait for the struct's fields to arrive from the argument segment.  They are YOUNGER than the prologue's
+    // tiles in the wave's in-order vector-memory queue and older than every tile of the loop: the counted waits of the first NST - 1 steps wait for these few
+    // loads too (never for less than their tile), from then on as before.
+#if OSG_GEMM_PIN
+    OSG_PIN(p.bias); OSG_PIN(p.residual); OSG_PIN(p.rowbias); OSG_PIN(p.rb_ld); OSG_PIN(p.strideC); OSG_PIN(p.ln_c1); OSG_PIN(p.rb_rows);
+    OSG_PIN(p.bias_f32); OSG_PIN(p.act); OSG_PIN(p.no_epre);
+#endif
+    EpiOps<TM, TN, CONV, EPRE> epre;
+    epre.have = false;
+    if (math && !p.ln_c1 && grp == 0) epi_prefetch<TM, TN, CONV, EPRE>(p, epre, m0, n0, wm0, wn0, lane, zb);
     kdbg_stamp(p, 1);
     if constexpr (WQ) { if (math) w8_finalize<TN, true>(w8); }
 
@@ -360,8 +379,12 @@ int launch_v2(osg_ctx* ctx, GemmParams& p, int batch) {
         if (ok) { ctx->sink_fused = true; p.sink_imgs = p.M / p.sink_hw; p.sink_per_xcd = ctx->xcd_ids8 ? 1 : 0; }
         else p.sink[0].table = p.sink[1].table = nullptr;
     }
-    hipLaunchKernelGGL(kern, grid, dim3((SPEC || KS == 2) ? 512 : 256), smem, ctx->compute, p);
+    int lda32;
+    unsigned sp_nm;
+    const int bad = kernarg_pack(ctx, p.lda, p.splits, p.n_major, p.kdbg != nullptr, batch > 1, &lda32, &sp_nm);
+    if (!bad) hipLaunchKernelGGL(kern, grid, dim3((SPEC || KS == 2) ? 512 : 256), smem, ctx->compute, (const void*)p.A, (const void*)p.Bt, p.M, p.N, p.K, p.k_per_split, p.a_bytes, p.b_bytes, p.grid, lda32, sp_nm, p);
     p.sink[0] = sinks_in[0]; p.sink[1] = sinks_in[1];
+    if (bad) return 1;
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }

@@ -46,8 +46,9 @@ __host__ __device__ inline float stat_q_scale(long elems) { return (float)(1L <<
 
 struct GemmParams {
     // ---- round 6: field ORDER = the order a workgroup needs them.  A launch of the pass lasts as long as one workgroup, and a workgroup's first DMA request waited for
-    // ~6 dependent round trips of scalar loads from the kernel-argument segment (hipcc loads a field where it is first used); the kernels now pull the first group in
-    // ONE batch at entry (OSG_PIN in gemm2_kernel), the second group (convolution geometry) and the third (operands of the epilogue prefetch) right behind it.
+    // ~6 dependent round trips of scalar loads from the kernel-argument segment (hipcc loads a field where it is first used); the kernels pull what they read in
+    // batches (OSG_PIN in gemm2_kernel).  Most of the first group now reaches the kernels as preloaded leading parameters (kernarg_pack below), the second group
+    // (convolution geometry) is pulled at entry, the third (operands of the epilogue prefetch) behind the prologue's DMA requests.
     // group 1: tile mapping + the DMA addressing of both operands
     const f16* A;
     const f16* Bt;
@@ -100,6 +101,35 @@ struct GemmParams {
     // [tile][slice][TM * TN][256] f32x4 (a lane's accumulator tile = one 16-byte element: 1-KiB bursts per wave-instruction), tickets two words per tile.
     int fold_acc;
 };
+// ---- kernel-argument preload (gfx950 delivers the first 14 dwords of the argument segment in user SGPRs at wave start) ------------------------------------
+// The contraction kernels take what a workgroup's first DMA request depends on as LEADING SCALAR parameters -- A, Bt, M, N, K, k_per_split, a_bytes, b_bytes,
+// grid, then the pitch of A (gemm2_kernel) or H and Cin (conv3x3_kernel), then splits and n_major in one word -- and the whole GemmParams behind them; the kernels
+// overwrite the struct's copies with the register values and derive mt / nt from M / N and the tile's compile-time size, so the tile walk and both buffer
+// descriptors need no scalar load at all.  A by-value struct is never preloaded, hence the flat parameters; the host-side GemmParams is unchanged.
+// Two things of the struct used to sit in front of the first request whatever the launch: the developer probe's buffer (kdbg, tested by the stamp at entry) and the
+// batch strides (added to A and Bt even where the batch index is 0).  The packed word says whether the launch has either (kPackKdbg, kPackBatch); only then does a
+// workgroup read them (kernarg_rare: behind a branch the compiler cannot fold back into a select, which would wait for the load on the common path too).
+// Packed fields: the pitch of A as 32 bits, splits in 16 bits beside the flags.  kernarg_pack: host side, 1 (and ctx->err) where a value does not fit its field.
+constexpr int kPackSplitsBits = 16;
+constexpr unsigned kPackNMajor = 1u << 16, kPackKdbg = 1u << 17, kPackBatch = 1u << 18;
+template <class T>
+__device__ __forceinline__ T kernarg_rare(T v) {
+    asm volatile("" : "+s"(v));
+    return v;
+}
+inline int kernarg_pack(osg_ctx* ctx, long lda, int splits, int n_major, bool kdbg, bool batched, int* lda32, unsigned* sp_nm) {
+    if (lda < 0 || lda > 0x7fffffffL) {
+        ctx->err = "contraction launch: the row pitch of A does not fit the 32-bit kernel parameter";
+        return 1;
+    }
+    if (splits < 1 || splits >= (1 << kPackSplitsBits)) {
+        ctx->err = "contraction launch: the number of k-slices does not fit its 16-bit kernel parameter field";
+        return 1;
+    }
+    *lda32 = (int)lda;
+    *sp_nm = (unsigned)splits | (n_major ? kPackNMajor : 0u) | (kdbg ? kPackKdbg : 0u) | (batched ? kPackBatch : 0u);
+    return 0;
+}
 // a kernel-argument field pulled into a scalar register NOW: see GemmParams.  (An INPUT of an empty asm: an in-out operand would make the value opaque -- pointers lose
 // their address space and every load through them becomes a flat_load, which counts on lgkmcnt AND vmcnt and breaks the counted waits of the k loop.)
 #define OSG_PIN(x) asm volatile("" ::"s"(x))

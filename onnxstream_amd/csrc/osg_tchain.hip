@@ -365,7 +365,11 @@ __device__ __forceinline__ void touch_lines(const void* base, int rows, int row_
 
 // NS = register slots for weight tiles (2: one tile ahead, 3: two tiles ahead)
 template <int RT, int C, int D, int TKT, int NS>
-__global__ __launch_bounds__(256, RT == 2 && NS == 2 ? 2 : 1) void tblock_tail_kernel(TailParams p) {   // (32-row blocks: two workgroups fit a CU -- 72 KB of LDS, <= 256 registers)
+__global__ __launch_bounds__(256, RT == 2 && NS == 2 ? 2 : 1) void tblock_tail_kernel(const void* a1, const void* x0, const void* wo1, const void* bo1, const void* g2, const void* be2, int M, int rows_per_img, TailParams pk) {   // (32-row blocks: two workgroups fit a CU -- 72 KB of LDS, <= 256 registers)
+    // what a row block's first requests depend on -- its A tile and residual rows, to_out1's weight fragments, the first small vectors, the block count -- arrives in
+    // user SGPRs (kernel-argument preload: 14 dwords); the other 24 pointers of the block come from the argument segment behind those requests
+    TailParams p = pk;
+    p.a1 = (const f16*)a1; p.x0 = (const f16*)x0; p.wo1 = (const f16*)wo1; p.bo1 = (const f16*)bo1; p.g2 = (const f16*)g2; p.be2 = (const f16*)be2; p.M = M; p.rows_per_img = rows_per_img;
     constexpr int RB = 16 * RT;                // rows of a row block
     constexpr int TB = kTileBytes<RT>;
     constexpr int KT = C / 64;                 // k-tiles of a C-deep contraction
@@ -777,7 +781,7 @@ int osg_tblock_tail(osg_ctx* ctx, const osg_tblock_tail_args* a) {
         if (osg_first_on_device(attr_mask)) {
             OSG_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
         }
-        hipLaunchKernelGGL(kern, dim3((unsigned)(nblk + npf)), dim3(256), smem, ctx->compute, p);
+        hipLaunchKernelGGL(kern, dim3((unsigned)(nblk + npf)), dim3(256), smem, ctx->compute, (const void*)p.a1, (const void*)p.x0, (const void*)p.wo1, (const void*)p.bo1, (const void*)p.g2, (const void*)p.be2, p.M, p.rows_per_img, p);
         return 0;
     };
     constexpr int vec_bytes = (9 * 320 + 8 * 320) * 2;     // the small operands behind the three row-block images

@@ -58,8 +58,48 @@ def kernels_of(obj: bytes):
         blk = ".agpr_count:" + blk
         g = lambda k, d=0: (re.search(r"\.%s:\s*(\S+)" % k, blk) or [None, d])[1]
         name = g("name", "?")
-        yield dict(name=name, vgpr=int(g("vgpr_count")), agpr=int(g("agpr_count")), sgpr=int(g("sgpr_count")), lds=int(g("group_segment_fixed_size")),
+        yield dict(name=name, lead=leading_scalar_dwords(blk), vgpr=int(g("vgpr_count")), agpr=int(g("agpr_count")), sgpr=int(g("sgpr_count")), lds=int(g("group_segment_fixed_size")),
                    scratch=int(g("private_segment_fixed_size")), wg=int(g("max_flat_workgroup_size")), vspill=int(g("vgpr_spill_count")), sspill=int(g("sgpr_spill_count")))
+
+
+def preload_lengths(obj: bytes):
+    """{kernel symbol: dwords of kernel arguments the kernel asks to be preloaded into user SGPRs}, read from the kernel descriptors of one code object.
+
+    A kernel NAME has a 64-byte descriptor NAME.kd in .rodata; its bytes 58..59 are KERNARG_PRELOAD (bits 6:0 = length in dwords, bits 15:7 = offset)."""
+    assert obj[:6] == b"\x7fELF\x02\x01", "ELF64 little-endian"
+    shoff, = struct.unpack_from("<Q", obj, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", obj, 0x3A)
+    secs = [struct.unpack_from("<IIQQQQIIQQ", obj, shoff + i * shentsize) for i in range(shnum)]     # name, type, flags, addr, offset, size, link, info, align, entsize
+    out = {}
+    for sec in secs:
+        if sec[1] != 2:             # SHT_SYMTAB
+            continue
+        stroff = secs[sec[6]][4]
+        for at in range(sec[4], sec[4] + sec[5], 24):
+            st_name, _, _, st_shndx, st_value, st_size = struct.unpack_from("<IBBHQQ", obj, at)
+            name = obj[stroff + st_name: obj.index(b"\0", stroff + st_name)].decode()
+            if not name.endswith(".kd") or st_size != 64 or not 0 < st_shndx < shnum:
+                continue
+            home = secs[st_shndx]
+            kd = home[4] + (st_value - home[3])
+            out[name[:-3]] = struct.unpack_from("<H", obj, kd + 58)[0] & 0x7F
+    return out
+
+
+def leading_scalar_dwords(blk: str, budget: int = 14) -> int:
+    """Dwords of the leading explicit scalar / pointer arguments of one kernel's metadata block that fit the preload budget: what the compiler can preload.
+
+    Arguments are walked in order; a by-value argument larger than 8 bytes (a struct) or a hidden argument ends the run, and so does the first that would pass the budget."""
+    n = 0
+    for m in re.finditer(r"- (?:\.\w+:\s*\S+\s*)*?\.offset:\s*(\d+)\s*(?:\.\w+:\s*\S+\s*)*?\.size:\s*(\d+)\s*(?:\.\w+:\s*\S+\s*)*?\.value_kind:\s*(\S+)", blk):
+        off, size, kind = int(m.group(1)), int(m.group(2)), m.group(3)
+        if kind not in ("by_value", "global_buffer") or size > 8:
+            break
+        end = (off + size + 3) // 4
+        if end > budget:
+            break
+        n = end
+    return n
 
 
 def demangle(names):
