@@ -380,6 +380,18 @@ int osg_sampler_cfg_multistep(osg_ctx* ctx, int form, float* x, const float* eps
  * and timestep[0 .. 2*prompts*t_per_sample) = t -- one launch. */
 int osg_sampler_prepare_rescale(osg_ctx* ctx, float* x, float* sample, float* timestep, int prompts, long L, float x_scale, float c_in, float t,
                                 long t_per_sample);
+/* The same three steps WITHOUT the guidance pair, for a pass that holds one sample per prompt: CFGDenoiser_CompVisDenoiser returns the cond
+ * branch alone in Turbo mode (src/sd.cpp:1537-1541), so den = eps[p]*c_out + x and eps, sample are [prompts, L].  Everything after den is the
+ * arithmetic of the entry points above (one kernel body per form, instantiated for both), with the same rounding rules and argument checks.
+ * osg_sampler_prepare_single: x_scale != 1: x[p] = x[p] * x_scale IN PLACE first (DDIM's prescale); then sample[p] = x[p] * c_in and
+ * timestep[0 .. prompts*t_per_sample) = t -- one launch. */
+int osg_sampler_prepare_single(osg_ctx* ctx, float* x, float* sample, float* timestep, int prompts, long L, float x_scale, float c_in, float t,
+                               long t_per_sample);
+int osg_sampler_euler_a_single(osg_ctx* ctx, float* x, const float* eps, const float* noise, int prompts, long L, float c_out, float sigma,
+                               float d_sigma, float sigma_up, float clip);
+int osg_sampler_multistep_single(osg_ctx* ctx, int form, float* x, const float* eps, float* h0, const float* h1, const float* h2, const float* h3,
+                                 int prompts, long L, float c_out, float sigma, float k0, float k1, float k2, float k3, float k4, double da,
+                                 double db);
 
 /* ---- latents -> image on the device: what surrounds the VAE decoder pass ------------------------------------------ */
 /* The tile grid both entry points share (Txt2Img.decode_tiled, after sd_tiled_decoder src/sd.cpp:1258-1346): along an axis of n latent pixels the

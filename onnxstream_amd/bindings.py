@@ -228,6 +228,52 @@ class Model:
                     dcoef.size, guidance, ctypes.byref(ms)))
         return ms.value
 
+    def hip_sampler_loop_single(self, sample: str, timestep: str, out: str, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, clip=None) -> float:
+        """hip_sampler_loop for a plan built by a run() with `prompts` pushes, ONE UNet sample per prompt (SDXL Turbo, src/sd.cpp:1537-1541):
+        den = eps*c_out + x, no guidance pair.  The arguments of hip_sampler_loop without `guidance`."""
+        import numpy as np
+        f = self._lib.model_hip_sampler_loop_single
+        fp = ctypes.POINTER(ctypes.c_float)
+        f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, fp, fp, fp, fp,
+                      ctypes.POINTER(ctypes.c_double)]
+        f.restype = ctypes.c_void_p
+        assert x.dtype == np.float32 and x.flags.c_contiguous
+        arrs = [np.ascontiguousarray(a, np.float32) for a in (c_in, c_out, t, sigma, d_sigma, sigma_up)]
+        steps = len(arrs[0])
+        if noise is not None:
+            noise = np.ascontiguousarray(noise, np.float32)
+            assert noise.size == steps * x.size
+        if clip is not None:
+            clip = np.ascontiguousarray(clip, np.float32)
+            assert clip.size == steps
+        ms = ctypes.c_double(0)
+        self._err(f(self._h, self._name(sample), self._name(timestep), self._name(out), steps, x.shape[0], x.ctypes.data_as(fp),
+                    noise.ctypes.data_as(fp) if noise is not None else None, *[a.ctypes.data_as(fp) for a in arrs],
+                    clip.ctypes.data_as(fp) if clip is not None else None, ctypes.byref(ms)))
+        return ms.value
+
+    def hip_sampler_loop_multistep_single(self, sample: str, timestep: str, out: str, x, sampler: int, c_in, c_out, t, sigma, order, coef, dcoef) -> float:
+        """hip_sampler_loop_multistep for a plan with ONE UNet sample per prompt (see hip_sampler_loop_single): the same arguments without `guidance`."""
+        import numpy as np
+        f = self._lib.model_hip_sampler_loop_multistep_single
+        fp, dp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+        f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, ip,
+                      fp, ctypes.c_ulonglong, dp, ctypes.c_ulonglong, ctypes.POINTER(ctypes.c_double)]
+        f.restype = ctypes.c_void_p
+        assert x.dtype == np.float32 and x.flags.c_contiguous
+        arrs = [np.ascontiguousarray(a, np.float32) for a in (c_in, c_out, t, sigma)]
+        steps = len(arrs[0])
+        if any(len(a) != steps for a in arrs) or len(order) != steps:
+            raise OnnxStreamError("hip_sampler_loop_multistep_single: c_in, c_out, t, sigma and order need one entry per step")
+        order = np.ascontiguousarray(order, np.int32)
+        coef = np.ascontiguousarray(coef, np.float32)
+        dcoef = np.ascontiguousarray(dcoef, np.float64)
+        ms = ctypes.c_double(0)
+        self._err(f(self._h, self._name(sample), self._name(timestep), self._name(out), steps, x.shape[0], int(sampler), x.ctypes.data_as(fp),
+                    *[a.ctypes.data_as(fp) for a in arrs], order.ctypes.data_as(ip), coef.ctypes.data_as(fp), coef.size, dcoef.ctypes.data_as(dp),
+                    dcoef.size, ctypes.byref(ms)))
+        return ms.value
+
     def hip_decode(self, in_name: str, out_name: str, latents, factor: float, image=None, pixels=None) -> float:
         """Latents -> image on the device (model_hip_decode): the latents are uploaded, scaled by `factor` and cut into the decoder's tiles, the
         resident pass runs, the tiles are blended and (y + 1) * 127.5 applied -- one call, one host sync.  latents: float32 [images, 4, h, w].

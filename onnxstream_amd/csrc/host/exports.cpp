@@ -339,7 +339,8 @@ char* model_hip_sampler_loop(Handle* h, char* sample_name, char* timestep_name, 
     }
 }
 // the same loop with a one-evaluation multistep sampler of src/samplers.h.  sampler: 0 = dpm++2m / dpm++2mv2, 1 = ipndm, 2 = ipndm_v, 3 = ipndm_vo,
-// 4 = taylor3, 5 = ddim; order: [steps] int (0 = the sampler's first-step form; <= step index); coef: [steps, 6] float = k0..k4 of the step's
+// 4 = taylor3, 5 = ddim; order: [steps] int (0 = the sampler's first-step form; <= step index; sampler 0 also takes 2 = the plain Euler step of the
+// reference's SDXL last-step rule, src/sd.cpp:1705-1719, at any step); coef: [steps, 6] float = k0..k4 of the step's
 // osg_multistep_form (include/osgpu.h) and DDIM's prescale factor of x; dcoef: [steps, 2] double = DDIM's (da, db); n_coef / n_dcoef: their lengths.
 char* model_hip_sampler_loop_multistep(Handle* h, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, int sampler, float* x,
                                        const float* c_in, const float* c_out, const float* t, const float* sigma, const int* order, const float* coef,
@@ -347,6 +348,32 @@ char* model_hip_sampler_loop_multistep(Handle* h, char* sample_name, char* times
     try {
         const double v = Plan::run_sampler_loop_multistep(h->model, sample_name, timestep_name, out_name, steps, prompts, sampler, x, c_in, c_out, t,
                                                            sigma, order, coef, (size_t)n_coef, dcoef, (size_t)n_dcoef, guidance);
+        if (ms) *ms = v;
+        return nullptr;
+    } catch (const std::exception& e) {
+        return dup_cstr(e.what());
+    }
+}
+// the two loops above for a plan that holds ONE sample per prompt (SDXL Turbo: CFGDenoiser_CompVisDenoiser returns the cond branch alone, src/sd.cpp:1537-1541):
+// den = eps*c_out + x, no guidance.  The arguments of their siblings without `guidance`; the plan's batch must be `prompts`.
+char* model_hip_sampler_loop_single(Handle* h, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, float* x, const float* noise,
+                                    const float* c_in, const float* c_out, const float* t, const float* sigma, const float* d_sigma, const float* sigma_up,
+                                    const float* clip, double* ms) {
+    try {
+        const double v = Plan::run_sampler_loop(h->model, sample_name, timestep_name, out_name, steps, prompts, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up,
+                                                clip, 1);
+        if (ms) *ms = v;
+        return nullptr;
+    } catch (const std::exception& e) {
+        return dup_cstr(e.what());
+    }
+}
+char* model_hip_sampler_loop_multistep_single(Handle* h, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, int sampler, float* x,
+                                              const float* c_in, const float* c_out, const float* t, const float* sigma, const int* order, const float* coef,
+                                              unsigned long long n_coef, const double* dcoef, unsigned long long n_dcoef, double* ms) {
+    try {
+        const double v = Plan::run_sampler_loop_multistep(h->model, sample_name, timestep_name, out_name, steps, prompts, sampler, x, c_in, c_out, t, sigma,
+                                                           order, coef, (size_t)n_coef, dcoef, (size_t)n_dcoef, 0.f, 1);
         if (ms) *ms = v;
         return nullptr;
     } catch (const std::exception& e) {

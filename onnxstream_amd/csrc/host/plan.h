@@ -183,7 +183,7 @@ struct Plan {
     void set_input(const std::string& name, long index, const float* data, size_t count);
     double sampler_loop(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps, int prompts,
                         float* x, const float* noise, const float* c_in, const float* c_out, const float* t, const float* sigma, const float* d_sigma,
-                        const float* sigma_up, float guidance, const float* clip);
+                        const float* sigma_up, float guidance, const float* clip, int branches = 2);
     // the same loop with one of the one-evaluation multistep samplers of src/samplers.h (DPM++ 2M / 2M v2, iPNDM, iPNDM_v, iPNDM_vo, Taylor3, DDIM):
     // per step a prepare launch (DDIM: with its in-place prescale of x), the pass, and one osg_sampler_cfg_multistep launch whose form follows
     // from `sampler` (OSG_LOOP_* of exports.cpp) and order[i].  coef: [steps, 6] float (k0..k4 of the form, then DDIM's prescale factor),
@@ -191,13 +191,20 @@ struct Plan {
     // reused; order[i] <= i is required, so a call never reads an entry an earlier image left behind.
     double sampler_loop_multistep(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps, int prompts,
                                   int sampler, float* x, const float* c_in, const float* c_out, const float* t, const float* sigma, const int* order,
-                                  const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef, float guidance);
+                                  const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef, float guidance, int branches = 2);
+    // branches (both loops): UNet samples per prompt in the plan's batch.  2 = the cond / uncond pair with the CFG combine; 1 = one sample per prompt and
+    // den = eps*c_out + x, what CFGDenoiser_CompVisDenoiser returns in Turbo mode (src/sd.cpp:1537-1541): the plan's batch must be `prompts`, guidance is
+    // unused and the osg_sampler_*_single kernels run (model_hip_sampler_loop_single / model_hip_sampler_loop_multistep_single).  Order 2 of sampler 0 is
+    // the Euler step of the reference's SDXL last-step rule (src/sd.cpp:1705-1719); it reads no history and is legal at any step.
     // the same on Model m's plan, recording its last-pass time (model_hip_sampler_loop_multistep).  A static member of Plan, Model's friend, so that
     // onnxstream.h -- the header the reference application is compiled against for the drop-in link (oracle/Makefile) -- stays as it is.
     static double run_sampler_loop_multistep(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name,
                                              int n_steps, int prompts, int sampler, float* x, const float* c_in, const float* c_out, const float* t,
                                              const float* sigma, const int* order, const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef,
-                                             float guidance);
+                                             float guidance, int branches = 2);
+    static double run_sampler_loop(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
+                                   int prompts, float* x, const float* noise, const float* c_in, const float* c_out, const float* t, const float* sigma,
+                                   const float* d_sigma, const float* sigma_up, const float* clip, int branches);
     // latents -> image without leaving the device (the VAE decoder plan): upload the latents [images, 4, H, W], osg_decode_gather cuts and scales the
     // tiles into the input staging, the pass (captured, or eager while no graph exists), osg_decode_blend folds the tiles and makes the fp32 image
     // [images, 3, u*H, u*W] and / or the packed uint8 image [images, u*H, u*W, 3]; only the one(s) asked for (non-NULL) come back.  Tile size t and
@@ -291,6 +298,11 @@ struct Plan {
     void* samp_noise = nullptr;
     void* samp_hist = nullptr;    // sampler_loop_multistep: history ring [H, prompts, L], device fp32
     size_t samp_x_bytes = 0, samp_noise_bytes = 0, samp_hist_bytes = 0;
+    // the prologue the two sampler loops share (plan_run.cpp): state and batch checks, the tensors a loop reads and writes, growing a state buffer
+    struct SamplerIO { const In* in_s = nullptr; const In* in_t = nullptr; const Out* out = nullptr; long L = 0, TL = 0; };
+    void sampler_check_state(const std::string& fn, int prompts, int branches) const;
+    SamplerIO sampler_io(const std::string& fn, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name) const;
+    void sampler_grow(void*& p, size_t& have, size_t need);
     void* dec_lat = nullptr;      // decode_tiles state: latents [images, 4, H, W] fp32, image [images, 3, uH, uW] fp32, pixels [images, uH, uW, 3] uint8
     void* dec_img = nullptr;
     void* dec_pix = nullptr;

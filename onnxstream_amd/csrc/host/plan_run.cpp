@@ -473,51 +473,75 @@ void Plan::set_input(const std::string& name, long index, const float* data, siz
     throw std::invalid_argument("Model::get_tensor_data: input tensor not found: " + name);
 }
 
+// what both sampler loops check (sampler_check_state) and look up (sampler_io) before they enqueue anything; `fn` is the "Model::hip_sampler_loop...: " prefix of the caller's error texts.
+// branches: UNet samples per prompt in the plan's batch, 2 = the cond / uncond pair, 1 = Turbo's single sample (the *_single entry points).
+void Plan::sampler_check_state(const std::string& fn, int prompts, int branches) const {
+    if (runs < 1) throw std::runtime_error(fn + "run() once first (the context inputs must be resident).");
+    if (stream_weights) throw std::runtime_error(fn + "not available in streamed-weights mode.");
+    if (u8) throw std::runtime_error(fn + "not available with uint8 arithmetic.");
+    if (branches == 2 && (prompts <= 0 || 2L * prompts != N))
+        throw std::invalid_argument(fn + "the plan's batch must be 2 * prompts (cond, uncond per prompt).");
+    if (branches != 2 && (prompts <= 0 || (long)prompts != N))
+        throw std::invalid_argument(fn + "the plan's batch must be prompts (one sample per prompt: this loop runs no guidance pair).");
+}
+
+Plan::SamplerIO Plan::sampler_io(const std::string& fn, const std::string& sample_name, const std::string& timestep_name,
+                                 const std::string& out_name) const {
+    SamplerIO io;
+    for (auto& in : inputs) {
+        if (in.name == sample_name) io.in_s = &in;
+        if (in.name == timestep_name) io.in_t = &in;
+    }
+    for (auto& o : outputs)
+        if (o.name == out_name) io.out = &o;
+    if (!io.in_s || !io.in_t || !io.out) throw std::invalid_argument(fn + "input/output tensor not found.");
+    if (io.out->raw16) throw std::invalid_argument(fn + "the output is excluded from the fp32 conversion (m_outputs_convert_set).");
+    io.L = vals[io.in_s->staging].numel();
+    io.TL = vals[io.in_t->staging].numel();
+    if (vals[io.out->f32val].numel() != io.L || !vals[io.out->f32val].batched)
+        throw std::invalid_argument(fn + "the output must have the shape of the sample input.");
+    return io;
+}
+
+void Plan::sampler_grow(void*& p, size_t& have, size_t need) {
+    if (have >= need) return;
+    if (p) be.check(be.api.osg_free(be.ctx, p), "osg_free");
+    p = nullptr;
+    have = 0;
+    be.check(be.api.osg_malloc(be.ctx, need, &p), "osg_malloc");
+    have = need;
+}
+
 double Plan::sampler_loop(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps, int prompts,
                           float* x, const float* noise, const float* c_in, const float* c_out, const float* t, const float* sigma, const float* d_sigma,
-                          const float* sigma_up, float guidance, const float* clip) {
-    if (runs < 1) throw std::runtime_error("Model::hip_sampler_loop: run() once first (the context inputs must be resident).");
-    if (stream_weights) throw std::runtime_error("Model::hip_sampler_loop: not available in streamed-weights mode.");
-    if (u8) throw std::runtime_error("Model::hip_sampler_loop: not available with uint8 arithmetic.");
-    if (prompts <= 0 || 2L * prompts != N) throw std::invalid_argument("Model::hip_sampler_loop: the plan's batch must be 2 * prompts (cond, uncond per prompt).");
+                          const float* sigma_up, float guidance, const float* clip, int branches) {
+    const bool pair = branches == 2;
+    const std::string fn = pair ? "Model::hip_sampler_loop: " : "Model::hip_sampler_loop_single: ";
+    sampler_check_state(fn, prompts, branches);
     FlightGuard flight(in_flight);
-    const In *in_s = nullptr, *in_t = nullptr;
-    for (auto& in : inputs) {
-        if (in.name == sample_name) in_s = &in;
-        if (in.name == timestep_name) in_t = &in;
-    }
-    const Out* out = nullptr;
-    for (auto& o : outputs)
-        if (o.name == out_name) out = &o;
-    if (!in_s || !in_t || !out) throw std::invalid_argument("Model::hip_sampler_loop: input/output tensor not found.");
-    if (out->raw16) throw std::invalid_argument("Model::hip_sampler_loop: the output is excluded from the fp32 conversion (m_outputs_convert_set).");
-    const long L = vals[in_s->staging].numel(), TL = vals[in_t->staging].numel();
-    if (vals[out->f32val].numel() != L || !vals[out->f32val].batched)
-        throw std::invalid_argument("Model::hip_sampler_loop: the output must have the shape of the sample input.");
+    const SamplerIO io = sampler_io(fn, sample_name, timestep_name, out_name);
+    const long L = io.L;
+    float *sample = (float*)ptr(io.in_s->staging), *tstep = (float*)ptr(io.in_t->staging);
+    const float* eps = (const float*)ptr(io.out->f32val);
     const size_t xb = (size_t)prompts * L * sizeof(float), nb = (size_t)n_steps * xb;
-    auto grow = [&](void*& p, size_t& have, size_t need) {
-        if (have >= need) return;
-        if (p) be.check(be.api.osg_free(be.ctx, p), "osg_free");
-        p = nullptr;
-        have = 0;
-        be.check(be.api.osg_malloc(be.ctx, need, &p), "osg_malloc");
-        have = need;
-    };
-    grow(samp_x, samp_x_bytes, xb);
-    if (noise) grow(samp_noise, samp_noise_bytes, nb);
+    sampler_grow(samp_x, samp_x_bytes, xb);
+    if (noise) sampler_grow(samp_noise, samp_noise_bytes, nb);
     be.check(be.api.osg_upload(be.ctx, samp_x, x, xb), "osg_upload");
     if (noise) be.check(be.api.osg_upload(be.ctx, samp_noise, noise, nb), "osg_upload");
     be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");
     for (int i = 0; i < n_steps; i++) {
-        be.check(be.api.osg_sampler_prepare(be.ctx, (const float*)samp_x, (float*)ptr(in_s->staging), (float*)ptr(in_t->staging), prompts, L, c_in[i], t[i], TL),
-                 "osg_sampler_prepare");
+        if (pair) be.check(be.api.osg_sampler_prepare(be.ctx, (const float*)samp_x, sample, tstep, prompts, L, c_in[i], t[i], io.TL), "osg_sampler_prepare");
+        else be.check(be.api.osg_sampler_prepare_single(be.ctx, (float*)samp_x, sample, tstep, prompts, L, 1.f, c_in[i], t[i], io.TL), "osg_sampler_prepare_single");
         if (graph) be.check(be.api.osg_graph_launch(be.ctx, graph), "osg_graph_launch");
         else run_steps();
-        const bool with_noise = noise != nullptr;
-        be.check(be.api.osg_sampler_cfg_euler_a(be.ctx, (float*)samp_x, (const float*)ptr(out->f32val),
-                                               with_noise ? (const float*)samp_noise + (size_t)i * prompts * L : nullptr, prompts, L, c_out[i], guidance,
-                                               sigma[i], d_sigma[i], sigma_up[i], clip ? clip[i] : 0.f),
-                 "osg_sampler_cfg_euler_a");
+        const float* nz = noise ? (const float*)samp_noise + (size_t)i * prompts * L : nullptr;
+        const float cl = clip ? clip[i] : 0.f;
+        if (pair)
+            be.check(be.api.osg_sampler_cfg_euler_a(be.ctx, (float*)samp_x, eps, nz, prompts, L, c_out[i], guidance, sigma[i], d_sigma[i], sigma_up[i], cl),
+                     "osg_sampler_cfg_euler_a");
+        else
+            be.check(be.api.osg_sampler_euler_a_single(be.ctx, (float*)samp_x, eps, nz, prompts, L, c_out[i], sigma[i], d_sigma[i], sigma_up[i], cl),
+                     "osg_sampler_euler_a_single");
     }
     float ms = 0;
     be.check(be.api.osg_timer_stop(be.ctx, &ms), "osg_timer_stop");
@@ -529,15 +553,15 @@ double Plan::sampler_loop(const std::string& sample_name, const std::string& tim
 
 double Plan::sampler_loop_multistep(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
                                    int prompts, int sampler, float* x, const float* c_in, const float* c_out, const float* t, const float* sigma,
-                                   const int* order, const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef, float guidance) {
-    static const char* fn = "Model::hip_sampler_loop_multistep: ";
-    if (runs < 1) throw std::runtime_error(std::string(fn) + "run() once first (the context inputs must be resident).");
-    if (stream_weights) throw std::runtime_error(std::string(fn) + "not available in streamed-weights mode.");
-    if (u8) throw std::runtime_error(std::string(fn) + "not available with uint8 arithmetic.");
-    if (prompts <= 0 || 2L * prompts != N) throw std::invalid_argument(std::string(fn) + "the plan's batch must be 2 * prompts (cond, uncond per prompt).");
-    // per sampler: history depth (create_buffers, src/samplers.h:5-24), highest order, and the kernel form of each order
+                                   const int* order, const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef, float guidance,
+                                   int branches) {
+    const bool pair = branches == 2;
+    const std::string fn = pair ? "Model::hip_sampler_loop_multistep: " : "Model::hip_sampler_loop_multistep_single: ";
+    sampler_check_state(fn, prompts, branches);
+    // per sampler: history depth (create_buffers, src/samplers.h:5-24), and the kernel form of each order.  Order 2 of the DPM++ pair is the plain
+    // Euler step the reference substitutes on the last step of an SDXL image (src/sd.cpp:1705-1719)
     static const int forms[6][4] = {
-        {OSG_MS_DPMPP_FIRST, OSG_MS_DPMPP_2M, -1, -1},                    // 0: DPM++ 2M and 2M v2 (they differ in the host coefficients only)
+        {OSG_MS_DPMPP_FIRST, OSG_MS_DPMPP_2M, OSG_MS_EULER_D, -1},        // 0: DPM++ 2M and 2M v2 (they differ in the host coefficients only)
         {OSG_MS_EULER_D, OSG_MS_IPNDM1, OSG_MS_IPNDM2, OSG_MS_IPNDM3},    // 1: iPNDM
         {OSG_MS_EULER_D, OSG_MS_IPNDM_V1, OSG_MS_IPNDM2, OSG_MS_IPNDM3},  // 2: iPNDM_v
         {OSG_MS_EULER_D, OSG_MS_IPNDM_VO1, OSG_MS_IPNDM_VO2, OSG_MS_IPNDM_VO3},  // 3: iPNDM_vo
@@ -545,38 +569,24 @@ double Plan::sampler_loop_multistep(const std::string& sample_name, const std::s
         {OSG_MS_DDIM, -1, -1, -1},                                        // 5: DDIM
     };
     static const int depth[6] = {1, 4, 4, 4, 3, 0};
-    if (sampler < 0 || sampler >= 6) throw std::invalid_argument(std::string(fn) + "unknown sampler form " + std::to_string(sampler) + ".");
+    // entries of earlier steps (h1..) that order o reads: o itself, except for that Euler step, which reads none and so is legal at step 0 too -- a
+    // one-step image is first and last step at once
+    auto reads = [&](int o) { return sampler == 0 && o == 2 ? 0 : o; };
+    if (sampler < 0 || sampler >= 6) throw std::invalid_argument(fn + "unknown sampler form " + std::to_string(sampler) + ".");
     if (n_steps < 0 || n_coef != (size_t)n_steps * 6 || n_dcoef != (size_t)n_steps * 2)
-        throw std::invalid_argument(std::string(fn) + "the coefficient tables must hold steps * 6 floats and steps * 2 doubles.");
+        throw std::invalid_argument(fn + "the coefficient tables must hold steps * 6 floats and steps * 2 doubles.");
     for (int i = 0; i < n_steps; i++)
-        if (order[i] < 0 || order[i] > 3 || order[i] > i || forms[sampler][order[i]] < 0)
-            throw std::invalid_argument(std::string(fn) + "order " + std::to_string(order[i]) + " at step " + std::to_string(i) + " is not available.");
+        if (order[i] < 0 || order[i] > 3 || forms[sampler][order[i]] < 0 || reads(order[i]) > i)
+            throw std::invalid_argument(fn + "order " + std::to_string(order[i]) + " at step " + std::to_string(i) + " is not available.");
     FlightGuard flight(in_flight);
-    const In *in_s = nullptr, *in_t = nullptr;
-    for (auto& in : inputs) {
-        if (in.name == sample_name) in_s = &in;
-        if (in.name == timestep_name) in_t = &in;
-    }
-    const Out* out = nullptr;
-    for (auto& o : outputs)
-        if (o.name == out_name) out = &o;
-    if (!in_s || !in_t || !out) throw std::invalid_argument(std::string(fn) + "input/output tensor not found.");
-    if (out->raw16) throw std::invalid_argument(std::string(fn) + "the output is excluded from the fp32 conversion (m_outputs_convert_set).");
-    const long L = vals[in_s->staging].numel(), TL = vals[in_t->staging].numel();
-    if (vals[out->f32val].numel() != L || !vals[out->f32val].batched)
-        throw std::invalid_argument(std::string(fn) + "the output must have the shape of the sample input.");
+    const SamplerIO io = sampler_io(fn, sample_name, timestep_name, out_name);
+    const long L = io.L;
+    float *sample = (float*)ptr(io.in_s->staging), *tstep = (float*)ptr(io.in_t->staging);
+    const float* eps = (const float*)ptr(io.out->f32val);
     const int H = depth[sampler];
     const size_t xb = (size_t)prompts * L * sizeof(float), hb = (size_t)H * xb;
-    auto grow = [&](void*& p, size_t& have, size_t need) {
-        if (have >= need) return;
-        if (p) be.check(be.api.osg_free(be.ctx, p), "osg_free");
-        p = nullptr;
-        have = 0;
-        be.check(be.api.osg_malloc(be.ctx, need, &p), "osg_malloc");
-        have = need;
-    };
-    grow(samp_x, samp_x_bytes, xb);
-    if (H) grow(samp_hist, samp_hist_bytes, hb);
+    sampler_grow(samp_x, samp_x_bytes, xb);
+    if (H) sampler_grow(samp_hist, samp_hist_bytes, hb);
     be.check(be.api.osg_upload(be.ctx, samp_x, x, xb), "osg_upload");
     // history entry k of step i (k = 0: written now, k >= 1: written k steps ago) lives in ring slot (i - k) mod H: the reference's shift of
     // sampler_history_buffer (src/samplers.h:695 and alike) becomes a rotation of the pointers
@@ -584,21 +594,27 @@ double Plan::sampler_loop_multistep(const std::string& sample_name, const std::s
     be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");
     for (int i = 0; i < n_steps; i++) {
         const float* k = coef + (size_t)i * 6;
-        if (sampler == 5)
-            be.check(be.api.osg_sampler_prepare_rescale(be.ctx, (float*)samp_x, (float*)ptr(in_s->staging), (float*)ptr(in_t->staging), prompts, L, k[5],
-                                                        c_in[i], t[i], TL),
+        if (!pair)
+            be.check(be.api.osg_sampler_prepare_single(be.ctx, (float*)samp_x, sample, tstep, prompts, L, sampler == 5 ? k[5] : 1.f, c_in[i], t[i], io.TL),
+                     "osg_sampler_prepare_single");
+        else if (sampler == 5)
+            be.check(be.api.osg_sampler_prepare_rescale(be.ctx, (float*)samp_x, sample, tstep, prompts, L, k[5], c_in[i], t[i], io.TL),
                      "osg_sampler_prepare_rescale");
         else
-            be.check(be.api.osg_sampler_prepare(be.ctx, (const float*)samp_x, (float*)ptr(in_s->staging), (float*)ptr(in_t->staging), prompts, L, c_in[i],
-                                                t[i], TL),
-                     "osg_sampler_prepare");
+            be.check(be.api.osg_sampler_prepare(be.ctx, (const float*)samp_x, sample, tstep, prompts, L, c_in[i], t[i], io.TL), "osg_sampler_prepare");
         if (graph) be.check(be.api.osg_graph_launch(be.ctx, graph), "osg_graph_launch");
         else run_steps();
-        const int o = order[i];
-        be.check(be.api.osg_sampler_cfg_multistep(be.ctx, forms[sampler][o], (float*)samp_x, (const float*)ptr(out->f32val), slot(i, 0),
-                                                  o >= 1 ? slot(i, 1) : nullptr, o >= 2 ? slot(i, 2) : nullptr, o >= 3 ? slot(i, 3) : nullptr, prompts, L,
-                                                  c_out[i], guidance, sigma[i], k[0], k[1], k[2], k[3], k[4], dcoef[2 * i], dcoef[2 * i + 1]),
-                 "osg_sampler_cfg_multistep");
+        const int form = forms[sampler][order[i]], r = reads(order[i]);
+        float* h0 = slot(i, 0);
+        const float *h1 = r >= 1 ? slot(i, 1) : nullptr, *h2 = r >= 2 ? slot(i, 2) : nullptr, *h3 = r >= 3 ? slot(i, 3) : nullptr;
+        if (pair)
+            be.check(be.api.osg_sampler_cfg_multistep(be.ctx, form, (float*)samp_x, eps, h0, h1, h2, h3, prompts, L, c_out[i], guidance, sigma[i], k[0], k[1],
+                                                      k[2], k[3], k[4], dcoef[2 * i], dcoef[2 * i + 1]),
+                     "osg_sampler_cfg_multistep");
+        else
+            be.check(be.api.osg_sampler_multistep_single(be.ctx, form, (float*)samp_x, eps, h0, h1, h2, h3, prompts, L, c_out[i], sigma[i], k[0], k[1], k[2],
+                                                         k[3], k[4], dcoef[2 * i], dcoef[2 * i + 1]),
+                     "osg_sampler_multistep_single");
     }
     float ms = 0;
     be.check(be.api.osg_timer_stop(be.ctx, &ms), "osg_timer_stop");
@@ -608,13 +624,25 @@ double Plan::sampler_loop_multistep(const std::string& sample_name, const std::s
     return ms;
 }
 
+double Plan::run_sampler_loop(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
+                              int prompts, float* x, const float* noise, const float* c_in, const float* c_out, const float* t, const float* sigma,
+                              const float* d_sigma, const float* sigma_up, const float* clip, int branches) {
+    if (!m.m_plan) throw std::runtime_error("Model::hip_sampler_loop_single: no plan (call run() first).");
+    const double ms = m.m_plan->sampler_loop(sample_name, timestep_name, out_name, n_steps, prompts, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, 0.f,
+                                             clip, branches);
+    m.m_last_ms = m.m_plan->last_ms();
+    return ms;
+}
+
 double Plan::run_sampler_loop_multistep(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name,
                                        int n_steps, int prompts, int sampler, float* x, const float* c_in, const float* c_out, const float* t,
                                        const float* sigma, const int* order, const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef,
-                                       float guidance) {
-    if (!m.m_plan) throw std::runtime_error("Model::hip_sampler_loop_multistep: no plan (call run() first).");
+                                       float guidance, int branches) {
+    if (!m.m_plan)
+        throw std::runtime_error(std::string(branches == 2 ? "Model::hip_sampler_loop_multistep" : "Model::hip_sampler_loop_multistep_single") +
+                                 ": no plan (call run() first).");
     const double ms = m.m_plan->sampler_loop_multistep(sample_name, timestep_name, out_name, n_steps, prompts, sampler, x, c_in, c_out, t, sigma, order,
-                                                       coef, n_coef, dcoef, n_dcoef, guidance);
+                                                       coef, n_coef, dcoef, n_dcoef, guidance, branches);
     m.m_last_ms = m.m_plan->last_ms();
     return ms;
 }

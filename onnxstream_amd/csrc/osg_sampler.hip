@@ -7,6 +7,10 @@
 //   osg_sampler_cfg_multistep   <- the same CFG combine, then one step of DPM++ 2M / 2M v2, iPNDM / iPNDM_v / iPNDM_vo, Taylor3 or DDIM
 //                                  (src/samplers.h:339-377, :543-582, :688-940, :942-1034, :1078-1100) with a history ring per prompt
 //   osg_sampler_prepare_rescale <- osg_sampler_prepare after DDIM's in-place prescale of x (prescale_sample, src/samplers.h:27-59)
+//   osg_sampler_*_single        <- the same three steps without the guidance pair: CFGDenoiser_CompVisDenoiser returns the cond branch alone in
+//                                  Turbo mode (src/sd.cpp:1537-1541), so the pass holds ONE sample per prompt and den = eps[p]*c_out + x
+// Every kernel is a template on B, the UNet samples ("branches") per prompt: 2 = the cond / uncond pair with the CFG combine, 1 = single.  The
+// update arithmetic after `den` has one body for both.
 // fp32 throughout, in the reference's operation order with every multiply and add rounded separately (no fma contraction), so the device
 // loop reproduces the host loop bit for bit (tests/test_pipeline.py).
 #include "osg_common.h"
@@ -16,20 +20,63 @@
 
 namespace {
 
-__global__ __launch_bounds__(256) void sampler_prepare_kernel(const float* __restrict__ x, float* __restrict__ sample, float* __restrict__ timestep,
-                                                              int prompts, long L, float c_in, float t, long t_per_sample) {
+// eps -> denoised for element e of prompt p (i = p * L + e): B == 2 the CFG combine of the pair eps[2p], eps[2p+1] (src/sd.cpp:1545-1556), B == 1 eps[p] alone
+template <int B>
+__device__ __forceinline__ float sampler_denoised(const float* __restrict__ eps, long p, long L, long e, float xv, float c_out, float guidance) {
+#pragma clang fp contract(off)
+    static_assert(B == 1 || B == 2, "one sample per prompt, or the cond / uncond pair");
+    if constexpr (B == 1) {
+        const float pc = eps[p * L + e] * c_out;
+        return pc + xv;
+    } else {
+        const float pc = eps[(2 * p) * L + e] * c_out, pu = eps[(2 * p + 1) * L + e] * c_out;
+        const float den_c = pc + xv;
+        const float den_u = pu + xv;
+        const float gd = guidance * (den_c - den_u);
+        return den_u + gd;
+    }
+}
+
+// the input side of a step.  RESCALE: DDIM's prescale (src/samplers.h:27-59) folded in: x *= x_scale in place first, the UNet input is the rescaled x.
+// One body; the two kernels below differ in their argument lists only (the plain one has no x_scale and reads x through a const pointer).
+template <int B, bool RESCALE>
+__device__ __forceinline__ void sampler_prepare_body(std::conditional_t<RESCALE, float, const float>* __restrict__ x, float* __restrict__ sample,
+                                                     float* __restrict__ timestep, int prompts, long L, float x_scale, float c_in, float t,
+                                                     long t_per_sample) {
 #pragma clang fp contract(off)
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)prompts * L;
     if (i < total) {
         const long p = i / L, e = i - p * L;
-        const float v = x[i] * c_in;
-        sample[(2 * p) * L + e] = v;          // pushes 2p (cond) and 2p+1 (uncond) see the same scaled latent
-        sample[(2 * p + 1) * L + e] = v;
+        float xs = x[i];
+        if constexpr (RESCALE) {
+            xs = xs * x_scale;
+            x[i] = xs;
+        }
+        const float v = xs * c_in;
+        if constexpr (B == 1) {
+            sample[i] = v;
+        } else {
+            sample[(2 * p) * L + e] = v;          // pushes 2p (cond) and 2p+1 (uncond) see the same scaled latent
+            sample[(2 * p + 1) * L + e] = v;
+        }
     }
-    if (i < 2L * prompts * t_per_sample) timestep[i] = t;
+    if (i < (long)B * prompts * t_per_sample) timestep[i] = t;
 }
 
+template <int B>
+__global__ __launch_bounds__(256) void sampler_prepare_kernel(const float* __restrict__ x, float* __restrict__ sample, float* __restrict__ timestep,
+                                                              int prompts, long L, float c_in, float t, long t_per_sample) {
+    sampler_prepare_body<B, false>(x, sample, timestep, prompts, L, 1.f, c_in, t, t_per_sample);
+}
+
+template <int B>
+__global__ __launch_bounds__(256) void sampler_prepare_rescale_kernel(float* __restrict__ x, float* __restrict__ sample, float* __restrict__ timestep,
+                                                                      int prompts, long L, float x_scale, float c_in, float t, long t_per_sample) {
+    sampler_prepare_body<B, true>(x, sample, timestep, prompts, L, x_scale, c_in, t, t_per_sample);
+}
+
+template <int B>
 __global__ __launch_bounds__(256) void sampler_cfg_euler_a_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ noise,
                                                                   int prompts, long L, float c_out, float guidance, float sigma, float d_sigma, float sigma_up, float clip) {
 #pragma clang fp contract(off)
@@ -37,11 +84,7 @@ __global__ __launch_bounds__(256) void sampler_cfg_euler_a_kernel(float* __restr
     if (i >= (long)prompts * L) return;
     const long p = i / L, e = i - p * L;
     const float xv = x[i];
-    const float pc = eps[(2 * p) * L + e] * c_out, pu = eps[(2 * p + 1) * L + e] * c_out;
-    const float den_c = pc + xv;
-    const float den_u = pu + xv;
-    const float gd = guidance * (den_c - den_u);
-    const float den = den_u + gd;
+    const float den = sampler_denoised<B>(eps, p, L, e, xv, c_out, guidance);
     const float dd = (xv - den) / sigma;          // IEEE division (hipcc keeps fp32 divides correctly rounded), one rounding per operation
     const float st = dd * d_sigma;
     float nx = xv + st;
@@ -53,11 +96,11 @@ __global__ __launch_bounds__(256) void sampler_cfg_euler_a_kernel(float* __restr
     x[i] = nx;
 }
 
-// The multistep samplers of src/samplers.h (ORIGINAL_SAMPLER_ALGORITHMS branch): the same CFG combine as above, then one of the update forms
+// The multistep samplers of src/samplers.h (ORIGINAL_SAMPLER_ALGORITHMS branch): the same den as above, then one of the update forms
 // of include/osgpu.h (osg_multistep_form), each its own straight-line instantiation.  h0 receives this step's history entry (the denoised
 // latent for DPM++, the derivative d otherwise); h1..h3 are the entries of the previous steps (ring slots chosen by the host, never copied).
 // For DPM++ 2M h1 == h0 (one slot, read before it is overwritten), so the history pointers carry no __restrict__.
-template <int F>
+template <int F, int B>
 __global__ __launch_bounds__(256) void sampler_cfg_multistep_kernel(float* __restrict__ x, const float* __restrict__ eps, float* h0, const float* h1,
                                                                     const float* h2, const float* h3, int prompts, long L, float c_out, float guidance,
                                                                     float sigma, float k0, float k1, float k2, float k3, float k4, double da, double db) {
@@ -66,11 +109,7 @@ __global__ __launch_bounds__(256) void sampler_cfg_multistep_kernel(float* __res
     if (i >= (long)prompts * L) return;
     const long p = i / L, e = i - p * L;
     const float xv = x[i];
-    const float pc = eps[(2 * p) * L + e] * c_out, pu = eps[(2 * p + 1) * L + e] * c_out;
-    const float den_c = pc + xv;
-    const float den_u = pu + xv;
-    const float gd = guidance * (den_c - den_u);
-    const float den = den_u + gd;
+    const float den = sampler_denoised<B>(eps, p, L, e, xv, c_out, guidance);
     if constexpr (F == OSG_MS_DDIM) {
         const double ax = (double)xv * da;
         const double bd = (double)den * db;
@@ -164,74 +203,51 @@ __global__ __launch_bounds__(256) void sampler_cfg_multistep_kernel(float* __res
     }
 }
 
-// osg_sampler_prepare with DDIM's prescale (src/samplers.h:27-59) folded in: x *= x_scale in place first, the UNet input is the rescaled x
-__global__ __launch_bounds__(256) void sampler_prepare_rescale_kernel(float* __restrict__ x, float* __restrict__ sample, float* __restrict__ timestep,
-                                                                      int prompts, long L, float x_scale, float c_in, float t, long t_per_sample) {
-#pragma clang fp contract(off)
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    const long total = (long)prompts * L;
-    if (i < total) {
-        const long p = i / L, e = i - p * L;
-        const float xs = x[i] * x_scale;
-        x[i] = xs;
-        const float v = xs * c_in;
-        sample[(2 * p) * L + e] = v;
-        sample[(2 * p + 1) * L + e] = v;
-    }
-    if (i < 2L * prompts * t_per_sample) timestep[i] = t;
-}
-
-}  // namespace
-
-extern "C" {
-
-int osg_sampler_prepare(osg_ctx* ctx, const float* x, float* sample, float* timestep, int prompts, long L, float c_in, float t, long t_per_sample) {
+// the launches behind the entry points, one per step of the loop, each for both branch counts; `fn` names the entry point in error texts
+// x_scale == 1 is the launch without DDIM's prescale: x is not written
+template <int B>
+int launch_prepare(osg_ctx* ctx, float* x, float* sample, float* timestep, int prompts, long L, float x_scale, float c_in, float t, long t_per_sample,
+                   bool rescale) {
     if (prompts <= 0 || L <= 0) return 0;
     const long total = (long)prompts * L;
-    const long n = total > 2L * prompts * t_per_sample ? total : 2L * prompts * t_per_sample;
-    hipLaunchKernelGGL(sampler_prepare_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->compute, x, sample, timestep, prompts, L, c_in, t,
-                       t_per_sample);
+    const long n = total > (long)B * prompts * t_per_sample ? total : (long)B * prompts * t_per_sample;
+    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+    if (rescale)
+        hipLaunchKernelGGL(sampler_prepare_rescale_kernel<B>, grid, block, 0, ctx->compute, x, sample, timestep, prompts, L, x_scale, c_in, t, t_per_sample);
+    else
+        hipLaunchKernelGGL(sampler_prepare_kernel<B>, grid, block, 0, ctx->compute, (const float*)x, sample, timestep, prompts, L, c_in, t, t_per_sample);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
 
-int osg_sampler_cfg_euler_a(osg_ctx* ctx, float* x, const float* eps, const float* noise, int prompts, long L, float c_out, float guidance,
-                            float sigma, float d_sigma, float sigma_up, float clip) {
+template <int B>
+int launch_euler_a(osg_ctx* ctx, float* x, const float* eps, const float* noise, int prompts, long L, float c_out, float guidance, float sigma,
+                   float d_sigma, float sigma_up, float clip) {
     if (prompts <= 0 || L <= 0) return 0;
     const long total = (long)prompts * L;
-    hipLaunchKernelGGL(sampler_cfg_euler_a_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->compute, x, eps, noise, prompts, L, c_out,
+    hipLaunchKernelGGL(sampler_cfg_euler_a_kernel<B>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, ctx->compute, x, eps, noise, prompts, L, c_out,
                        guidance, sigma, d_sigma, sigma_up, clip);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
 
-int osg_sampler_prepare_rescale(osg_ctx* ctx, float* x, float* sample, float* timestep, int prompts, long L, float x_scale, float c_in, float t,
-                                long t_per_sample) {
-    if (prompts <= 0 || L <= 0) return 0;
-    const long total = (long)prompts * L;
-    const long n = total > 2L * prompts * t_per_sample ? total : 2L * prompts * t_per_sample;
-    hipLaunchKernelGGL(sampler_prepare_rescale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->compute, x, sample, timestep, prompts, L,
-                       x_scale, c_in, t, t_per_sample);
-    OSG_LAUNCH_CHECK(ctx);
-    return 0;
-}
-
-int osg_sampler_cfg_multistep(osg_ctx* ctx, int form, float* x, const float* eps, float* h0, const float* h1, const float* h2, const float* h3,
-                              int prompts, long L, float c_out, float guidance, float sigma, float k0, float k1, float k2, float k3, float k4,
-                              double da, double db) {
-    if (form < 0 || form >= OSG_MS_FORMS) OSG_FAIL(ctx, "osg_sampler_cfg_multistep: unknown form " + std::to_string(form));
+template <int B>
+int launch_multistep(osg_ctx* ctx, const char* fn, int form, float* x, const float* eps, float* h0, const float* h1, const float* h2, const float* h3,
+                     int prompts, long L, float c_out, float guidance, float sigma, float k0, float k1, float k2, float k3, float k4, double da,
+                     double db) {
+    if (form < 0 || form >= OSG_MS_FORMS) OSG_FAIL(ctx, std::string(fn) + ": unknown form " + std::to_string(form));
     const int need = form == OSG_MS_DDIM ? 0 : form == OSG_MS_IPNDM3 || form == OSG_MS_IPNDM_VO3 ? 4
                    : form == OSG_MS_IPNDM2 || form == OSG_MS_IPNDM_VO2 || form == OSG_MS_TAYLOR2 ? 3
                    : form == OSG_MS_DPMPP_FIRST || form == OSG_MS_EULER_D ? 1 : 2;    // history pointers the form touches: h0 .. h(need-1)
     const float* hs[4] = {h0, h1, h2, h3};
     for (int k = 0; k < need; k++)
-        if (!hs[k]) OSG_FAIL(ctx, "osg_sampler_cfg_multistep: form " + std::to_string(form) + " needs history pointer h" + std::to_string(k));
+        if (!hs[k]) OSG_FAIL(ctx, std::string(fn) + ": form " + std::to_string(form) + " needs history pointer h" + std::to_string(k));
     if (prompts <= 0 || L <= 0) return 0;
     const long total = (long)prompts * L;
     const dim3 grid((unsigned)((total + 255) / 256)), block(256);
 #define OSG_MS_CASE(F)                                                                                                                              \
     case F:                                                                                                                                         \
-        hipLaunchKernelGGL(sampler_cfg_multistep_kernel<F>, grid, block, 0, ctx->compute, x, eps, h0, h1, h2, h3, prompts, L, c_out, guidance,   \
+        hipLaunchKernelGGL((sampler_cfg_multistep_kernel<F, B>), grid, block, 0, ctx->compute, x, eps, h0, h1, h2, h3, prompts, L, c_out, guidance, \
                            sigma, k0, k1, k2, k3, k4, da, db);                                                                                      \
         break;
     switch (form) {
@@ -243,6 +259,48 @@ int osg_sampler_cfg_multistep(osg_ctx* ctx, int form, float* x, const float* eps
 #undef OSG_MS_CASE
     OSG_LAUNCH_CHECK(ctx);
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int osg_sampler_prepare(osg_ctx* ctx, const float* x, float* sample, float* timestep, int prompts, long L, float c_in, float t, long t_per_sample) {
+    return launch_prepare<2>(ctx, const_cast<float*>(x), sample, timestep, prompts, L, 1.f, c_in, t, t_per_sample, false);
+}
+
+int osg_sampler_prepare_rescale(osg_ctx* ctx, float* x, float* sample, float* timestep, int prompts, long L, float x_scale, float c_in, float t,
+                                long t_per_sample) {
+    return launch_prepare<2>(ctx, x, sample, timestep, prompts, L, x_scale, c_in, t, t_per_sample, true);
+}
+
+int osg_sampler_prepare_single(osg_ctx* ctx, float* x, float* sample, float* timestep, int prompts, long L, float x_scale, float c_in, float t,
+                               long t_per_sample) {
+    return launch_prepare<1>(ctx, x, sample, timestep, prompts, L, x_scale, c_in, t, t_per_sample, x_scale != 1.f);
+}
+
+int osg_sampler_cfg_euler_a(osg_ctx* ctx, float* x, const float* eps, const float* noise, int prompts, long L, float c_out, float guidance,
+                            float sigma, float d_sigma, float sigma_up, float clip) {
+    return launch_euler_a<2>(ctx, x, eps, noise, prompts, L, c_out, guidance, sigma, d_sigma, sigma_up, clip);
+}
+
+int osg_sampler_euler_a_single(osg_ctx* ctx, float* x, const float* eps, const float* noise, int prompts, long L, float c_out, float sigma,
+                               float d_sigma, float sigma_up, float clip) {
+    return launch_euler_a<1>(ctx, x, eps, noise, prompts, L, c_out, 0.f, sigma, d_sigma, sigma_up, clip);
+}
+
+int osg_sampler_cfg_multistep(osg_ctx* ctx, int form, float* x, const float* eps, float* h0, const float* h1, const float* h2, const float* h3,
+                              int prompts, long L, float c_out, float guidance, float sigma, float k0, float k1, float k2, float k3, float k4,
+                              double da, double db) {
+    return launch_multistep<2>(ctx, "osg_sampler_cfg_multistep", form, x, eps, h0, h1, h2, h3, prompts, L, c_out, guidance, sigma, k0, k1, k2, k3, k4,
+                               da, db);
+}
+
+int osg_sampler_multistep_single(osg_ctx* ctx, int form, float* x, const float* eps, float* h0, const float* h1, const float* h2, const float* h3,
+                                 int prompts, long L, float c_out, float sigma, float k0, float k1, float k2, float k3, float k4, double da,
+                                 double db) {
+    return launch_multistep<1>(ctx, "osg_sampler_multistep_single", form, x, eps, h0, h1, h2, h3, prompts, L, c_out, 0.f, sigma, k0, k1, k2, k3, k4,
+                               da, db);
 }
 
 }  // extern "C"

@@ -21,7 +21,7 @@ from .bindings import Model
 f32 = np.float32
 
 
-def _libm_float_fn(name):
+def _libm_float_fn(name, nargs=1):
     """The reference app computes its schedule with the C library's FLOAT functions (std::exp / std::log on float: expf / logf, src/sd.cpp:1402,
     :1608).  numpy's float32 exp / log are its own SIMD kernels and differ from glibc's in the last bit for a third of the table
     (sigma[0] = 14.614644 vs 14.614643) -- one ulp of sigma flips f16 roundings of the UNet input and moves a whole pass by 1e-3.  So the
@@ -31,15 +31,16 @@ def _libm_float_fn(name):
     import math
     try:
         fn = getattr(ctypes.CDLL(ctypes.util.find_library("m") or "libm.so.6"), name + "f")
-        fn.restype, fn.argtypes = ctypes.c_float, [ctypes.c_float]
-        return lambda v: f32(fn(float(v)))
+        fn.restype, fn.argtypes = ctypes.c_float, [ctypes.c_float] * nargs
+        return lambda *v: f32(fn(*[float(a) for a in v]))
     except (OSError, AttributeError):
         dbl = getattr(math, name)
-        return lambda v: f32(dbl(float(v)))
+        return lambda *v: f32(dbl(*[float(a) for a in v]))
 
 
 expf, logf = _libm_float_fn("exp"), _libm_float_fn("log")
 expm1f, sqrtf = _libm_float_fn("expm1"), _libm_float_fn("sqrt")
+powf = _libm_float_fn("pow", 2)
 
 # the samplers of the reference's --sampler (src/sd.cpp:41-63) that sample() and sample_device() run: the default Euler-Ancestral, Euler, and the
 # one-evaluation, noise-free multistep samplers of src/samplers.h (the ORIGINAL_SAMPLER_ALGORITHMS branch)
@@ -47,12 +48,44 @@ SAMPLERS = ("euler_a", "euler", "dpm++2m", "dpm++2mv2", "ipndm", "ipndm_v", "ipn
 # multistep sampler -> loop form of model_hip_sampler_loop_multistep (exports.cpp)
 MULTISTEP = {"dpm++2m": 0, "dpm++2mv2": 0, "ipndm": 1, "ipndm_v": 2, "ipndm_vo": 3, "taylor3": 4, "ddim": 5}
 # loop form -> (history depth as src/samplers.h create_buffers, the osg_multistep_form of each order); the table of Plan::sampler_loop_multistep
-_MS_LOOP = {0: (1, (0, 1)), 1: (4, (2, 3, 5, 6)), 2: (4, (2, 4, 5, 6)), 3: (4, (2, 7, 8, 9)), 4: (3, (2, 10, 11)), 5: (0, (12,))}
+# (order 2 of loop form 0 is the plain Euler step the reference substitutes on the last step of an SDXL image, src/sd.cpp:1705-1719)
+_MS_LOOP = {0: (1, (0, 1, 2)), 1: (4, (2, 3, 5, 6)), 2: (4, (2, 4, 5, 6)), 3: (4, (2, 7, 8, 9)), 4: (3, (2, 10, 11)), 5: (0, (12,))}
 
 
 def _check_sampler(sampler: str) -> None:
     if sampler not in SAMPLERS:
         raise ValueError(f"unknown sampler {sampler!r}; valid names: {', '.join(SAMPLERS)}")
+
+
+# pow(2.f, -p - .5f) with the reference's constexpr p = 0 (src/samplers.h:101-103), stated as the constant the compiler folds it to: the correctly
+# rounded float of 2 ** -0.5 (glibc's powf returns the same value at run time)
+_RESHAPER_BASE = f32(0.70710677)
+
+
+def sigma_reshaper(si1, i: int, steps: int, turbo: bool):
+    """sigma_reshaper of process_sample (src/samplers.h:97-106): what the non-ancestral samplers read in place of sigma[i + 1] for the Turbo model;
+    the identity outside Turbo mode.  Float arithmetic in the reference's expression tree, pow = powf."""
+    si1 = f32(si1)
+    if not turbo:
+        return si1
+    e = f32(_RESHAPER_BASE / f32(steps))
+    curve = f32(f32(powf(f32(f32(steps - i) / f32(steps)), e) + powf(f32(f32(i + 1) / f32(steps)), e)) / f32(2))
+    return f32(si1 * (max(f32(0.0001), curve) if curve else f32(0)))
+
+
+def sigma_reshaper_sharp(si1, i: int, steps: int, turbo: bool):
+    """sigma_reshaper_sharp (src/samplers.h:109-113): the correction of sigma_reshaper scaled by the signed cube root of 3 / (steps - 2.5)."""
+    si1 = f32(si1)
+    pre = sigma_reshaper(si1, i, steps, turbo)
+    if pre == si1:
+        return si1
+    smooth = f32(f32(3) / f32(f32(steps) - f32(2.5)))
+    return f32(si1 + f32(f32(f32(smooth / abs(smooth)) * powf(abs(smooth), f32(f32(1) / f32(3)))) * f32(pre - si1)))
+
+
+def _per_prompt(v, P: int) -> list:
+    """an argument given once per call, or as a list with one entry per prompt -> the list"""
+    return list(v) if isinstance(v, (list, tuple)) else [v] * P
 
 
 def multistep_update(form: int, x: np.ndarray, den: np.ndarray, hist, sigma, k, dk) -> np.ndarray:
@@ -220,7 +253,7 @@ class Txt2Img:
                     m._set_option("hip_autotune", int(bool(autotune)))
             m.read_file(d + "model.txt")
         self._configured: Dict[int, bool] = {}
-        self._dev_ready: Dict[tuple, bool] = {}
+        self._dev_ready: Dict[tuple, int] = {}       # sample_device: (model, prompts[, samples per prompt]) -> hip_plans_built() when that plan was captured
         self.last_loop_ms = 0.0
         self._vae_dir = vae_dir
         self._dec_ready = None        # decode_device: (key, upscale factor, plans built) of the decoder plan that is resident and captured
@@ -257,8 +290,10 @@ class Txt2Img:
         return res
 
     def denoise(self, x: np.ndarray, sigma: float, cond: np.ndarray, uncond: np.ndarray, guidance: float = 7.0,
-                extra_cond: Optional[Dict[str, np.ndarray]] = None, extra_uncond: Optional[Dict[str, np.ndarray]] = None) -> np.ndarray:
-        """CFGDenoiser_CompVisDenoiser: eps-prediction wrapped as a denoiser, then the CFG combine (src/sd.cpp:1397-1559)."""
+                extra_cond=None, extra_uncond=None, turbo: bool = False) -> np.ndarray:
+        """CFGDenoiser_CompVisDenoiser: eps-prediction wrapped as a denoiser, then the CFG combine (src/sd.cpp:1397-1559).  extra_cond / extra_uncond:
+        SDXL's micro-conditioning (text_embeds [1,1280], time_ids [1,6]; src/sd.cpp:1488-1516) pushed along with each branch -- a dict, or a list
+        with one dict per prompt.  turbo: the cond branch alone (:1537-1541), one UNet sample per prompt; uncond is not read."""
         n = self.names
         c_out = f32(-1.0 * sigma)
         c_in = f32(1.0 / np.sqrt(f32(sigma) * f32(sigma) + 1))
@@ -266,25 +301,36 @@ class Txt2Img:
             self._t_cache[sigma] = sigma_to_t(sigma, self.log_sigmas)
         t = f32(self._t_cache[sigma])
         xin = (x * c_in).astype(f32)
+        B = 1 if turbo else 2
         if xin.shape[0] > 1 and isinstance(cond, (list, tuple)):
             # several prompts at the same step of the schedule (the reference's `--num N` batching, src/sd.cpp:1098-1161): 2N samples
-            # pushed under the same names -> ONE batched pass; prompt p = pushes 2p (cond) and 2p+1 (uncond)
+            # pushed under the same names -> ONE batched pass; prompt p = pushes 2p (cond) and 2p+1 (uncond); in Turbo mode N samples, prompt p = push p
+            P = xin.shape[0]
+            extras = (_per_prompt(extra_cond, P), _per_prompt(extra_uncond, P))
             pushes = []
-            for p_i in range(xin.shape[0]):
-                for c in (cond[p_i], uncond[p_i]):
+            for p_i in range(P):
+                for br, c in enumerate((cond[p_i],) if turbo else (cond[p_i], uncond[p_i])):
                     pushes.append({n["timestep"]: np.asarray([t], f32), n["sample"]: xin[p_i:p_i + 1], n["ctx"]: c})
+                    if extras[br][p_i]:
+                        pushes[-1].update(extras[br][p_i])
             eps = self._run(self.unet, pushes, n["out"])
-            den_c = np.concatenate(eps[0::2]) * c_out + x
+            den_c = np.concatenate(eps[0::B]) * c_out + x
+            if turbo:
+                return den_c.astype(f32)
             den_u = np.concatenate(eps[1::2]) * c_out + x
             return (den_u + f32(guidance) * (den_c - den_u)).astype(f32)
-        pushes = [{n["timestep"]: np.asarray([t], f32), n["sample"]: xin, n["ctx"]: c} for c in (cond, uncond)]
+        pushes = [{n["timestep"]: np.asarray([t], f32), n["sample"]: xin, n["ctx"]: c} for c in ((cond,) if turbo else (cond, uncond))]
         # SDXL micro-conditioning (text_embeds [1,1280], time_ids [1,6]; reference src/sd.cpp:1488-1516) rides along per branch
         for push, extra in zip(pushes, (extra_cond, extra_uncond)):
+            if isinstance(extra, (list, tuple)):
+                extra = extra[0]
             if extra:
                 push.update(extra)
-        eps_c, eps_u = self._run(self.unet, pushes, n["out"])
-        den_c = eps_c * c_out + x
-        den_u = eps_u * c_out + x
+        eps = self._run(self.unet, pushes, n["out"])
+        den_c = eps[0] * c_out + x
+        if turbo:
+            return den_c.astype(f32)
+        den_u = eps[1] * c_out + x
         return (den_u + f32(guidance) * (den_c - den_u)).astype(f32)
 
     @staticmethod
@@ -300,36 +346,42 @@ class Txt2Img:
 
     def sample(self, cond: np.ndarray, uncond: np.ndarray, steps: int = 20, seed: int = 42, latent_shape=(1, 4, 64, 64),
                on_step: Optional[Callable[[int, np.ndarray], None]] = None, init_latent: Optional[np.ndarray] = None,
-               step_noise: Optional[Callable[[int], np.ndarray]] = None, sampler: str = "euler_a") -> np.ndarray:
+               step_noise: Optional[Callable[[int], np.ndarray]] = None, sampler: str = "euler_a", extra_cond=None, extra_uncond=None,
+               xl: bool = False, turbo: bool = False) -> np.ndarray:
         """diffusion_solver (src/sd.cpp:1574-1780) with the default sampler, Euler Ancestral as the shipped reference runs it
         (src/samplers.h:1431-1449, ORIGINAL_SAMPLER_ALGORITHMS):  x += ((x - d) / sigma_i) * (sigma_down - sigma_i) + r * sigma_up,
         every operation rounded to float on its own.  init_latent: N(0,1) start (default: numpy stream; the reference draws
         randn_4_w_h(seed % 1000), :1595) -- it is scaled by sigma[0] here as :1611-1612 does; step_noise(i): the ancestral noise of step i.
         sampler="euler": the plain Euler step of the same branch (src/samplers.h:116-126): x += (x - d) / sigma_i * (sigma_{i+1} - sigma_i), no noise.
         The multistep samplers of MULTISTEP (DPM++ 2M / 2M v2, iPNDM, iPNDM_v, iPNDM_vo, Taylor3, DDIM) take their per-step scalars from
-        multistep_table() and step with multistep_update(), the host restatement of the device kernel; they draw no noise."""
+        multistep_table() and step with multistep_update(), the host restatement of the device kernel; they draw no noise.
+        extra_cond / extra_uncond: SDXL's micro-conditioning, as denoise() takes it.  xl: the reference's `--xl` (the DPM++ pair takes the Euler step on
+        the last step, multistep_table()).  turbo: `--turbo` -- implies xl; one UNet sample per prompt and no guidance (uncond may be None), the
+        Turbo forms of sigma_reshaper / sigma_reshaper_sharp and of DDIM's prescale, any steps >= 1 (src/sd.cpp:2923)."""
         _check_sampler(sampler)
+        xl = xl or turbo
+        dn = dict(extra_cond=extra_cond, extra_uncond=extra_uncond, turbo=turbo)
         sig = sigma_schedule(steps, self.log_sigmas)
         rng = np.random.default_rng(seed)     # the reference draws mt19937 normals; any N(0,1) stream is equivalent for the harness
         x0 = rng.standard_normal(latent_shape, dtype=f32) if init_latent is None else np.asarray(init_latent, f32).reshape(latent_shape)
         x = (x0 * f32(sig[0])).astype(f32)
         if sampler in MULTISTEP:
-            loop, order, coef, dcoef = self.multistep_table(sig, sampler)
+            loop, order, coef, dcoef = self.multistep_table(sig, sampler, xl=xl, turbo=turbo)
             depth, forms = _MS_LOOP[loop]
             ring = [np.zeros(x.shape, f32) for _ in range(depth)]
             for i in range(steps):
                 if loop == 5:         # DDIM's prescale_sample (src/samplers.h:27-59), before the denoiser sees x
                     x = (x * coef[i, 5]).astype(f32)
-                den = self.denoise(x, float(sig[i]), cond, uncond)
+                den = self.denoise(x, float(sig[i]), cond, uncond, **dn)
                 hist = [ring[(i - k) % depth] if depth and k <= order[i] else None for k in range(4)]
                 x = multistep_update(forms[order[i]], x, den, hist, sig[i], coef[i], dcoef[i])
                 if on_step:
                     on_step(i, x)
             return x
         for i in range(steps):
-            den = self.denoise(x, float(sig[i]), cond, uncond)
+            den = self.denoise(x, float(sig[i]), cond, uncond, **dn)
             if sampler == "euler":
-                x = (x + f32(f32(x - den) / f32(sig[i])) * f32(f32(sig[i + 1]) - f32(sig[i]))).astype(f32)
+                x = (x + f32(f32(x - den) / f32(sig[i])) * f32(sigma_reshaper(sig[i + 1], i, steps, turbo) - f32(sig[i]))).astype(f32)
                 if on_step:
                     on_step(i, x)
                 continue
@@ -340,9 +392,10 @@ class Txt2Img:
                 on_step(i, x)
         return x
 
-    def loop_scalars(self, sig: np.ndarray, sampler: str = "euler_a"):
+    def loop_scalars(self, sig: np.ndarray, sampler: str = "euler_a", turbo: bool = False):
         """Per-step fp32 scalars of the loop, computed exactly as denoise()/sample() do: c_in, c_out, t (sigma_to_t), sigma_i, d_sigma =
-        sigma_down - sigma_i and sigma_up of the Euler-Ancestral update."""
+        sigma_down - sigma_i and sigma_up of the Euler-Ancestral update.  turbo: Euler reads sigma_{i+1} through sigma_reshaper (src/samplers.h:119);
+        Euler-Ancestral does not."""
         steps = len(sig) - 1
         c_in, c_out, ts, s_arr, d_sigma, s_up = (np.empty(steps, f32) for _ in range(6))
         for i in range(steps):
@@ -354,16 +407,19 @@ class Txt2Img:
             ts[i] = f32(self._t_cache[sigma])
             sigma_up, sigma_down = self.ancestral_step_scalars(sig[i], sig[i + 1])
             if sampler == "euler":      # (the Euler step is the ancestral one with sigma_down = sigma_{i+1} and no noise, src/samplers.h:116-126)
-                sigma_up, sigma_down = f32(0.0), f32(sig[i + 1])
+                sigma_up, sigma_down = f32(0.0), sigma_reshaper(sig[i + 1], i, steps, turbo)
             s_arr[i] = f32(sig[i])
             d_sigma[i] = f32(sigma_down - f32(sig[i]))
             s_up[i] = sigma_up
         return c_in, c_out, ts, s_arr, d_sigma, s_up
 
-    def multistep_table(self, sig: np.ndarray, sampler: str):
+    def multistep_table(self, sig: np.ndarray, sampler: str, xl: bool = False, turbo: bool = False):
         """Per-step scalars of a multistep sampler, as the reference's process_sample computes them (src/samplers.h, ORIGINAL_SAMPLER_ALGORITHMS;
-        the loop-invariant per-element coefficients hoisted with the same expression tree, every operation rounded to float; sigma_reshaper and
-        sigma_reshaper_sharp are the identity outside Turbo mode).  Returns (loop form, order [steps] int32, coef [steps, 6] float32 = k0..k4 of
+        the loop-invariant per-element coefficients hoisted with the same expression tree, every operation rounded to float).  Every sampler reads
+        sigma[i + 1] -- and no other sigma -- through a reshaper: sigma_reshaper for DPM++ 2M and the iPNDM family, sigma_reshaper_sharp for DPM++ 2M v2,
+        Taylor3 and DDIM; both are the identity unless `turbo`, which also softens DDIM's prescale after the first step (src/samplers.h:50-59).
+        xl (implied by turbo): the reference's SDXL rule (src/sd.cpp:1705-1719) -- the DPM++ pair takes the plain Euler step of src/samplers.h:116-126
+        on the last step, order 2 of loop form 0, which reads no history.  Returns (loop form, order [steps] int32, coef [steps, 6] float32 = k0..k4 of
         the step's osg_multistep_form and DDIM's prescale factor of x, dcoef [steps, 2] float64 = DDIM's (a, b))."""
         _check_sampler(sampler)
         if sampler not in MULTISTEP:
@@ -375,10 +431,15 @@ class Txt2Img:
         dcoef = np.zeros((steps, 2), np.float64)
         one, two = f32(1), f32(2)
         dt_prev = None
+        xl = xl or turbo
+        reshape = sigma_reshaper_sharp if sampler in ("dpm++2mv2", "taylor3", "ddim") else sigma_reshaper
         for i in range(steps):
-            s, s1 = f32(sig[i]), f32(sig[i + 1])
+            s, s1 = f32(sig[i]), reshape(sig[i + 1], i, steps, turbo)
             sp = f32(sig[i - 1]) if i else None
-            if sampler in ("dpm++2m", "dpm++2mv2"):               # src/samplers.h:339-377, :543-582
+            if xl and i == steps - 1 and sampler in ("dpm++2m", "dpm++2mv2"):      # the sampler IS Euler for this step: sigma_reshaper, src/samplers.h:119-125
+                order[i] = 2
+                coef[i, 0] = f32(sigma_reshaper(sig[i + 1], i, steps, turbo) - s)
+            elif sampler in ("dpm++2m", "dpm++2mv2"):             # src/samplers.h:339-377, :543-582
                 if i == 0 or s1 == 0:
                     with np.errstate(divide="ignore"):
                         coef[i, :2] = f32(s1 / s), expm1f(f32(logf(s1) - logf(s)))       # log(0) = -inf, expm1(-inf) = -1 on the last step
@@ -443,6 +504,8 @@ class Txt2Img:
                 dt_prev = dt
             else:                                                         # ddim, src/samplers.h:1078-1100 and prescale_sample :27-59
                 root = sqrtf(f32(f32(s * s) + one))
+                if turbo and i:                                           # "soften correction for Turbo model": pow(scale, 0.9925f - 2.5f / steps / steps)
+                    root = powf(root, f32(f32(0.9925) - f32(f32(f32(2.5) / f32(steps)) / f32(steps))))
                 coef[i, 5] = f32(root / s) if i == 0 else root
                 sn2 = float(f32(s1 * s1))
                 alpha = 1.0 / (sn2 + 1.0)
@@ -452,44 +515,55 @@ class Txt2Img:
 
     def sample_device(self, cond, uncond, steps: int = 20, seed: int = 42, latent_shape=(1, 4, 64, 64), guidance: float = 7.0,
                       init_latent: Optional[np.ndarray] = None, step_noise: Optional[Callable[[int], np.ndarray]] = None,
-                      sampler: str = "euler_a") -> np.ndarray:
+                      sampler: str = "euler_a", extra_cond=None, extra_uncond=None, xl: bool = False, turbo: bool = False) -> np.ndarray:
         """sample() with the whole loop enqueued on the GPU (HIP backend only): per step a scaling kernel fills the UNet's input staging,
         the captured pass is launched, and one kernel does eps -> denoised, the CFG combine and the Euler-Ancestral update -- no host
         round trip until the last step.  Same schedule, same random stream, same fp32 operation order as sample(): the two agree bit
-        for bit.  The multistep samplers (MULTISTEP) run their update kernel (osg_sampler_cfg_multistep) with a history ring on the device.  cond / uncond: one context each, or lists with one entry per prompt (latent_shape[0] prompts)."""
+        for bit.  The multistep samplers (MULTISTEP) run their update kernel (osg_sampler_cfg_multistep) with a history ring on the device.  cond / uncond: one context each, or lists with one entry per prompt (latent_shape[0] prompts).
+        extra_cond / extra_uncond, xl, turbo: as sample().  In Turbo mode the pass holds one sample per prompt and the guidance-free kernels
+        (osg_sampler_*_single) run; the extras stay resident with the contexts and are refreshed with them when the plan is reused."""
         _check_sampler(sampler)
         if not self.batched:
             raise RuntimeError("sample_device needs the HIP backend (batched=True)")
-        n, P = self.names, latent_shape[0]
-        conds = list(cond) if isinstance(cond, (list, tuple)) else [cond] * P
-        unconds = list(uncond) if isinstance(uncond, (list, tuple)) else [uncond] * P
+        xl = xl or turbo
+        n, P, B = self.names, latent_shape[0], 1 if turbo else 2
+        conds, unconds = _per_prompt(cond, P), _per_prompt(uncond, P)
+        extras = (_per_prompt(extra_cond, P), _per_prompt(extra_uncond, P))
         sig = sigma_schedule(steps, self.log_sigmas)
         rng = np.random.default_rng(seed)
         x0 = rng.standard_normal(latent_shape, dtype=f32) if init_latent is None else np.asarray(init_latent, f32).reshape(latent_shape)
         x = np.ascontiguousarray(x0 * f32(sig[0]), f32)
-        c_in, c_out, ts, s_arr, d_sigma, s_up = self.loop_scalars(sig, "euler" if sampler in MULTISTEP else sampler)
+        c_in, c_out, ts, s_arr, d_sigma, s_up = self.loop_scalars(sig, "euler" if sampler in MULTISTEP else sampler, turbo=turbo)
         if sampler not in MULTISTEP:
             noise = np.empty((steps,) + tuple(latent_shape), f32)
             for i in range(steps):
                 noise[i] = rng.standard_normal(latent_shape, dtype=f32) if step_noise is None else np.asarray(step_noise(i), f32).reshape(latent_shape)
-        key = (id(self.unet), P)
-        if self._dev_ready.get(key):
-            for p in range(P):      # plan + captured pass exist: only the contexts change between images
-                self.unet.hip_set_input(n["ctx"], 2 * p, conds[p])
-                self.unet.hip_set_input(n["ctx"], 2 * p + 1, unconds[p])
+        # a Model keeps one plan: the one of this batch (P prompts, B samples each) is resident iff no other was built since it was captured
+        key = (id(self.unet), P) if B == 2 else (id(self.unet), P, B)
+        if self._dev_ready.get(key) == self.unet.hip_plans_built():
+            for p in range(P):      # plan + captured pass exist: only the contexts (and SDXL's extras) change between images
+                for br, c in enumerate((conds[p], unconds[p])[:B]):
+                    self.unet.hip_set_input(n["ctx"], B * p + br, c)
+                    for name, v in (extras[br][p] or {}).items():
+                        self.unet.hip_set_input(name, B * p + br, v)
         else:
             for _ in range(2):      # run() #1 plans and runs eagerly, #2 captures the pass; both leave the contexts resident
                 if P > 1:
-                    self.denoise(x, float(sig[0]), conds, unconds, guidance)
+                    self.denoise(x, float(sig[0]), conds, unconds, guidance, extras[0], extras[1], turbo)
                 else:
-                    self.denoise(x, float(sig[0]), conds[0], unconds[0], guidance)
-            self._dev_ready[key] = True
+                    self.denoise(x, float(sig[0]), conds[0], unconds[0], guidance, extras[0][0], extras[1][0], turbo)
+            self._dev_ready[key] = self.unet.hip_plans_built()
+        io = (n["sample"], n["timestep"], n["out"], x)
         if sampler in MULTISTEP:
-            loop, order, coef, dcoef = self.multistep_table(sig, sampler)
-            self.last_loop_ms = self.unet.hip_sampler_loop_multistep(n["sample"], n["timestep"], n["out"], x, loop, c_in, c_out, ts, s_arr, order, coef,
-                                                                     dcoef, guidance)
-            return x
-        self.last_loop_ms = self.unet.hip_sampler_loop(n["sample"], n["timestep"], n["out"], x, noise, c_in, c_out, ts, s_arr, d_sigma, s_up, guidance)
+            loop, order, coef, dcoef = self.multistep_table(sig, sampler, xl=xl, turbo=turbo)
+            if turbo:
+                self.last_loop_ms = self.unet.hip_sampler_loop_multistep_single(*io, loop, c_in, c_out, ts, s_arr, order, coef, dcoef)
+            else:
+                self.last_loop_ms = self.unet.hip_sampler_loop_multistep(*io, loop, c_in, c_out, ts, s_arr, order, coef, dcoef, guidance)
+        elif turbo:
+            self.last_loop_ms = self.unet.hip_sampler_loop_single(*io, noise, c_in, c_out, ts, s_arr, d_sigma, s_up)
+        else:
+            self.last_loop_ms = self.unet.hip_sampler_loop(*io, noise, c_in, c_out, ts, s_arr, d_sigma, s_up, guidance)
         return x
 
     def decode(self, latents: np.ndarray, factor: float = 5.48998) -> np.ndarray:
@@ -570,10 +644,14 @@ class Txt2Img:
         self.last_decode_ms = self.vae.hip_decode(in_name, out_name, lat, factor, image, pixels)
         return (image, pixels) if want == "both" else image if want == "f32" else pixels
 
-    def txt2img(self, cond: np.ndarray, uncond: np.ndarray, steps: int = 20, seed: int = 42, latent_shape=(1, 4, 64, 64)) -> np.ndarray:
-        return self.decode(self.sample(cond, uncond, steps, seed, latent_shape))
+    def txt2img(self, cond: np.ndarray, uncond: np.ndarray, steps: int = 20, seed: int = 42, latent_shape=(1, 4, 64, 64), extra_cond=None,
+                extra_uncond=None, xl: bool = False, turbo: bool = False) -> np.ndarray:
+        return self.decode(self.sample(cond, uncond, steps, seed, latent_shape, extra_cond=extra_cond, extra_uncond=extra_uncond, xl=xl, turbo=turbo))
 
     def txt2img_device(self, cond, uncond, steps: int = 20, seed: int = 42, latent_shape=(1, 4, 64, 64), sampler: str = "euler_a",
-                       factor: float = 5.48998, names=None, want: str = "f32", tile: Optional[int] = None):
+                       factor: float = 5.48998, names=None, want: str = "f32", tile: Optional[int] = None, extra_cond=None, extra_uncond=None,
+                       xl: bool = False, turbo: bool = False):
         """txt2img() on the device: sample_device() then decode_device() -- two host syncs per image batch"""
-        return self.decode_device(self.sample_device(cond, uncond, steps, seed, latent_shape, sampler=sampler), factor, names, want, tile)
+        lat = self.sample_device(cond, uncond, steps, seed, latent_shape, sampler=sampler, extra_cond=extra_cond, extra_uncond=extra_uncond, xl=xl,
+                                 turbo=turbo)
+        return self.decode_device(lat, factor, names, want, tile)
