@@ -207,10 +207,11 @@ int osg_gemm_rowstats(osg_ctx* ctx, const void* A, const void* B_nk, const void*
  *   out[4] the reduce kernel that finished the split: 0 none, 1 splitk_reduce_kernel, 2 / 3 splitk_reduce4_kernel<4 / 8>, 4 / 5 splitk_reduce_stats_kernel<4 / 8> */
 int osg_last_route(const osg_ctx* ctx, int out[5]);
 /* The same kind of record for the attention and normalisation entry points -- osg_attention / osg_attention_strided / osg_sdpa, osg_group_norm_nhwc,
- * osg_group_norm_stats_nhwc, osg_layer_norm, osg_instance_norm: what the most recent of these calls on ctx launched.  A sibling of osg_last_route and not
+ * osg_group_norm_stats_nhwc, osg_layer_norm, osg_instance_norm, osg_tblock_tail: what the most recent of these calls on ctx launched.  A sibling of osg_last_route and not
  * more family codes of it: the two records are independent (a contraction does not clear this one, nor the reverse) and this one has eight fields.  Host
  * stores at launch time only: no device work, nothing added to a captured graph.
- *   out[0] family: 0 attention, 1 GroupNorm, 2 LayerNorm, 3 InstanceNorm; -1 none yet.  Fields a family does not list are 0.
+ *   out[0] family: 0 attention, 1 GroupNorm, 2 LayerNorm, 3 InstanceNorm, 4 the transformer-block tail (osg_tblock_tail); -1 none yet.  Fields a family does
+ *          not list are 0.
  *   attention:    out[1] 1 attn_kernel<DP, DT, QT, BKV>, 2 attn2_kernel<D, QT, NST>;  out[2] DP (attn_kernel) / D (attn2_kernel);  out[3] DT / NST;
  *                 out[4] QT (a workgroup covers 64 QT query rows);  out[5] BKV, the keys per tile (attn2_kernel: 64);  out[6] workgroups launched
  *   GroupNorm:    out[1] route: 0 gn_slab_kernel<NV, false>, 1 the cluster gn_slab_kernel<NV, true>, 2 three passes with the partials folded in the apply
@@ -219,7 +220,9 @@ int osg_last_route(const osg_ctx* ctx, int out[5]);
  *                 out[2] NV, row vectors per thread (routes 0, 1);  out[3] threads per block;  out[4] groups per block (routes 0, 1);
  *                 out[5] S: blocks per slab (route 1), statistics slabs per image (routes 2-4), 1 otherwise;  out[6] apply slabs per image (routes 2-5)
  *   LayerNorm:    out[1] NV of layer_norm_kernel<f16, NV>, 0 = layer_norm_generic_kernel;  out[2] the osg_dtype
- *   InstanceNorm: out[1] threads per block;  out[2] the osg_dtype */
+ *   InstanceNorm: out[1] threads per block;  out[2] the osg_dtype
+ *   block tail:   out[1] rows per row block (32 / 64);  out[2] NS, the register slots of the weight ring (2 / 3);  out[3] row blocks launched;
+ *                 out[4] weight-prefetching workgroups launched behind them (0 / 8);  out[5] 1 = proj_out ran (wpo != NULL);  out[6] 1 = a second destination */
 int osg_last_kernel(const osg_ctx* ctx, int out[8]);
 
 /* The hot kernels take what their first memory requests depend on as leading scalar kernel parameters (preloaded into scalar registers at wave start), some of them

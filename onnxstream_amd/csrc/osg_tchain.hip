@@ -793,6 +793,7 @@ int osg_tblock_tail(osg_ctx* ctx, const osg_tblock_tail_args* a) {
     else rc = launch(osg_tb::tblock_tail_kernel<2, 320, 40, 5, 2>, 3 * 5 * osg_tb::kTileBytes<2> + vec_bytes, attr32);
     if (rc) return rc;
     OSG_LAUNCH_CHECK(ctx);
+    osg_set_kernel(ctx, 4, rows, rows == 32 && ns3 ? 3 : 2, nblk, npf, a->wpo ? 1 : 0, a->out2 ? 1 : 0);
     return 0;
 }
 

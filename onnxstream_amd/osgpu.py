@@ -237,7 +237,7 @@ class Gpu:
         return tuple(r)
 
     def last_kernel(self):
-        """osg_last_kernel: what the most recent attention / GroupNorm / LayerNorm / InstanceNorm call launched (eight fields, include/osgpu.h)"""
+        """osg_last_kernel: what the most recent attention / GroupNorm / LayerNorm / InstanceNorm / transformer-block tail call launched (eight fields, include/osgpu.h)"""
         r = (ctypes.c_int * 8)()
         self._ck(self.lib.osg_last_kernel(self.ctx, r))
         return tuple(r)
@@ -396,12 +396,27 @@ class Gpu:
         self._ck(self.lib.osg_copy(self.ctx, vtp.ptr, dst.ptr + n * 2, n * 2))
         return kp, vtp
 
+    def tblock_kv_pack_jobs(self, base: DevBuf, ld: int, imgs: int, tk: int, heads: int, jobs, out: Optional[DevBuf] = None):
+        """osg_tblock_kv_pack_jobs as the planner calls it: every job of `jobs` = (k_col, v_col, D) reads two column ranges of the one matrix `base`
+        ([imgs * tk] rows, ld elements apart) in ONE launch.  Returns (dst, [element offset of each job's packs inside dst]): at an offset kp
+        [imgs, heads, 80, DP], and osg_tblock_kv_pack_elems further on vtp [imgs, heads, DP, 80]."""
+        offs, total = [], 0
+        for _, _, d in jobs:
+            offs.append(total)
+            total += 2 * self.lib.osg_tblock_kv_pack_elems(imgs, heads, d)
+        table = self.to_dev(np.array([[kc, vc, d, o] for (kc, vc, d), o in zip(jobs, offs)], np.int32))
+        dst = self._out(out, (total,), base.dtype)
+        self._ck(self.lib.osg_tblock_kv_pack_jobs(self.ctx, base.ptr, ld, imgs, tk, heads, len(offs), table.ptr, dst.ptr))
+        self.sync()           # (the job table is read by the launch: it may go once the launch has run)
+        table.free()
+        return dst, offs
+
     TBLOCK_WEIGHTS = ("wo1", "wq2", "wo2", "w1", "w2", "wpo")
 
-    def tblock_pack_weight(self, w_nk: DevBuf) -> DevBuf:
+    def tblock_pack_weight(self, w_nk: DevBuf, out: Optional[DevBuf] = None) -> DevBuf:
         """[N, K] (k contiguous) -> the kn8 layout osg_tblock_tail streams, returned as a [K/8, N, 8] buffer"""
         n, k = w_nk.shape
-        out = self.empty((k // 8, n, 8), w_nk.dtype)
+        out = self._out(out, (k // 8, n, 8), w_nk.dtype)
         self._ck(self.lib.osg_tblock_pack_weight(self.ctx, w_nk.ptr, n, k, out.ptr))
         return out
 
@@ -410,20 +425,25 @@ class Gpu:
         return {n: (self.tblock_pack_weight(self.to_dev(t)) if n in self.TBLOCK_WEIGHTS else self.to_dev(t)) for n, t in w.items()}
 
     def tblock_tail(self, a1: DevBuf, x0: DevBuf, w: dict, kp: DevBuf, vtp: DevBuf, tk: int, heads: int, scale: float, rows_per_img: int, eps: float = 1e-5,
-                    xin: Optional[DevBuf] = None, out2: Optional[DevBuf] = None, out2_col: int = 0, debug: bool = False, out: Optional[DevBuf] = None, stamps: Optional[DevBuf] = None, rows_per_block: int = 0):
-        """osg_tblock_tail.  w: dict of DevBuf -- wo1 bo1 g2 be2 wq2 wo2 bo2 g3 be3 w1 b1 w2 b2 [wpo bpo]; weights in the kn8 layout (tblock_weights).  Returns (out, [dumps])."""
+                    xin: Optional[DevBuf] = None, out2: Optional[DevBuf] = None, out2_col: int = 0, debug: bool = False, out: Optional[DevBuf] = None, stamps: Optional[DevBuf] = None, rows_per_block: int = 0,
+                    out_col: Optional[int] = None):
+        """osg_tblock_tail.  w: dict of DevBuf -- wo1 [bo1] g2 be2 wq2 [bq2] wo2 [bo2] g3 be3 w1 [b1] w2 [b2] [wpo bpo]; weights in the kn8 layout (tblock_weights).
+        out: a dense [m, c] buffer (the default: a fresh one) or, with out_col given, a wider [m, pitch] buffer whose columns [out_col, out_col + c) are
+        written (a Concat slot, as out2 / out2_col).  Returns (out, [dumps])."""
         m, c = a1.shape
         a = TBlockTailArgs()
         a.a1, a.x0 = a1.ptr, x0.ptr
-        for k_ in ("wo1", "bo1", "g2", "be2", "wq2", "wo2", "bo2", "g3", "be3", "w1", "b1", "w2", "b2", "wpo", "bpo"):
+        for k_ in ("wo1", "bo1", "g2", "be2", "wq2", "wo2", "bo2", "g3", "be3", "w1", "b1", "w2", "b2", "wpo", "bpo", "bq2"):
             setattr(a, k_, w[k_].ptr if w.get(k_) is not None else None)
-        a.bq2 = None
         a.kp, a.vtp, a.scale, a.Tk = kp.ptr, vtp.ptr, scale, tk
         a.eps2 = a.eps3 = eps
         a.xin = xin.ptr if xin is not None else None
         if out is None:
             out = self.empty((m, c), a1.dtype)
-        a.out, a.ldo = out.ptr, c
+        if out_col is None:
+            a.out, a.ldo = out.ptr, c
+        else:
+            a.out, a.ldo = out.ptr + out_col * 2, out.shape[-1]
         if out2 is not None:
             a.out2, a.ldo2 = out2.ptr + out2_col * 2, out2.shape[-1]
         a.M, a.rows_per_img, a.C, a.heads = m, rows_per_img, c, heads
@@ -528,9 +548,9 @@ class Gpu:
         self._ck(self.lib.osg_geglu(self.ctx, _NP2DT[x.dtype], x.ptr, y.ptr, rows, c2 // 2))
         return y
 
-    def transpose(self, x: DevBuf, perm: Sequence[int]):
+    def transpose(self, x: DevBuf, perm: Sequence[int], out: Optional[DevBuf] = None):
         rank = len(x.shape)
-        y = self.empty(tuple(x.shape[p] for p in perm), x.dtype)
+        y = self._out(out, tuple(x.shape[p] for p in perm), x.dtype)
         S = (ctypes.c_long * rank)(*x.shape)
         P = (ctypes.c_int * rank)(*perm)
         self._ck(self.lib.osg_transpose(self.ctx, x.dtype.itemsize, x.ptr, y.ptr, rank, S, P))
@@ -539,41 +559,41 @@ class Gpu:
     def copy_2d(self, src: DevBuf, src_pitch, src_off, dst: DevBuf, dst_pitch, dst_off, outer, inner):
         self._ck(self.lib.osg_copy_2d(self.ctx, src.dtype.itemsize, src.ptr, src_pitch, src_off, dst.ptr, dst_pitch, dst_off, outer, inner))
 
-    def concat2(self, a: DevBuf, b: DevBuf):
+    def concat2(self, a: DevBuf, b: DevBuf, out: Optional[DevBuf] = None):
         """Concat of two dense tensors along the last axis in one launch."""
         outer = int(np.prod(a.shape[:-1]))
-        y = self.empty(a.shape[:-1] + (a.shape[-1] + b.shape[-1],), a.dtype)
+        y = self._out(out, a.shape[:-1] + (a.shape[-1] + b.shape[-1],), a.dtype)
         self._ck(self.lib.osg_concat2(self.ctx, a.dtype.itemsize, a.ptr, a.shape[-1], b.ptr, b.shape[-1], y.ptr, outer))
         return y
 
-    def resize_nearest(self, x: DevBuf, ho: int, wo: int, nhwc: bool):
+    def resize_nearest(self, x: DevBuf, ho: int, wo: int, nhwc: bool, out: Optional[DevBuf] = None):
         if nhwc:
             n, h, w, c = x.shape
-            y = self.empty((n, ho, wo, c), x.dtype)
+            y = self._out(out, (n, ho, wo, c), x.dtype)
         else:
             n, c, h, w = x.shape
-            y = self.empty((n, c, ho, wo), x.dtype)
+            y = self._out(out, (n, c, ho, wo), x.dtype)
         self._ck(self.lib.osg_resize_nearest(self.ctx, x.dtype.itemsize, x.ptr, y.ptr, n, c, h, w, ho, wo, int(nhwc)))
         return y
 
-    def gather_rows(self, x: DevBuf, idx: DevBuf):
+    def gather_rows(self, x: DevBuf, idx: DevBuf, out: Optional[DevBuf] = None):
         n_rows = x.shape[0]
         row = int(np.prod(x.shape[1:]))
-        y = self.empty((idx.size,) + x.shape[1:], x.dtype)
+        y = self._out(out, (idx.size,) + x.shape[1:], x.dtype)
         self._ck(self.lib.osg_gather_rows(self.ctx, x.dtype.itemsize, x.ptr, idx.ptr, y.ptr, idx.size, row, n_rows))
         return y
 
-    def maxpool_nhwc(self, x: DevBuf, k, stride, pads):
+    def maxpool_nhwc(self, x: DevBuf, k, stride, pads, out: Optional[DevBuf] = None):
         n, h, w, c = x.shape
         pt, pl, pb, pr = pads
         ho, wo = (h + pt + pb - k[0]) // stride[0] + 1, (w + pl + pr - k[1]) // stride[1] + 1
-        y = self.empty((n, ho, wo, c), x.dtype)
+        y = self._out(out, (n, ho, wo, c), x.dtype)
         self._ck(self.lib.osg_maxpool_nhwc(self.ctx, _NP2DT[x.dtype], x.ptr, y.ptr, n, h, w, c, k[0], k[1], stride[0], stride[1], pt, pl,
                                            pb, pr))
         return y
 
-    def convert(self, x: DevBuf, dtype, scale: float = 1.0, zero_point: int = 0):
-        y = self.empty(x.shape, dtype)
+    def convert(self, x: DevBuf, dtype, scale: float = 1.0, zero_point: int = 0, out: Optional[DevBuf] = None):
+        y = self._out(out, x.shape, dtype)
         self._ck(self.lib.osg_convert(self.ctx, _NP2DT[x.dtype], _NP2DT[np.dtype(dtype)], x.ptr, y.ptr, x.size, scale, zero_point))
         return y
 
