@@ -207,10 +207,10 @@ int osg_gemm_rowstats(osg_ctx* ctx, const void* A, const void* B_nk, const void*
  *   out[4] the reduce kernel that finished the split: 0 none, 1 splitk_reduce_kernel, 2 / 3 splitk_reduce4_kernel<4 / 8>, 4 / 5 splitk_reduce_stats_kernel<4 / 8> */
 int osg_last_route(const osg_ctx* ctx, int out[5]);
 /* The same kind of record for the attention and normalisation entry points -- osg_attention / osg_attention_strided / osg_sdpa, osg_group_norm_nhwc,
- * osg_group_norm_stats_nhwc, osg_layer_norm, osg_instance_norm, osg_tblock_tail: what the most recent of these calls on ctx launched.  A sibling of osg_last_route and not
+ * osg_group_norm_stats_nhwc, osg_layer_norm, osg_instance_norm, osg_tblock_tail, osg_qu8_*: what the most recent of these calls on ctx launched.  A sibling of osg_last_route and not
  * more family codes of it: the two records are independent (a contraction does not clear this one, nor the reverse) and this one has eight fields.  Host
  * stores at launch time only: no device work, nothing added to a captured graph.
- *   out[0] family: 0 attention, 1 GroupNorm, 2 LayerNorm, 3 InstanceNorm, 4 the transformer-block tail (osg_tblock_tail); -1 none yet.  Fields a family does
+ *   out[0] family: 0 attention, 1 GroupNorm, 2 LayerNorm, 3 InstanceNorm, 4 the transformer-block tail (osg_tblock_tail), 5 / 6 uint8 arithmetic; -1 none yet.  Fields a family does
  *          not list are 0.
  *   attention:    out[1] 1 attn_kernel<DP, DT, QT, BKV>, 2 attn2_kernel<D, QT, NST>;  out[2] DP (attn_kernel) / D (attn2_kernel);  out[3] DT / NST;
  *                 out[4] QT (a workgroup covers 64 QT query rows);  out[5] BKV, the keys per tile (attn2_kernel: 64);  out[6] workgroups launched
@@ -222,7 +222,26 @@ int osg_last_route(const osg_ctx* ctx, int out[5]);
  *   LayerNorm:    out[1] NV of layer_norm_kernel<f16, NV>, 0 = layer_norm_generic_kernel;  out[2] the osg_dtype
  *   InstanceNorm: out[1] threads per block;  out[2] the osg_dtype
  *   block tail:   out[1] rows per row block (32 / 64);  out[2] NS, the register slots of the weight ring (2 / 3);  out[3] row blocks launched;
- *                 out[4] weight-prefetching workgroups launched behind them (0 / 8);  out[5] 1 = proj_out ran (wpo != NULL);  out[6] 1 = a second destination */
+ *                 out[4] weight-prefetching workgroups launched behind them (0 / 8);  out[5] 1 = proj_out ran (wpo != NULL);  out[6] 1 = a second destination
+ * The uint8-arithmetic entry points (osg_qu8_*) record here too, as two more families:
+ *   5 uint8 contraction (osg_qu8_gemm, osg_qu8_conv2d_nhwc, osg_qu8_conv2d_nhwc_t):
+ *                 out[1] 1 q8_gemm_kernel<CONV, VEC, BM, BN> (register-staged), 2 q8_gemm2_kernel<BM, BN, NST, CONV, WGM> (pipelined);  out[2] BM;  out[3] BN;
+ *                 out[4] NST, the ring depth (0 for kernel 1);  out[5] flags: conv | vec << 1 | (WGM == 4) << 2 (kernel 2 always moves 16-byte chunks: vec = 1);
+ *                 out[6] workgroups launched;  out[7] the halo correction of kernel 2: 0 none (kernel 1 fills padding taps with the zero point itself),
+ *                 1 tap sums from the caller, 2 tap sums built into the workspace by this call
+ *   6 uint8 elementwise / normalisation:  out[1] the entry point: 1 osg_qu8_lut, 2 osg_qu8_binary, 3 osg_qu8_affine_act, 4 osg_qu8_instance_norm,
+ *                 5 osg_qu8_instance_norm_nhwc, 6 osg_qu8_norm_affine_act_nhwc, 7 osg_qu8_softmax_last;  out[2] its route;  out[3] workgroups launched (the
+ *                 instance norms: of the histogram launch, which is also the grid of the lookup; norm + affine: of the last pass over the tensor)
+ *                 binary:        route 0 q8_binary_kernel (generic broadcast), 1 same shape, 2 periodic operand, 3 periodic operand on the left (operands
+ *                                swapped) -- 1 to 3 are q8_binary_fast_kernel; | 4 = Mul (else Add)
+ *                 affine:        route = ACT (1 = the Sigmoid table and the last Mul run)
+ *                 instance norm: route 0;  out[4] the 64 KiB pieces per row
+ *                 NHWC norm:     route = sh (cpg == 1 << sh; -1: not a power of two, the kernels divide);  out[4] the 16-byte path as the host can tell it
+ *                                (C % 16 == 0 and aligned pointers): 1 the histogram takes it | 2 the lookup takes it
+ *                 norm + affine: route 0 channel tables (q8_chan_lut_kernel, q8_chan_apply_kernel), 1 per-group tables inside q8_affine_act_kernel<ACT, true>;
+ *                                | 2 = ACT;  out[4] sh as above
+ *                 lut, softmax:  route 0 (softmax: one workgroup per row)
+ *   A call that is refused (an error return) leaves the record as it was. */
 int osg_last_kernel(const osg_ctx* ctx, int out[8]);
 
 /* The hot kernels take what their first memory requests depend on as leading scalar kernel parameters (preloaded into scalar registers at wave start), some of them

@@ -455,7 +455,7 @@ __global__ __launch_bounds__(64) void q8_tap_sums_kernel(const uint8_t* __restri
 }
 
 template <int BM, int BN, int NST, bool CONV, int WGM = 2, int DBG = 0>
-int launch_q8v2(osg_ctx* ctx, Q8Params& p, int batch) {
+int launch_q8v2(osg_ctx* ctx, Q8Params& p, int batch, int halo) {
     constexpr size_t smem = (size_t)NST * (BM + BN) * 128;
     static_assert(smem <= 160 * 1024, "LDS budget");
     auto kern = q8_gemm2_kernel<BM, BN, NST, CONV, WGM, DBG>;
@@ -466,6 +466,7 @@ int launch_q8v2(osg_ctx* ctx, Q8Params& p, int batch) {
     p.mt = (p.M + BM - 1) / BM;
     p.nt = (p.N + BN - 1) / BN;
     hipLaunchKernelGGL(kern, dim3((unsigned)(p.mt * p.nt * batch)), dim3(WGM * 128), smem, ctx->compute, p);
+    osg_set_kernel(ctx, 5, 2, BM, BN, NST, (CONV ? 1 : 0) | 2 | (WGM == 4 ? 4 : 0), p.mt * p.nt * batch, halo);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -495,7 +496,9 @@ static int try_q8v2(osg_ctx* ctx, Q8Params p, int batch, bool conv, bool* taken)
     if (!tile) return 0;
     p.a_bytes = (unsigned)a_bytes;
     p.b_bytes = (unsigned)b_bytes;
+    int halo = 0;               // osg_last_kernel: 0 no halo correction, 1 tap sums from the caller, 2 tap sums built into the workspace by this call
     if (conv && (p.pt || p.pl || (p.Ho - 1) * p.sh - p.pt + p.KH > p.H || (p.Wo - 1) * p.sw - p.pl + p.KW > p.W)) {
+        halo = p.wtap ? 1 : 2;
         if (!p.wtap) {      // no table from the caller: into the workspace, on every call (stream-ordered before the launch that reads it)
             if (osg_ensure_workspace(ctx, (size_t)p.N * taps * sizeof(int))) return 1;
             hipLaunchKernelGGL(q8_tap_sums_kernel, dim3((unsigned)(p.N * taps)), dim3(64), 0, ctx->compute, p.Bt, (int*)ctx->ws, p.Cin);
@@ -509,22 +512,22 @@ static int try_q8v2(osg_ctx* ctx, Q8Params p, int batch, bool conv, bool* taken)
     const int wgm = getenv("OSG_QU8_WGM") ? atoi(getenv("OSG_QU8_WGM")) : 2;            // 4: the 256 x 128 tile on eight waves
     if (tile == 64) {
         const int nst = nst_env ? nst_env : 4;
-        if (conv) return nst == 2 ? launch_q8v2<64, 64, 2, true>(ctx, p, batch) : nst == 3 ? launch_q8v2<64, 64, 3, true>(ctx, p, batch) : launch_q8v2<64, 64, 4, true>(ctx, p, batch);
-        return nst == 2 ? launch_q8v2<64, 64, 2, false>(ctx, p, batch) : nst == 3 ? launch_q8v2<64, 64, 3, false>(ctx, p, batch) : launch_q8v2<64, 64, 4, false>(ctx, p, batch);
+        if (conv) return nst == 2 ? launch_q8v2<64, 64, 2, true>(ctx, p, batch, halo) : nst == 3 ? launch_q8v2<64, 64, 3, true>(ctx, p, batch, halo) : launch_q8v2<64, 64, 4, true>(ctx, p, batch, halo);
+        return nst == 2 ? launch_q8v2<64, 64, 2, false>(ctx, p, batch, halo) : nst == 3 ? launch_q8v2<64, 64, 3, false>(ctx, p, batch, halo) : launch_q8v2<64, 64, 4, false>(ctx, p, batch, halo);
     }
     const int nst = nst_env ? nst_env : 2;
     if (conv) {
-        if (dbg == 1) return nst == 2 ? launch_q8v2<128, 128, 2, true, 2, 1>(ctx, p, batch) : launch_q8v2<128, 128, 3, true, 2, 1>(ctx, p, batch);
-        if (dbg == 2) return nst == 2 ? launch_q8v2<128, 128, 2, true, 2, 2>(ctx, p, batch) : launch_q8v2<128, 128, 3, true, 2, 2>(ctx, p, batch);
-        if (wgm == 4) return nst == 2 ? launch_q8v2<256, 128, 2, true, 4>(ctx, p, batch) : launch_q8v2<256, 128, 3, true, 4>(ctx, p, batch);
-        if (nst == 2) return launch_q8v2<128, 128, 2, true>(ctx, p, batch);
-        if (nst == 4) return launch_q8v2<128, 128, 4, true>(ctx, p, batch);
-        return launch_q8v2<128, 128, 3, true>(ctx, p, batch);
+        if (dbg == 1) return nst == 2 ? launch_q8v2<128, 128, 2, true, 2, 1>(ctx, p, batch, halo) : launch_q8v2<128, 128, 3, true, 2, 1>(ctx, p, batch, halo);
+        if (dbg == 2) return nst == 2 ? launch_q8v2<128, 128, 2, true, 2, 2>(ctx, p, batch, halo) : launch_q8v2<128, 128, 3, true, 2, 2>(ctx, p, batch, halo);
+        if (wgm == 4) return nst == 2 ? launch_q8v2<256, 128, 2, true, 4>(ctx, p, batch, halo) : launch_q8v2<256, 128, 3, true, 4>(ctx, p, batch, halo);
+        if (nst == 2) return launch_q8v2<128, 128, 2, true>(ctx, p, batch, halo);
+        if (nst == 4) return launch_q8v2<128, 128, 4, true>(ctx, p, batch, halo);
+        return launch_q8v2<128, 128, 3, true>(ctx, p, batch, halo);
     }
-    if (wgm == 4) return nst == 2 ? launch_q8v2<256, 128, 2, false, 4>(ctx, p, batch) : launch_q8v2<256, 128, 3, false, 4>(ctx, p, batch);
-    if (nst == 2) return launch_q8v2<128, 128, 2, false>(ctx, p, batch);
-    if (nst == 4) return launch_q8v2<128, 128, 4, false>(ctx, p, batch);
-    return launch_q8v2<128, 128, 3, false>(ctx, p, batch);
+    if (wgm == 4) return nst == 2 ? launch_q8v2<256, 128, 2, false, 4>(ctx, p, batch, halo) : launch_q8v2<256, 128, 3, false, 4>(ctx, p, batch, halo);
+    if (nst == 2) return launch_q8v2<128, 128, 2, false>(ctx, p, batch, halo);
+    if (nst == 4) return launch_q8v2<128, 128, 4, false>(ctx, p, batch, halo);
+    return launch_q8v2<128, 128, 3, false>(ctx, p, batch, halo);
 }
 
 int launch_q8(osg_ctx* ctx, const Q8Params& p, int batch, bool conv) {
@@ -544,6 +547,7 @@ int launch_q8(osg_ctx* ctx, const Q8Params& p, int batch, bool conv) {
         if (grid.y > 65535u) OSG_FAIL(ctx, "osg_qu8: M too large for one launch");
         if (conv) hipLaunchKernelGGL((q8_gemm_kernel<true, true, 128, 128>), grid, dim3(256), 0, ctx->compute, p);
         else hipLaunchKernelGGL((q8_gemm_kernel<false, true, 128, 128>), grid, dim3(256), 0, ctx->compute, p);
+        osg_set_kernel(ctx, 5, 1, 128, 128, 0, (conv ? 1 : 0) | 2, (int)(grid.x * grid.y * grid.z), 0);
         OSG_LAUNCH_CHECK(ctx);
         return 0;
     }
@@ -556,6 +560,7 @@ int launch_q8(osg_ctx* ctx, const Q8Params& p, int batch, bool conv) {
         if (vec) hipLaunchKernelGGL((q8_gemm_kernel<false, true, 64, 64>), grid, dim3(256), 0, ctx->compute, p);
         else hipLaunchKernelGGL((q8_gemm_kernel<false, false, 64, 64>), grid, dim3(256), 0, ctx->compute, p);
     }
+    osg_set_kernel(ctx, 5, 1, 64, 64, 0, (conv ? 1 : 0) | (vec ? 2 : 0), (int)(grid.x * grid.y * grid.z), 0);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -1027,6 +1032,7 @@ int osg_qu8_conv2d_nhwc(osg_ctx* ctx, const void* x, float x_scale, int x_zp, co
 int osg_qu8_lut(osg_ctx* ctx, const void* x, void* y, long n, const void* lut256) {
     if (n <= 0) return 0;
     hipLaunchKernelGGL(q8_lut_kernel, dim3(grid_for(n)), dim3(256), 0, ctx->compute, (const uint8_t*)x, (uint8_t*)y, n, (const uint8_t*)lut256);
+    osg_set_kernel(ctx, 6, 1, 0, (int)grid_for(n));
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -1069,6 +1075,7 @@ int osg_qu8_affine_act(osg_ctx* ctx, const void* x, float x_scale, int x_zp, con
     const dim3 grid(grid_for(n / 16 + 1)), block(256);
     if (sig_lut) hipLaunchKernelGGL((q8_affine_act_kernel<true, false>), grid, block, 0, ctx->compute, (const uint8_t*)x, (const uint8_t*)g, (const uint8_t*)b, (const uint8_t*)sig_lut, (uint8_t*)y, n, C, inner, qm, qa, qs, (const uint8_t*)nullptr, 1, 0);
     else hipLaunchKernelGGL((q8_affine_act_kernel<false, false>), grid, block, 0, ctx->compute, (const uint8_t*)x, (const uint8_t*)g, (const uint8_t*)b, (const uint8_t*)nullptr, (uint8_t*)y, n, C, inner, qm, qa, qs, (const uint8_t*)nullptr, 1, 0);
+    osg_set_kernel(ctx, 6, 3, sig_lut ? 1 : 0, (int)grid.x);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -1105,6 +1112,7 @@ int osg_qu8_norm_affine_act_nhwc(osg_ctx* ctx, const void* x, long HW, int C, in
         long ppw = HW * cblocks / 1024;                          // ~1024 workgroups when the tensor is big enough
         ppw = ppw < 64 ? 64 : ppw > 1024 ? 1024 : ppw;
         hipLaunchKernelGGL(q8_chan_apply_kernel, dim3((unsigned)((HW + ppw - 1) / ppw), (unsigned)cblocks), dim3(256), 0, ctx->compute, (const uint8_t*)x, (uint8_t*)y, (const uint8_t*)chan_lut, HW, C, (int)ppw);
+        osg_set_kernel(ctx, 6, 6, 0 | (sig_lut ? 2 : 0), (int)((HW + ppw - 1) / ppw) * cblocks, sh);
         OSG_LAUNCH_CHECK(ctx);
         return 0;
     }
@@ -1112,6 +1120,7 @@ int osg_qu8_norm_affine_act_nhwc(osg_ctx* ctx, const void* x, long HW, int C, in
     const dim3 grid(grid_for(n / 16 + 1)), block(256);
     if (sig_lut) hipLaunchKernelGGL((q8_affine_act_kernel<true, true>), grid, block, lut_bytes, ctx->compute, (const uint8_t*)x, (const uint8_t*)g, (const uint8_t*)b, (const uint8_t*)sig_lut, (uint8_t*)y, n, C, 1L, qm, qa, qs, (const uint8_t*)lut, cpg, G);
     else hipLaunchKernelGGL((q8_affine_act_kernel<false, true>), grid, block, lut_bytes, ctx->compute, (const uint8_t*)x, (const uint8_t*)g, (const uint8_t*)b, (const uint8_t*)nullptr, (uint8_t*)y, n, C, 1L, qm, qa, qs, (const uint8_t*)lut, cpg, G);
+    osg_set_kernel(ctx, 6, 6, 1 | (sig_lut ? 2 : 0), (int)grid.x, sh);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -1156,6 +1165,7 @@ int osg_qu8_binary(osg_ctx* ctx, osg_binary_kind kind, const void* a, const long
     else if (al && an == n && periodic(b_shape, bn)) mode = 1;
     else if (al && bn == n && periodic(a_shape, an)) mode = 2;
     const uint8_t *pa = (const uint8_t*)a, *pb = (const uint8_t*)b;
+    const bool swapped = mode == 2;
     if (mode == 2) {           // Add and Mul commute: swap the operands together with their parameters
         std::swap(pa, pb);
         std::swap(a_scale, b_scale);
@@ -1185,6 +1195,8 @@ int osg_qu8_binary(osg_ctx* ctx, osg_binary_kind kind, const void* a, const long
         else if (mode == 1) hipLaunchKernelGGL((q8_binary_fast_kernel<0, 1>), dim3(grid_for(n / 16 + 1)), dim3(256), 0, ctx->compute, pa, pb, (uint8_t*)y, n, inner, period, q);
         else hipLaunchKernelGGL(q8_binary_kernel<0>, dim3(grid_for(n)), dim3(256), 0, ctx->compute, (const uint8_t*)a, (const uint8_t*)b, (uint8_t*)y, n, p, q);
     }
+    // route: 0 generic, 1 same shape, 2 periodic operand, 3 periodic operand on the left (operands swapped); | 4 = Mul
+    osg_set_kernel(ctx, 6, 2, (mode < 0 ? 0 : mode == 0 ? 1 : swapped ? 3 : 2) | (kind == OSG_BIN_MUL ? 4 : 0), (int)(mode < 0 ? grid_for(n) : grid_for(n / 16 + 1)));
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -1202,6 +1214,7 @@ int osg_qu8_instance_norm(osg_ctx* ctx, const void* x, void* y, int rows, long L
     hipLaunchKernelGGL(q8_in_hist_kernel, dim3(pieces, (unsigned)rows), dim3(256), 0, ctx->compute, (const uint8_t*)x, hist, L);
     hipLaunchKernelGGL(q8_in_lut_kernel, dim3((unsigned)rows), dim3(256), 0, ctx->compute, hist, lut, L, n_scale, scale, bias, eps, in_scale, in_zp, out_scale, out_zp);
     hipLaunchKernelGGL(q8_in_apply_kernel, dim3(pieces, (unsigned)rows), dim3(256), 0, ctx->compute, (const uint8_t*)x, (uint8_t*)y, lut, L);
+    osg_set_kernel(ctx, 6, 4, 0, (int)pieces * rows, (int)pieces);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -1224,6 +1237,7 @@ int osg_qu8_instance_norm_nhwc(osg_ctx* ctx, const void* x, void* y, long HW, in
     hipLaunchKernelGGL(q8_in_hist_nhwc_kernel, dim3(pieces), dim3(256), hist_bytes, ctx->compute, (const uint8_t*)x, hist, n, C, C / G, G, sh);
     hipLaunchKernelGGL(q8_in_lut_kernel, dim3((unsigned)G), dim3(256), 0, ctx->compute, hist, lut, L, n_scale, scale, bias, eps, in_scale, in_zp, out_scale, out_zp);
     hipLaunchKernelGGL(q8_in_apply_nhwc_kernel, dim3(pieces), dim3(256), lut_bytes, ctx->compute, (const uint8_t*)x, (uint8_t*)y, lut, n, C, C / G, G, sh);
+    osg_set_kernel(ctx, 6, 5, sh, (int)pieces, ((C & 15) == 0 && ((uintptr_t)x & 15) == 0 ? 1 : 0) | ((C & 15) == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0 ? 2 : 0));
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -1232,6 +1246,7 @@ int osg_qu8_softmax_last(osg_ctx* ctx, const void* x, void* y, long rows, long C
     if (rows <= 0 || C <= 0) return 0;
     if (rows > 2147483647L) OSG_FAIL(ctx, "osg_qu8_softmax_last: too many rows");
     hipLaunchKernelGGL(q8_softmax_kernel, dim3((unsigned)rows), dim3(256), 0, ctx->compute, (const uint8_t*)x, (uint8_t*)y, C, (const unsigned*)lut_u32_256);
+    osg_set_kernel(ctx, 6, 7, 0, (int)rows);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }

@@ -237,7 +237,7 @@ class Gpu:
         return tuple(r)
 
     def last_kernel(self):
-        """osg_last_kernel: what the most recent attention / GroupNorm / LayerNorm / InstanceNorm / transformer-block tail call launched (eight fields, include/osgpu.h)"""
+        """osg_last_kernel: what the most recent attention / GroupNorm / LayerNorm / InstanceNorm / transformer-block tail / uint8-arithmetic call launched (eight fields, include/osgpu.h)"""
         r = (ctypes.c_int * 8)()
         self._ck(self.lib.osg_last_kernel(self.ctx, r))
         return tuple(r)
@@ -626,20 +626,29 @@ class Gpu:
         self._ck(self.lib.osg_decode_blend(self.ctx, tiles.ptr, self._p(img), self._p(pix), images, H, W, tile, up))
         return img, pix
 
-    # ---- uint8 arithmetic (a uint8 tensor = codes DevBuf + (scale, zero_point)) ----
-    def qu8_conv_tap_sums(self, w: DevBuf) -> DevBuf:
+    # ---- uint8 arithmetic (a uint8 tensor = codes DevBuf + (scale, zero_point)); out=: the caller's output buffer, as for the other ops ----
+    def _table(self, t, dtype):
+        """a 256-entry table: a DevBuf is used where it lies (owned by the caller), a host array is uploaded (owned here) -> (DevBuf, owned)"""
+        if isinstance(t, DevBuf):
+            if t.size != 256 or t.dtype != np.dtype(dtype):
+                raise OsgError(f"a device table of 256 {np.dtype(dtype)} is wanted, not {t.shape} {t.dtype}")
+            return t, False
+        return self.to_dev(np.ascontiguousarray(t, dtype)), True
+
+    def qu8_conv_tap_sums(self, w: DevBuf, out: Optional[DevBuf] = None) -> DevBuf:
         cout, kh, kw, cin = w.shape
-        t = self.empty((cout, kh * kw), np.int32)
+        t = self._out(out, (cout, kh * kw), np.int32)
         self._ck(self.lib.osg_qu8_conv_tap_sums(self.ctx, w.ptr, cout, kh, kw, cin, t.ptr))
         return t
 
-    def qu8_conv2d_nhwc(self, x: DevBuf, xq, w: DevBuf, wq, bias: Optional[DevBuf], oq, stride=1, pads=(1, 1, 1, 1), tap_sums: Optional[DevBuf] = None):
+    def qu8_conv2d_nhwc(self, x: DevBuf, xq, w: DevBuf, wq, bias: Optional[DevBuf], oq, stride=1, pads=(1, 1, 1, 1), tap_sums: Optional[DevBuf] = None,
+                        out: Optional[DevBuf] = None):
         n, h, wd, cin = x.shape
         cout, kh, kw, _ = w.shape
         sh, sw = (stride, stride) if isinstance(stride, int) else stride
         pt, pl, pb, pr = pads
         ho, wo = (h + pt + pb - kh) // sh + 1, (wd + pl + pr - kw) // sw + 1
-        y = self.empty((n, ho, wo, cout), np.uint8)
+        y = self._out(out, (n, ho, wo, cout), np.uint8)
         if tap_sums is not None:
             self._ck(self.lib.osg_qu8_conv2d_nhwc_t(self.ctx, x.ptr, float(xq[0]), int(xq[1]), w.ptr, float(wq[0]), int(wq[1]), self._p(bias), float(oq[0]), int(oq[1]),
                                                     y.ptr, n, h, wd, cin, cout, kh, kw, sh, sw, pt, pl, pb, pr, tap_sums.ptr))
@@ -648,67 +657,88 @@ class Gpu:
                                               y.ptr, n, h, wd, cin, cout, kh, kw, sh, sw, pt, pl, pb, pr))
         return y
 
-    def qu8_gemm(self, a: DevBuf, aq, b_nk: DevBuf, bq, bias: Optional[DevBuf], oq):
-        """a:[(batch,)M,K], b_nk:[(batch,)N,K] codes."""
+    def qu8_gemm(self, a: DevBuf, aq, b_nk: DevBuf, bq, bias: Optional[DevBuf], oq, out: Optional[DevBuf] = None, lda: Optional[int] = None,
+                 stride_a: Optional[int] = None, stride_b: Optional[int] = None, stride_c: Optional[int] = None):
+        """a:[(batch,)M,K], b_nk:[(batch,)N,K] codes.  lda: the row pitch of a (default K: dense) -- with lda > K or a batch stride beyond the dense one, `a`
+        is the [(batch,)M,K] SHAPE of the operand and its buffer holds the pitched layout; stride_*: the batch strides in codes (defaults: dense, and 0 for a
+        2-D b_nk).  With a stride_c of its own, out= is required and holds the strided layout (it is not checked against the dense shape)."""
         batch = a.shape[0] if len(a.shape) == 3 else 1
         m, k = a.shape[-2:]
         n = b_nk.shape[-2]
-        c = self.empty(a.shape[:-1] + (n,), np.uint8)
-        self._ck(self.lib.osg_qu8_gemm(self.ctx, a.ptr, k, float(aq[0]), int(aq[1]), b_nk.ptr, float(bq[0]), int(bq[1]), self._p(bias), float(oq[0]), int(oq[1]),
-                                       c.ptr, m, n, k, batch, m * k if batch > 1 else 0, n * k if len(b_nk.shape) == 3 else 0, m * n if batch > 1 else 0))
+        lda = k if lda is None else int(lda)
+        sa = (m * lda if batch > 1 else 0) if stride_a is None else int(stride_a)
+        sb = (n * k if len(b_nk.shape) == 3 else 0) if stride_b is None else int(stride_b)
+        if stride_c is None:
+            sc = m * n if batch > 1 else 0
+            c = self._out(out, a.shape[:-1] + (n,), np.uint8)
+        else:
+            sc = int(stride_c)
+            if out is None or out.dtype != np.dtype(np.uint8) or out.size < (batch - 1) * sc + m * n:
+                raise OsgError("qu8_gemm: a stride_c of its own needs an out= of at least (batch - 1) * stride_c + M * N codes")
+            c = out
+        self._ck(self.lib.osg_qu8_gemm(self.ctx, a.ptr, lda, float(aq[0]), int(aq[1]), b_nk.ptr, float(bq[0]), int(bq[1]), self._p(bias), float(oq[0]), int(oq[1]),
+                                       c.ptr, m, n, k, batch, sa, sb, sc))
         return c
 
-    def qu8_lut(self, x: DevBuf, lut: np.ndarray):
-        y = self.empty(x.shape, np.uint8)
-        t = self.to_dev(np.ascontiguousarray(lut, np.uint8))
+    def qu8_lut(self, x: DevBuf, lut, out: Optional[DevBuf] = None):
+        """lut: 256 uint8 codes, a host array (uploaded for the call) or a DevBuf"""
+        y = self._out(out, x.shape, np.uint8)
+        t, owned = self._table(lut, np.uint8)
         self._ck(self.lib.osg_qu8_lut(self.ctx, x.ptr, y.ptr, x.size, t.ptr))
-        self.sync()
+        if owned:
+            self.sync()
+            t.free()
         return y
 
-    def qu8_binary(self, kind: str, a: DevBuf, aq, b: DevBuf, bq, oq):
+    def qu8_binary(self, kind: str, a: DevBuf, aq, b: DevBuf, bq, oq, out: Optional[DevBuf] = None):
         rank = max(len(a.shape), len(b.shape))
         ash = (1,) * (rank - len(a.shape)) + a.shape
         bsh = (1,) * (rank - len(b.shape)) + b.shape
-        y = self.empty(tuple(np.broadcast_shapes(ash, bsh)), np.uint8)
+        y = self._out(out, tuple(np.broadcast_shapes(ash, bsh)), np.uint8)
         A = (ctypes.c_long * rank)(*ash)
         B = (ctypes.c_long * rank)(*bsh)
         self._ck(self.lib.osg_qu8_binary(self.ctx, BIN[kind], a.ptr, A, float(aq[0]), int(aq[1]), b.ptr, B, float(bq[0]), int(bq[1]), y.ptr, float(oq[0]), int(oq[1]), rank))
         return y
 
-    def qu8_instance_norm(self, x: DevBuf, xq, scale: DevBuf, bias: DevBuf, eps: float, oq):
+    def qu8_instance_norm(self, x: DevBuf, xq, scale: DevBuf, bias: DevBuf, eps: float, oq, out: Optional[DevBuf] = None):
         rows, L = int(np.prod(x.shape[:-1])), x.shape[-1]
-        y = self.empty(x.shape, np.uint8)
+        y = self._out(out, x.shape, np.uint8)
         self._ck(self.lib.osg_qu8_instance_norm(self.ctx, x.ptr, y.ptr, rows, L, scale.size, scale.ptr, bias.ptr, eps, float(xq[0]), int(xq[1]), float(oq[0]), int(oq[1])))
         return y
 
-    def qu8_affine_act(self, x: DevBuf, xq, g: DevBuf, gq, mq, b: DevBuf, bq, aq, sig_lut: Optional[DevBuf], sq, oq, channels: int, inner: int = 1):
+    def qu8_affine_act(self, x: DevBuf, xq, g: DevBuf, gq, mq, b: DevBuf, bq, aq, sig_lut: Optional[DevBuf], sq, oq, channels: int, inner: int = 1,
+                       out: Optional[DevBuf] = None):
         """Mul(x, g[C]) -> Add(., b[C]) [-> Sigmoid -> Mul] in one pass; *q = (scale, zero point) of x, g, Mul out, b, Add out, Sigmoid out, final Mul out"""
-        y = self.empty(x.shape, np.uint8)
+        y = self._out(out, x.shape, np.uint8)
         self._ck(self.lib.osg_qu8_affine_act(self.ctx, x.ptr, float(xq[0]), int(xq[1]), g.ptr, float(gq[0]), int(gq[1]), float(mq[0]), int(mq[1]), b.ptr, float(bq[0]),
                                              int(bq[1]), float(aq[0]), int(aq[1]), self._p(sig_lut), float(sq[0]), int(sq[1]), float(oq[0]), int(oq[1]), y.ptr, x.size,
                                              channels, inner))
         return y
 
-    def qu8_instance_norm_nhwc(self, x: DevBuf, groups: int, xq, scale: DevBuf, bias: DevBuf, eps: float, oq):
+    def qu8_instance_norm_nhwc(self, x: DevBuf, groups: int, xq, scale: DevBuf, bias: DevBuf, eps: float, oq, out: Optional[DevBuf] = None):
         """x: [HW, C] codes (NHWC); rows of the normalisation = `groups` blocks of C/groups channels over every pixel"""
         hw, c = int(np.prod(x.shape[:-1])), x.shape[-1]
-        y = self.empty(x.shape, np.uint8)
+        y = self._out(out, x.shape, np.uint8)
         self._ck(self.lib.osg_qu8_instance_norm_nhwc(self.ctx, x.ptr, y.ptr, hw, c, groups, scale.size, scale.ptr, bias.ptr, eps, float(xq[0]), int(xq[1]), float(oq[0]), int(oq[1])))
         return y
 
-    def qu8_norm_affine_act_nhwc(self, x: DevBuf, groups: int, xq, scale: DevBuf, bias: DevBuf, eps: float, nq, g: DevBuf, gq, mq, b: DevBuf, bq, aq, sig_lut: Optional[DevBuf], sq, oq):
+    def qu8_norm_affine_act_nhwc(self, x: DevBuf, groups: int, xq, scale: DevBuf, bias: DevBuf, eps: float, nq, g: DevBuf, gq, mq, b: DevBuf, bq, aq, sig_lut: Optional[DevBuf], sq, oq,
+                                 out: Optional[DevBuf] = None):
         """qu8_instance_norm_nhwc followed by qu8_affine_act, the normalisation's per-group table applied inside the affine pass"""
         hw, c = int(np.prod(x.shape[:-1])), x.shape[-1]
-        y = self.empty(x.shape, np.uint8)
+        y = self._out(out, x.shape, np.uint8)
         self._ck(self.lib.osg_qu8_norm_affine_act_nhwc(self.ctx, x.ptr, hw, c, groups, scale.size, scale.ptr, bias.ptr, eps, float(xq[0]), int(xq[1]), float(nq[0]), int(nq[1]),
                                                        g.ptr, float(gq[0]), int(gq[1]), float(mq[0]), int(mq[1]), b.ptr, float(bq[0]), int(bq[1]), float(aq[0]), int(aq[1]),
                                                        self._p(sig_lut), float(sq[0]), int(sq[1]), float(oq[0]), int(oq[1]), y.ptr))
         return y
 
-    def qu8_softmax_last(self, x: DevBuf, lut_u32: np.ndarray):
+    def qu8_softmax_last(self, x: DevBuf, lut_u32, out: Optional[DevBuf] = None):
+        """lut_u32: the 256 uint32 entries of XNNPACK's exp table, a host array (uploaded for the call) or a DevBuf"""
         rows, c = int(np.prod(x.shape[:-1])), x.shape[-1]
-        y = self.empty(x.shape, np.uint8)
-        t = self.to_dev(np.ascontiguousarray(lut_u32, np.uint32))
+        y = self._out(out, x.shape, np.uint8)
+        t, owned = self._table(lut_u32, np.uint32)
         self._ck(self.lib.osg_qu8_softmax_last(self.ctx, x.ptr, y.ptr, rows, c, t.ptr))
-        self.sync()
+        if owned:
+            self.sync()
+            t.free()
         return y

@@ -104,14 +104,23 @@ def matmul_u8(a, s_a, z_a, b, s_b, z_b, s_out, z_out):
 def softmax_u8(q, s_in, axis=-1):
     """Softmax, uint8 branch -> XnnPack::softmax<uint8_t> -> XNNPACK qu8 softmax (onnxstream.cpp:1958-2060): output scale 1/256, zero point 0;
     lookup table t[i] = lrint(min(UINT32_MAX / channels, 2^23 - 1) * exp((i - 255) * s_in)); per row y = min(255, ((t[x + 255 - max] << 8)
-    + (sum >> 1)) / sum).  (In the oracle the table operator itself is the shim's restatement of the same algorithm.)"""
+    + (sum >> 1)) / sum).  (In the oracle the table operator itself is the shim's restatement of the same algorithm.)
+
+    The row sum is a uint32_t, i.e. taken modulo 2^32: the table scale UINT32_MAX / channels is rounded to nearest, so `channels` entries at the row
+    maximum can add up to just over 2^32 (a constant row of 600 codes: 600 * 7158279 = 4 294 967 400 -> 104; of 513 codes -> 32) and the sum wraps.
+    XNNPACK's own source is not at hand offline to confirm this; oracle/xnn_shim.cpp, qu8::softmax_row (csrc/host/qu8.h) and q8_softmax_kernel all
+    accumulate in uint32_t, and this specification follows the three of them.  A row whose wrapped sum is 0 (a constant row at 1024 or 4096 channels)
+    is a division by zero in every one of them: it is refused here with a ValueError that names the row."""
     x = np.moveaxis(np.asarray(q), axis, -1)
     c = x.shape[-1]
     qscale = min(float(np.iinfo(np.uint32).max) / c, 8388607.0)
     t = np.rint(qscale * np.exp((np.arange(256, dtype=np.float64) - 255.0) * float(f32(s_in)))).astype(np.uint64)
     m = x.max(-1, keepdims=True).astype(np.int64)
     tv = t[(x.astype(np.int64) + 255 - m)]
-    s = tv.sum(-1, keepdims=True)
+    s = tv.sum(-1, keepdims=True) & np.uint64(0xFFFFFFFF)            # uint32_t accumulator
+    if (s == 0).any():
+        row = tuple(int(i) for i in np.argwhere(s[..., 0] == 0)[0])
+        raise ValueError(f"softmax_u8: the 32-bit sum of the table entries of row {row} ({c} channels) is 0: the reference divides by zero there")
     y = np.minimum(((tv << np.uint64(8)) + (s >> np.uint64(1))) // s, 255).astype(np.uint8)
     return np.moveaxis(y, -1, axis), f32(1.0 / 256.0), 0
 

@@ -86,6 +86,21 @@ def test_softmax_and_instance_norm_tables(hooks):
         hooks.h_softmax(_p(x, u8p), ctypes.c_float(s_in), ctypes.c_size_t(rows), ctypes.c_size_t(ch), _p(y, u8p))
         want, so, zo = Q.softmax_u8(x, s_in)
         assert np.array_equal(y, want) and so == np.float32(1 / 256) and zo == 0
+    # constant rows: every entry sits at the row maximum, the sum is ch * t[255].  At 513 and 600 channels it passes 2^32 and wraps (to 32 and 104) in the
+    # uint32_t accumulator of qu8::softmax_row, so every column saturates at 255; 512 channels of code 255 stay below 2^32 (2^32 - 512 -> code 1 per column)
+    for ch, code, wrapped, out in [(513, 7, 32, 255), (600, 200, 104, 255), (512, 255, (1 << 32) - 512, 1)]:
+        x = np.full((2, ch), code, np.uint8)
+        x[1] = rng.integers(0, 256, ch, dtype=np.uint8)              # (an ordinary row beside it)
+        s_in = np.float32(0.0625)
+        t255 = int(np.rint(min(float(np.iinfo(np.uint32).max) / ch, 8388607.0)))
+        assert (ch * t255) % (1 << 32) == wrapped
+        y = np.empty_like(x)
+        hooks.h_softmax(_p(x, u8p), ctypes.c_float(s_in), ctypes.c_size_t(2), ctypes.c_size_t(ch), _p(y, u8p))
+        want, _, _ = Q.softmax_u8(x, s_in)
+        assert (want[0] == out).all()
+        assert np.array_equal(y, want), (ch, int((y != want).sum()), y[0, :4], want[0, :4])
+    with pytest.raises(ValueError, match="row \\(1,\\)"):          # 1024 * 4194304 = 2^32: the wrapped sum is 0, which the specification refuses
+        Q.softmax_u8(np.stack([np.arange(1024) % 256, np.full(1024, 9)]).astype(np.uint8), np.float32(0.0625))
     for C, L in [(8, 1024), (4, 4096), (3, 77)]:
         x = np.clip(rng.normal(128, 30, (1, C, L)), 0, 255).astype(np.uint8)
         (si, zi), (so, zo) = _qp(rng), _qp(rng)
