@@ -119,7 +119,10 @@ class Model:
         r = ctypes.cast(p, ctypes.POINTER(_GetTensorReturnLayout)).contents
         dims = ctypes.cast(r.dims, ctypes.POINTER(ctypes.c_size_t))
         shape = [dims[i] for i in range(r.dims_num)]
-        arr = numpy.ctypeslib.as_array(ctypes.cast(r.data, ctypes.POINTER(ctypes.c_float)), shape=(r.data_num,)).copy()
+        if r.data_num:
+            arr = numpy.ctypeslib.as_array(ctypes.cast(r.data, ctypes.POINTER(ctypes.c_float)), shape=(r.data_num,)).copy()
+        else:      # (a tensor without elements has no data to point to)
+            arr = numpy.zeros(0, numpy.float32)
         self._lib.model_free_buffer(p)
         return arr.reshape(shape), shape
 

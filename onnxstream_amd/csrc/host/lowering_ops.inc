@@ -581,9 +581,14 @@
             long da = i + as.size() >= rank ? as[i + as.size() - rank] : 1;
             long db = i + bs.size() >= rank ? bs[i + bs.size() - rank] : 1;
             need(op, da == db || da == 1 || db == 1, "shapes are not broadcastable.");
-            os[i] = std::max(da, db);
+            os[i] = da == 0 || db == 0 ? 0 : std::max(da, db);   // (NumPy: an extent of 0 against 1 is 0 -- an operand without elements has nothing to stretch)
         }
         const bool batched = V(a).batched || V(b).batched;
+        if (prod(os) == 0) {   // an empty operand (the zero-length caches of the LLM flow's first call; its declared 0 is a wildcard for check_out): an empty result, no launch
+            const osg_dtype edt = cur_up ? OSG_F32 : OSG_F16;
+            V(out_val(op, os, Lay::plain, batched, edt)).up32 = edt == OSG_F32;
+            return;
+        }
         // ---- NHWC-aware fast paths: keep the conv layout when the other operand is per-channel / same-layout ----
         auto per_channel = [&](int v, long C) {  // logical [C,1,1] / [1,C,1,1] / scalar
             const Shape& s = V(v).shape;
@@ -1511,7 +1516,8 @@
         }
     }
 
-    // Slice (reference :6499-6695): last or last-but-one axis, step 1, one or two axes
+    // Slice (reference :6499-6695): last or last-but-one axis, step 1, one or two axes.  Without an `axes` input EVERY (start, end) pair applies to the last axis,
+    // the second pair to the result of the first (the reference's last_but_one is only ever set from `axes`, :6529-6554)
     void lower_slice(const Operation& op) {
         need(op, op.m_input.size() >= 3 && op.m_input.size() <= 5, "wrong number of inputs.");
         need(op, op.m_attributes.empty(), "unrecognized attribute (not implemented).");
@@ -1529,7 +1535,6 @@
             const int rank = (int)s.size();
             int axis = rank - 1;
             if (ax) { need(op, ax->host_i.size() == na, "unsupported shape of axes (not implemented)."); axis = (int)ax->host_i[k]; if (axis < 0) axis += rank; }
-            else if (na == 2) axis = rank - 2 + (int)k;
             need(op, axis == rank - 1 || axis == rank - 2, "unsupported axes value(s): slice supported on last or last but one axis only (not implemented).");
             if (sp) need(op, sp->host_i.size() == na && sp->host_i[k] == 1, "unsupported steps value(s) (not implemented).");
             long dim = s[axis], b = st->host_i[k], e = en->host_i[k];
@@ -1602,9 +1607,12 @@
         const long Ho = (s[2] + pads[0] + pads[2] - ks[0]) / strides[0] + 1, Wo = (s[3] + pads[1] + pads[3] - ks[1]) / strides[1] + 1;
         int y = out_val(op, {s[0], s[1], Ho, Wo}, Lay::nhwc, V(x).batched);
         const long nb = B(x);
+        // pads re-centred as the reference does (:1553-1558, like Conv): the total per direction, the odd cell at the bottom / on the right
+        const int ph = pads[0] + pads[2], pw = pads[1] + pads[3];
+        const int pt = ph / 2, pb = ph - pt, pl = pw / 2, pr = pw - pl;
         P.add_step("MaxPool " + op.m_name, {x}, {y}, [=, this] {
             be.check(be.api.osg_maxpool_nhwc(be.ctx, OSG_F16, P.ptr(x), P.ptr(y), (int)nb, (int)s[2], (int)s[3], (int)s[1], ks[0], ks[1], strides[0], strides[1],
-                                             pads[0], pads[1], pads[2], pads[3]),
+                                             pt, pl, pb, pr),
                      "MaxPool");
         });
     }
