@@ -574,7 +574,9 @@
             int dv = prod_of(ops()[i].m_input[0]);
             if (!is(dv, "Div") || use_count(ops()[i].m_input[0].m_name) != 1) continue;
             float c = 0;
-            if (!const_scalar(ops()[dv].m_input[1], &c) || std::fabs(c - 1.41421356f) > 2e-3f) continue;
+            // fp16 arithmetic: the divisor is an f16 by the time the Div sees it.  The two exporter forms (the f32 sqrt(2) and its f16 rounding 1.4140625) are
+            // the constants that round to the f16 of sqrt(2); anything else (1.413, 1.416) is another function and stays op by op
+            if (!const_scalar(ops()[dv].m_input[1], &c) || float_to_half(c) != float_to_half(1.41421356f)) continue;
             const Tensor gate = ops()[dv].m_input[0];
             int gs = prod_of(gate);
             if (!is(gs, "Slice") || use_count(gate.m_name) != 2) continue;
@@ -861,6 +863,12 @@
                     // merge: Reshape[1,h,T,d] -> Transpose(0,2,1,3) -> Reshape[1,T,h*d]
                     int o0 = sole_consumer(ops()[mm1].m_output[0]);
                     if (!is(o0, "Reshape")) goto plain;
+                    {
+                        // the first merge Reshape must give [1,h,T,d]: [h,1,T,d] -> Transpose(0,2,1,3) -> [1,T,h*d] keeps the heads one after the other
+                        // ([h,T,d] order), which is not the per-token interleave that osg.Attention writes
+                        const auto& ms = ops()[o0].m_output[0].m_shape;
+                        if (ms.size() != 4 || ms[0] != 1 || (long)ms[1] != h || (long)ms[2] != (long)q.m_shape[1] || (long)ms[3] != d) goto plain;
+                    }
                     int o1 = sole_consumer(ops()[o0].m_output[0]);
                     auto* pm2 = o1 >= 0 ? attr(ops()[o1], "perm") : nullptr;
                     if (!is(o1, "Transpose") || !pm2 || int_list(*pm2) != std::vector<int>{0, 2, 1, 3}) goto plain;
@@ -1027,6 +1035,7 @@
             Operation& op = ops()[i];
             if (op.m_input.size() != 1 || op.m_output.size() != 1 || !act(op.m_input[0])) continue;
             if (use_count(op.m_output[0].m_name) >= 1000) continue;  // an extra output the caller reads
+            if (use_count(op.m_output[0].m_name) == 0) continue;     // nobody consumes it: a graph output, read by name through get_tensor
             auto it = first.find(op.m_input[0].m_name);
             if (it == first.end()) first[op.m_input[0].m_name] = op.m_output[0].m_name;
             else {
@@ -1050,6 +1059,7 @@
             if (!is((int)i, "Conv")) continue;
             Operation& op = ops()[i];
             if (op.m_output.size() != 1 || attr(op, "osg_residual")) continue;
+            if (attr(op, "osg_act")) continue;   // the epilogue applies the activation LAST: silu(conv) + g is not silu(conv + g)
             int ad = sole_consumer(op.m_output[0]);
             if (!is(ad, "Add")) continue;
             int ti = other(ops()[ad], op.m_output[0].m_name);
@@ -1100,6 +1110,7 @@
             if (!conv && !lin) continue;
             Operation& op = ops()[i];
             if (op.m_output.size() != 1) continue;
+            if (attr(op, "osg_residual")) continue;   // the op this pass has just written in place of an Add: the epilogue takes ONE residual, a second Add stays an Add
             int ad = sole_consumer(op.m_output[0]);
             if (!is(ad, "Add")) continue;
             int ri = other(ops()[ad], op.m_output[0].m_name);

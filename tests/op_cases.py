@@ -11,6 +11,7 @@ One case = one operator in one attribute form / layout / broadcast form:
                "elementwise" within one f16 ulp of the float64 value rounded to f16 (osg_elementwise.hip: f32 arithmetic, one rounding)
                "reduce"      the bound of the kernel-level test of the same kernel, named in `bound` (BOUNDS below cites where each comes from)
                "reject"      refused at plan time with a message that contains `reject`
+               "chain"       several launches, no per-operator class (the graphs of tests/fusion_cases.py, which name a class per level where one launch remains)
   upcast       substrings for Model.set_upcast_substrings
   stub_values  the stub backend carries this case's values (every launch of it is data movement)
   const_out    outputs that depend on constants only: they have one sample however many were pushed
@@ -42,7 +43,7 @@ class Case:
         self.name, self.cls, self.build, self.inputs, self.ref, self.outs = name, cls, build, inputs, ref, tuple(outs)
         self.reject, self.upcast, self.bound, self.const_out, self.extra, self.dynamic = reject, upcast, bound, tuple(const_out), extra or {}, dynamic
         self.stub_values = (cls == "move") if stub_values is None else stub_values
-        assert cls in ("move", "elementwise", "reduce", "reject") and (cls != "reduce" or bound in BOUNDS) and (cls != "reject" or reject), name
+        assert cls in ("move", "elementwise", "reduce", "reject", "chain") and (cls != "reduce" or bound in BOUNDS) and (cls != "reject" or reject), name
 
     def sample(self, k):
         """fp32 inputs of pushed sample k (0..2)"""
@@ -776,9 +777,15 @@ def emit(case, sink):
     g.finish()
 
 
-def run_case(case, pushes=1, fusion=2, first=0):
+def plan_steps(info):
+    """the `what` of every step of Model.hip_plan_info()"""
+    return [line.split(" | ", 1)[1] for line in info.splitlines() if line.startswith("step ")]
+
+
+def run_case(case, pushes=1, fusion=2, first=0, options=None, extra_outputs=(), plan=False):
     """pushes samples first .. first + pushes - 1 -> output name -> list of fp32 arrays, one per pushed sample (one only for an output that depends on constants alone); raises
-    onnxstream_amd.bindings.OnnxStreamError with the refusal's message"""
+    onnxstream_amd.bindings.OnnxStreamError with the refusal's message.  options: Model options set before the graph is read (hip_fusion_level among them overrides `fusion`);
+    extra_outputs: names for add_extra_output; plan: return (outputs, the `what` of every plan step) instead"""
     import tempfile
 
     from onnxstream_amd import build as b
@@ -790,6 +797,10 @@ def run_case(case, pushes=1, fusion=2, first=0):
         m = Model(b.LIB_HOST, 0, "ram+nocache")
         try:
             m._set_option("hip_fusion_level", fusion)
+            for name, value in (options or {}).items():
+                m._set_option(name, value)
+            for name in extra_outputs:
+                m.add_extra_output(name)
             if case.dynamic:
                 m.set_support_dynamic_shapes(True)
             if case.upcast:
@@ -804,9 +815,10 @@ def run_case(case, pushes=1, fusion=2, first=0):
             for o in case.outs:
                 res = [m.get_tensor(o, i) for i in range(pushes)]
                 got[o] = [r[0] for r in res if r is not None]
+            steps = plan_steps(m.hip_plan_info()) if plan else None
         finally:
             m.close()
-    return got
+    return (got, steps) if plan else got
 
 
 def bits(x):
