@@ -43,16 +43,22 @@ KNOBS = ("OSG_GEMM_CFG", "OSG_GEMM_NST", "OSG_GEMM_SPLITS", "OSG_GEMM_KS", "OSG_
 
 # ---- the table -----------------------------------------------------------------------------------------------------------------------------------------
 @lru_cache(maxsize=None)
-def table():
-    """(kV2Entries, kV3Entries, {v2 entry: (cfg, nst, ks, spec) of a request of the entry's own form that resolves to it})"""
+def driver():
+    """{mode: what tests/cpp/contraction_routes.cpp prints in it} for the modes entries and resolve"""
     d = tempfile.mkdtemp(prefix="osg_routes_")
     try:
         exe = os.path.join(d, "routes")
         subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(REPO, "onnxstream_amd", "csrc"), os.path.join(REPO, "tests", "cpp", "contraction_routes.cpp"),
                         "-o", exe], check=True)
-        out = {m: subprocess.run([exe, m], stdout=subprocess.PIPE, text=True, check=True).stdout for m in ("entries", "resolve")}
+        return {m: subprocess.run([exe, m], stdout=subprocess.PIPE, text=True, check=True).stdout for m in ("entries", "resolve")}
     finally:
         shutil.rmtree(d, ignore_errors=True)
+
+
+@lru_cache(maxsize=None)
+def table():
+    """(kV2Entries, kV3Entries, {v2 entry: (cfg, nst, ks, spec) of a request of the entry's own form that resolves to it})"""
+    out = driver()
     v2, v3 = [], []
     for line in out["entries"].splitlines():
         f = line.split()
@@ -143,7 +149,7 @@ class Out:
         untouched = np.concatenate([raw[:GUARD], raw[GUARD + self.rows * self.ld:], region[gap]])
         assert (untouched.view(np.uint8) == 0xFF).all(), "a store landed outside the output (guard band or column gap changed)"
         out = region[:, self.col:self.col + self.cols].copy()
-        bad = ~np.isfinite(out.astype(f64))
+        bad = ~np.isfinite(out)
         assert not bad.any(), f"{int(bad.sum())} of {out.size} output elements not finite (first at {tuple(np.argwhere(bad)[0])}): never written, or NaN / inf computed"
         return out
 
@@ -169,8 +175,12 @@ def contraction(a, b, bias=None, res=None, rowbias=None, scale=None):
     """a . b^T (* scale[n]) + bias + per-image bias + residual in float64 on the exact operands (a: [..., M, K]; b: [N, K] f16 values or q - zp) and its f32
     error bound E = (K + 3 (+ 1 per-image bias) (+ 1 scale)) 2^-24 S"""
     a64, b64 = a.astype(f64), b.astype(f64)
-    pre, S = a64 @ b64.T, np.abs(a64) @ np.abs(b64).T
-    n = a.shape[-1] + 3 + (rowbias is not None) + (scale is not None)
+    return epilogue(a64 @ b64.T, np.abs(a64) @ np.abs(b64).T, a.shape[-1], bias, res, rowbias, scale)
+
+
+def epilogue(pre, S, k, bias=None, res=None, rowbias=None, scale=None):
+    """contraction's second half, on the float64 products pre = a . b^T and S = |a| . |b|^T of k terms each (tuned_rows.py forms them blockwise)"""
+    n = k + 3 + (rowbias is not None) + (scale is not None)
     if scale is not None:
         pre, S = pre * scale, S * np.abs(scale)
     for t in (bias, rowbias, res):
@@ -216,9 +226,13 @@ def ulps_off(got, want):
     return np.abs(order(got.astype(f16)) - order(want.astype(f16)))
 
 
+def bound_of(want, E):
+    return H * np.abs(want) + (1 + H) * E + TINY
+
+
 def check(got, want, E, what):
     g = got.astype(f64)
-    bound = H * np.abs(want) + (1 + H) * E + TINY
+    bound = bound_of(want, E)
     bad = np.abs(g - want) > bound
     if bad.any():
         i = tuple(np.argwhere(bad)[0])
@@ -342,14 +356,18 @@ def conv(gpu, x, w, bias, res, ib, act, stride, pad, w8=None, ld=None, col=0):
     return got, gpu.last_route()
 
 
+def ln_fold(w, gamma, beta, bias):
+    """the folded operands Gpu.gemm_ln builds: W' = f16(gamma W), c1 = sum_k W', c2 = W . beta + bias"""
+    wf = (gamma.astype(f32)[None, :] * w.astype(f32)).astype(f16)
+    return wf, wf.astype(f64).sum(axis=1).astype(f32), (w.astype(f64) @ beta.astype(f64) + bias.astype(f64)).astype(f32)
+
+
 def gemm_ln(gpu, x, w, gamma, beta, bias, res, act, with_rowstats):
     """osg_gemm_ln with the folded operands Gpu.gemm_ln builds (W' = f16(gamma W), c1 = sum_k W', c2 = W . beta + bias); with_rowstats: the producer's
     [M][K/32][2] slot sums handed over, built here in float32 from float64 sums (the consumer tested alone)"""
     m, k = x.shape
     n = w.shape[0]
-    wf = (gamma.astype(f32)[None, :] * w.astype(f32)).astype(f16)
-    c1 = wf.astype(f64).sum(axis=1).astype(f32)
-    c2 = (w.astype(f64) @ beta.astype(f64) + bias.astype(f64)).astype(f32)
+    wf, c1, c2 = ln_fold(w, gamma, beta, bias)
     rs = None
     if with_rowstats:
         x3 = x.astype(f64).reshape(m, k // 32, 32)
