@@ -18,83 +18,31 @@
 template <>
 int osg_mm::launch3_unit<0>(int entry, osg_ctx* ctx, GemmParams& p) { return launch3_in_unit<0>(entry, ctx, p); }
 
-int osg_conv3x3_supported(int N, int H, int W, int Cin, int Cout) {
-    if (!(W == 64 || W == 32 || W == 16 || W == 8)) return 0;
-    const int TI = W == 8 ? 2 : 1, TH = 128 / (W * TI);
-    if (H % TH || (W == 8 && H != 8)) return 0;
-    if (Cin % 64 || Cout % 4) return 0;
-    if ((double)N * H * W * Cin * 2.0 >= 2147483648.0 || (double)Cout * 9.0 * Cin * 2.0 >= 2147483648.0) return 0;
-    return 1;
-}
-
-// Shape gate + tile/split choice.  Model (cycles, calibrated like choose_v2 in osg_gemm.hip): a (slab, tap) unit costs
-// max(MFMA, bytes / 23 B/clk) with bytes = the weight tile + 1/9 of the patch; whole rounds of tiles over the CUs.
-// shape gate: -1 when the halo-reuse kernel does not take the shape; fills the buffer extents otherwise
+// shape gate: -1 when the halo-reuse kernel does not take the shape (osg_gemm_select.h halo3_takes, OSG_CONV3X3_OFF, operands not 16-byte aligned); fills the
+// buffer extents otherwise
 int osg_conv3x3_prepare(osg_ctx* ctx, GemmParams& p) {
     static const bool off = getenv("OSG_CONV3X3_OFF") != nullptr;
-    if (off) return -1;
-    const int W = p.W, H = p.H;
-    if (!(W == 64 || W == 32 || W == 16 || W == 8)) return -1;
-    if (p.Wo != W || p.Ho != H || p.sh != 1 || p.sw != 1 || p.pt != 1 || p.pl != 1 || p.KW != 3 || p.K != 9 * p.Cin) return -1;
-    if (p.Cin % 64 || p.N % 4) return -1;
-    const int TI = W == 8 ? 2 : 1, TH = 128 / (W * TI);
-    if (H % TH) return -1;
-    if (W == 8 && H != 8) return -1;
-    if (p.a_bytes_l >= 2147483648L || (double)p.N * p.K * 2.0 >= 2147483648.0) return -1;
+    if (off || !halo3_takes(select_shape(p, 1))) return -1;
     if ((((uintptr_t)p.A | (uintptr_t)p.Bt) & 15) != 0) return -1;
     p.a_bytes = (unsigned)p.a_bytes_l;
     p.b_bytes = (unsigned)((long)p.N * p.K * (p.w8 ? 1 : 2));
     return 0;
 }
 
-// every legal (BN, splits) with its modelled cost in cycles, cheapest first
-std::vector<std::pair<double, std::pair<int, int>>> osg_conv3x3_rank(const osg_ctx* ctx, const GemmParams& p) {
-    const int W = p.W;
-    const int TI = W == 8 ? 2 : 1, TH = 128 / (W * TI);
-    const double cus = ctx->num_cu;
-    const int slabs = p.Cin / 64;
-    const int mt = (p.M + 127) / 128;
-    const int pp = TI * (TH + 2) * (W == 8 ? 16 : W + 2);
-    std::vector<std::pair<double, std::pair<int, int>>> out;
-    static const int bns[3] = {80, 128, 160};
-    for (int bn : bns) {
-        if (bn != 128 && p.N % bn) continue;
-        const double tiles = (double)mt * ((p.N + bn - 1) / bn);
-        const double mfma = 128.0 * bn * 128.0 / 4069.0;
-        const double tload = (bn * (p.w8 ? 64.0 : 128.0) + pp * 128.0 / 9.0) / 23.0;
-        for (int s = 1; s <= (ctx->autotune ? 12 : 8); s++) {
-            if (s > 1 && slabs / s < (ctx->autotune ? 1 : 2)) break;   // measured choice: let finer splits compete too
-            const int sl = (slabs + s - 1) / s;
-            if (s > 1 && sl * (s - 1) >= slabs) continue;
-            const double blocks = tiles * s;
-            const double rounds = std::ceil(blocks / cus);
-            double cost = rounds * (sl * 9.0 * (std::max(mfma, tload) + 250.0) + 6000.0);
-            if (s > 1) cost += 9000.0 + (double)p.M * p.N * s * 4.0 / 2000.0;
-            out.push_back({cost, {bn, s}});
-            // (measured candidates only) the same split finished inside the kernel by the last arriver of each tile: splits + 1000
-            if (ctx->autotune && s >= 2 && s <= 4 && osg_mm::splitk_fold_mode() != 0) out.push_back({cost * 1.0005, {bn, s + 1000}});
-        }
-    }
-    std::stable_sort(out.begin(), out.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    return out;
-}
-
 // launch one configuration (reduce kernel included); p must have passed osg_conv3x3_prepare.  The request resolves to an instantiation first (osg_gemm_routes.h
 // resolve3: 8 loader waves only where the ring stays deep enough, uint8 codes with 160 columns at W = 64 run 80), the split is sized for the tile that runs.
-int osg_conv3x3_launch(osg_ctx* ctx, GemmParams p, int bn, int s, int nl, int fold) {
-    const int entry = resolve3(p.W, bn, nl, p.w8 != 0);
+int osg_conv3x3_launch(osg_ctx* ctx, GemmParams p, Halo3Choice ch) {
+    const int entry = resolve3(p.W, ch.bn, ch.loaders, p.w8 != 0);
     if (entry < 0) OSG_FAIL(ctx, "osg_conv3x3: no kernel takes this image width");
-    bn = kV3Entries[entry].bn;
-    const int slabs = p.Cin / 64;
-    if (s < 1) s = 1;
-    const int sl = (slabs + s - 1) / s;
-    p.splits = (slabs + sl - 1) / sl;
-    p.k_per_split = sl * 64;
+    const int bn = kV3Entries[entry].bn;
+    const auto [slices, slabs_per] = split_slices(p.Cin / 64, ch.splits);
+    p.splits = slices;
+    p.k_per_split = slabs_per * 64;
     p.tickets = nullptr;
     p.fold_acc = 0;
     if (p.splits > 1) {
         size_t need = (size_t)p.splits * p.M * p.N * sizeof(float);
-        if (fold) need = std::max(need, osg_mm::splitk_fold_route(ctx, p, (long)((p.M + 127) / 128) * ((p.N + bn - 1) / bn), 128, bn));
+        if (ch.fold) need = std::max(need, osg_mm::splitk_fold_route(ctx, p, (long)((p.M + 127) / 128) * ((p.N + bn - 1) / bn), 128, bn));
         if (osg_ensure_workspace(ctx, need)) return 1;
         p.partial = (float*)ctx->ws;
     }
@@ -105,15 +53,10 @@ int osg_conv3x3_launch(osg_ctx* ctx, GemmParams p, int bn, int s, int nl, int fo
     return 0;
 }
 
+// the cost model's choice (osg_gemm_select.h model_halo3), then the per-call OSG_CONV3X3_* overrides
 int osg_conv3x3_run(osg_ctx* ctx, GemmParams& p) {
     if (osg_conv3x3_prepare(ctx, p)) return -1;
-    auto ranked = osg_conv3x3_rank(ctx, p);
-    int best_bn = 128, best_s = 1;
-    if (!ranked.empty()) { best_bn = ranked[0].second.first; best_s = ranked[0].second.second % 1000; }
-    if (const char* e = getenv("OSG_CONV3X3_BN")) best_bn = atoi(e);
-    if (const char* e = getenv("OSG_CONV3X3_SPLITS")) best_s = atoi(e);
-    int nl = 4;
-    if (const char* e = getenv("OSG_CONV3X3_NL")) nl = atoi(e) == 8 ? 8 : 4;
-    const int fold = getenv("OSG_CONV3X3_FOLD") ? atoi(getenv("OSG_CONV3X3_FOLD")) : 0;   // (tests / probes)
-    return osg_conv3x3_launch(ctx, p, best_bn, best_s, nl, fold);
+    Halo3Choice ch = model_halo3(select_env(ctx), select_shape(p, 1));
+    apply_knobs(kHalo3Knobs, &ch);
+    return osg_conv3x3_launch(ctx, p, ch);
 }

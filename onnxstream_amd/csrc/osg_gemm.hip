@@ -1,17 +1,24 @@
-// libosgpu: dense contractions on the gfx950 matrix cores.
+// libosgpu: dense contractions on the gfx950 matrix cores -- the launchers of Conv (XnnPack::convolution, reference onnxstream.cpp:1292) and MatMul/Gemm
+// (XnnPack::matrix_multiply, :1035):   C[M,N] = A[M,K] * Bt[N,K]^T   (f16 operands or uint8 weight codes, f32 accumulate on v_mfma_f32_16x16x32_f16, one RNE
+// rounding to f16 in the epilogue -- the numerics class of XNNPACK's f16_f32acc GEMMs).
 //
-// One implicit-GEMM kernel serves Conv (XnnPack::convolution, reference onnxstream.cpp:1292) and MatMul/Gemm
-// (XnnPack::matrix_multiply, :1035):   C[M,N] = A[M,K] * Bt[N,K]^T   (f16 operands, f32 accumulate on
-// v_mfma_f32_16x16x32_f16, one RNE rounding to f16 in the epilogue -- the numerics class of XNNPACK's f16_f32acc GEMMs).
-//   * A is either a plain row-major matrix or gathered on the fly from an NHWC activation (im2col never materialised):
-//     m -> (n,ho,wo), k -> (kh,kw,c); a 16-byte k-chunk never straddles a filter tap when Cin % 8 == 0.
-//   * Bt is K-contiguous: OHWI conv weights already are [Cout][KH*KW*Cin]; MatMul weights ([K,N] on disk) are
-//     re-laid out to [N,K] once when they become resident.
-//   * global -> registers -> LDS (padded rows: +16 B => conflict-free ds_read_b128), double-buffered, one barrier per
-//     k-tile, next tile's global loads in flight under the MFMAs.
-//   * operands are swapped (weights as MFMA "A") so each lane owns 4 consecutive output channels of one pixel:
-//     8-byte epilogue stores, bias/residual fused in f32 before the single rounding.
-//   * split-K (grid.z) with f32 partial slabs + a fused reduce epilogue for the small-M (8x8, 16x16 latent) layers.
+// What runs a request (run_gemm, conv2d_route):
+//   * gemm2_kernel (osg_gemm2.h; this unit instantiates the f16 tiles 0-3, osg_gemm_wide.hip / osg_gemm_w8.hip / osg_gemm_w8_conv.hip the rest): global -> LDS by
+//     DMA, a 2 .. 8-stage ring -- every shape with K (Cin) % 64 == 0 and 16-byte aligned operands under 2 GiB.  What it REQUESTS (tile, ring, k-slices, fold, loader
+//     waves) is decided in osg_gemm_select.h -- the cost model's default, or with autotune the measured choice (run_measured below, osg_tune.h) --, and
+//     osg_gemm_routes.h resolves the request to an instantiation.
+//   * conv3x3_kernel (osg_conv3x3.hip) for the 3x3 / stride 1 / pad 1 convolutions it takes; with autotune it competes with gemm2_kernel per shape.
+//   * conv_cin4_mfma_kernel below for 3x3 convolutions of 4 input channels.
+//   * gemm_kernel below, the register-staged kernel of round 1, for everything else (K or Cin no multiple of 64, unaligned operands):
+//       - A is either a plain row-major matrix or gathered on the fly from an NHWC activation (im2col never materialised):
+//         m -> (n,ho,wo), k -> (kh,kw,c); a 16-byte k-chunk never straddles a filter tap when Cin % 8 == 0.
+//       - Bt is K-contiguous: OHWI conv weights already are [Cout][KH*KW*Cin]; MatMul weights ([K,N] on disk) are
+//         re-laid out to [N,K] once when they become resident.
+//       - global -> registers -> LDS (padded rows: +16 B => conflict-free ds_read_b128), double-buffered, one barrier per
+//         k-tile, next tile's global loads in flight under the MFMAs.
+//       - operands are swapped (weights as MFMA "A") so each lane owns 4 consecutive output channels of one pixel:
+//         8-byte epilogue stores, bias/residual fused in f32 before the single rounding.
+//   * split-K (grid.z) with f32 partial slabs + a fused reduce epilogue (the launches below) for the small-M (8x8, 16x16 latent) layers, or folded in the kernel.
 #include "osg_gemm_common.h"
 #include "osg_tune.h"
 #include <algorithm>
@@ -381,66 +388,11 @@ int launch_cfg(osg_ctx* ctx, const GemmParams& p, int batch) {
 }
 
 
-// v2 tile / ring / split-K choice.  Measured on MI355X (tools/gemm_probe.py): the L2->LDS DMA path sustains ~23 B/clk per CU
-// and bounds every configuration (a 128x128x64 k-tile moves 32 KiB for 515 MFMA cycles), so the model is: k-tile time =
-// max(MFMA, bytes / 23) (+ ~450 exposed cycles when a block is alone on its CU), whole rounds of tiles over the CU slots,
-// a fixed fill + epilogue per round, and the extra pass of a split-K reduce.
-// every legal (tile, stages, splits) with its modelled cost in cycles, cheapest first
-static std::vector<std::pair<double, V2Choice>> rank_v2(const osg_ctx* ctx, int M, int N, int K, int batch, bool allow_split, V2Form form = V2Form{}) {
-    const double cus = ctx->num_cu;
-    const int kt = K / 64;
-    std::vector<std::pair<double, V2Choice>> out;
-    static const bool no_wide = getenv("OSG_TUNE_NO_WIDE") != nullptr;   // (A/B runs: the candidate set of round 5)
-    for (int c = 0; c < (ctx->autotune ? (no_wide ? 4 : 8) : 3); c++)
-        for (int nst = 8; nst >= 2; nst -= 2) {
-            if (!v2_holds(form, c, nst)) continue;                            // (an instantiation for the form: osg_gemm_routes.h)
-            // 6 / 8 stages (every tile of a short-K GEMM in flight at once): only as a measured candidate, only where the ring fits the LDS
-            if ((nst == 6 || nst == 8) && !ctx->autotune) continue;
-            if (c >= 4 && N % 80 != 0) continue;              // (the 80 / 160-column tiles are for the widths they divide)
-            const int bnp = (kV2BN[c] + 31) / 32 * 32;
-            const double tiles = (double)((M + kV2BM[c] - 1) / kV2BM[c]) * ((N + kV2BN[c] - 1) / kV2BN[c]) * batch;
-            const double mfma = kV2BM[c] * kV2BN[c] * 128.0 / 4069.0;
-            const double tload = (kV2BM[c] * 128.0 + kV2BN[c] * (form.w8 ? 64.0 : 128.0)) / 23.0;
-            const int smem = form.w8 ? nst * (kV2BM[c] * 128 + (kV2BN[c] + 63) / 64 * 64 * 64) : nst * (kV2BM[c] + bnp) * 128;
-            if (smem > 160 * 1024) continue;
-            const int bpc = std::min(4, 163840 / smem);
-            for (int s = 1; s <= (allow_split ? 16 : 1); s++) {
-                if (s > 1 && (kt / s < (ctx->autotune ? 3 : 8))) break;   // measured choice: let shorter slices compete too
-                const int kts = (kt + s - 1) / s;
-                if (s > 1 && (kts * (s - 1) >= kt)) continue;   // an empty split
-                const double blocks = tiles * s;
-                const double rounds = std::ceil(blocks / (cus * bpc));
-                const double conc = std::min((double)bpc, std::ceil(blocks / cus));
-                const double tk = conc <= 1.0 ? std::max(mfma, tload) + 450.0 : conc * std::max(mfma, tload);
-                double cost = rounds * (kts * tk + 3500.0);
-                if (s > 1) cost += 9000.0 + (double)M * N * batch * s * 4.0 / 2000.0;   // reduce launch (measured ~4-7 us) + slab traffic
-                out.push_back({cost, V2Choice{c, nst, s}});
-                // (measured candidates only, round 6) the one-workgroup-per-CU tiles with their DMA requests issued by four LOADER waves: a wave that issues both
-                // stalls ~70-100 cycles per request (the CU's address path takes 1 KiB per ~17 cycles and the four waves queue on it) with its MFMAs behind them
-                static const bool no_spec = getenv("OSG_TUNE_NO_SPEC") != nullptr;   // (A/B runs)
-                if (ctx->autotune && !no_spec && !no_wide && !form.w8 && (c == 0 || c == 4) && nst == 4 && s == 1 && !form.conv && !form.ln1) out.push_back({cost * 0.9995, V2Choice{c, nst, s, 1, 0, 1}});
-                // KS = 2 (measured candidates only): the 64x64 tile with a 2- or 4-stage ring, the 128x64 tile with 2 stages (what the 160 KiB hold), >= 2 k-tiles per slice
-                static const bool no_ks2 = getenv("OSG_TUNE_NO_KS2") != nullptr;   // (A/B runs)
-                if (ctx->autotune && !no_ks2 && !form.w8 && kts >= 2 && ((c == 2 && (nst == 2 || nst == 4)) || (c == 1 && nst == 2))) out.push_back({cost * 0.999, V2Choice{c, nst, s, 2}});
-                // (measured candidates only) 2 .. 4 slices folded by the last arriver of each tile instead of a reduce launch: the tiles of at most 10 accumulator quads per lane
-                if (ctx->autotune && s >= 2 && s <= 4 && c != 0 && c != 4 && c != 7 && osg_mm::splitk_fold_mode() != 0) out.push_back({cost * 1.0005, V2Choice{c, nst, s, 1, 1}});
-            }
-        }
-    std::stable_sort(out.begin(), out.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    return out;
-}
-static V2Choice choose_v2(const osg_ctx* ctx, int M, int N, int K, int batch) {
-    auto r = rank_v2(ctx, M, N, K, batch, true);
-    return r.empty() ? V2Choice{0, 4, 1} : r[0].second;
-}
-
-static osg_tune::Key tune_key(const osg_ctx* ctx, int kind, const GemmParams& p, int batch) {
-    osg_tune::Key k{};
-    k.kind = kind; k.device = 0;   /* (one table for every MI355X of a node: ranks seeded from one file make identical choices) */ k.M = p.M; k.N = p.N; k.K = p.K; k.batch = batch;
-    if (kind != 0) { k.H = p.H; k.W = p.W; k.Cin = p.Cin; k.KW = p.KW; k.sh = p.sh; k.sw = p.sw; }
-    else k.H = p.lda;
-    k.flags = (int)p.act | (p.residual ? 16 : 0) | (p.rowbias ? 32 : 0) | (p.bias_f32 ? 64 : 0) | (p.ln_c1 ? 128 : 0) | (p.rs_in ? 256 : 0) | (p.rs_out ? 512 : 0) | (p.w8 ? 1024 : 0);
-    return k;
+static KeyForm key_form(const GemmParams& p) {
+    KeyForm f;
+    f.act = (int)p.act; f.residual = p.residual != nullptr; f.rowbias = p.rowbias != nullptr; f.bias_f32 = p.bias_f32 != 0; f.ln = p.ln_c1 != nullptr;
+    f.rs_in = p.rs_in != nullptr; f.rs_out = p.rs_out != nullptr; f.w8 = p.w8 != 0;
+    return f;
 }
 // a launch may be repeated for timing only when it does not consume its own output
 static bool tune_safe(const GemmParams& p) { return (const void*)p.C != (const void*)p.A && (const void*)p.C != (const void*)p.residual; }
@@ -453,6 +405,39 @@ static V2Form v2_form(const GemmParams& p, bool conv) {
     return f;
 }
 
+// The measured choice of a launch (osg_tune.h), for the GEMM and the 3x3 convolution alike: the table's row for the key; on a miss the first of candidates() --
+// unless the launch may be timed (not frozen, not under capture, not consuming its own output): then every candidate is timed through launch(row), the
+// fastest stored.  A frozen table remembers the untimed choice.  Then the launch itself.
+template <class Candidates, class Launch>
+int run_measured(osg_ctx* ctx, const osg_tune::Key& key, const GemmParams& p, const char* what, Candidates&& candidates, Launch&& launch) {
+    osg_tune::Choice row;
+    if (!osg_tune::lookup(key, &row)) {
+        const std::vector<Candidate> cands = candidates();
+        row = cands.empty() ? tune_row(V2Choice{0, 4, 1}) : cands[0].row;   // (no candidate: a form no kernel takes -- the launch says so)
+        if (!ctx->capturing && tune_safe(p) && !cands.empty() && !osg_tune::frozen()) {
+            static const bool dump = getenv("OSG_TUNE_DUMP") != nullptr;
+            row.us = -1.f;
+            for (const Candidate& c : cands) {
+                const float us = osg_tune::time_us(ctx, [&] { return launch(c.row); });
+                if (dump && c.row.family == 1) {
+                    const Halo3Choice h = row_halo3(c.row);
+                    fprintf(stderr, "[tune] %s M=%d N=%d K=%d flags=%d: halo bn=%d splits=%d loaders=%d fold=%d -> %.2f us (model %.0f)\n", what, p.M, p.N, p.K, key.flags, h.bn, h.splits,
+                            h.loaders, h.fold, us, c.model);
+                } else if (dump) {
+                    const V2Choice v = row_v2(c.row);
+                    fprintf(stderr, "[tune] %s M=%d N=%d K=%d flags=%d: tile %dx%d nst=%d splits=%d ks=%d fold=%d spec=%d -> %.2f us (model %.0f)\n", what, p.M, p.N, p.K, key.flags,
+                            kV2BM[v.cfg], kV2BN[v.cfg], v.nst, v.splits, v.ks, v.fold, v.spec, us, c.model);
+                }
+                if (us >= 0.f && (row.us < 0.f || us < row.us)) { row = c.row; row.us = us; }
+            }
+            if (row.us < 0.f) OSG_FAIL(ctx, "osg_gemm / osg_conv2d_nhwc: autotune could not time any configuration");
+            osg_tune::store(key, row);
+        } else if (osg_tune::frozen())
+            osg_tune::remember(key, row);
+    }
+    return launch(row);
+}
+
 // launch one configuration: resolve it to an instantiation (osg_gemm_routes.h resolve_v2), size split-K for the tile that runs, launch, then the reduce launch
 // unless the split is folded in the kernel
 template <bool CONV>
@@ -460,9 +445,8 @@ int launch_v2_choice(osg_ctx* ctx, GemmParams p, int batch, V2Choice ch) {
     const V2Route r = resolve_v2(ch, v2_form(p, CONV));
     if (r.entry < 0) OSG_FAIL(ctx, "osg_gemm: no kernel takes this form (LayerNorm or row statistics with uint8 weight codes, LayerNorm in a convolution)");
     const V2Entry& e = kV2Entries[r.entry];
-    const int ktiles = p.K / 64;
-    int kt_per = (ktiles + ch.splits - 1) / ch.splits;
-    p.splits = (ktiles + kt_per - 1) / kt_per;
+    const auto [slices, kt_per] = split_slices(p.K / 64, ch.splits);
+    p.splits = slices;
     p.k_per_split = kt_per * 64;
     p.tickets = nullptr;
     p.fold_acc = 0;
@@ -483,51 +467,19 @@ int launch_v2_choice(osg_ctx* ctx, GemmParams p, int batch, V2Choice ch) {
     return 0;
 }
 
+// gemm2_kernel's request: the caller's (a candidate being timed), the measured choice, or the cost model's default with the per-call OSG_GEMM_* overrides
 template <bool CONV>
 int run_gemm_v2(osg_ctx* ctx, GemmParams p, int batch, const V2Choice* forced) {
-    const bool allow_split = p.act != OSG_ACT_GEGLU && !p.ln_c1 && !p.rs_out;   // GEGLU pairing / folded LayerNorm / row statistics live in the tile epilogue
-    V2Choice ch;
-    const bool env_forced = getenv("OSG_GEMM_CFG") || getenv("OSG_GEMM_SPLITS") || getenv("OSG_GEMM_NST") || getenv("OSG_GEMM_KS") || getenv("OSG_GEMM_FOLD") || getenv("OSG_GEMM_SPEC");
-    if (forced) {
-        ch = *forced;
-    } else if (ctx->autotune && !env_forced) {
-        const osg_tune::Key key = tune_key(ctx, CONV ? 2 : 0, p, batch);
-        osg_tune::Choice tc;
-        if (osg_tune::lookup(key, &tc)) {
-            ch = tune_choice(tc.cfg, tc.nst, tc.splits);
-        } else {
-            auto ranked = rank_v2(ctx, p.M, p.N, p.K, batch, allow_split, v2_form(p, CONV));
-            ch = ranked.empty() ? V2Choice{0, 4, 1} : ranked[0].second;
-            if (!ctx->capturing && tune_safe(p) && !ranked.empty() && !osg_tune::frozen()) {
-                float best = -1.f;
-                for (auto& cand : ranked) {
-                    const float us = osg_tune::time_us(ctx, [&] { return launch_v2_choice<CONV>(ctx, p, batch, cand.second); });
-                    static const bool dump = getenv("OSG_TUNE_DUMP") != nullptr;
-                    if (dump) fprintf(stderr, "[tune] %s M=%d N=%d K=%d flags=%d: tile %dx%d nst=%d splits=%d ks=%d -> %.2f us (model %.0f)\n", CONV ? "conv" : "gemm", p.M, p.N, p.K, key.flags,
-                                      kV2BM[cand.second.cfg], kV2BN[cand.second.cfg], cand.second.nst, cand.second.splits, cand.second.ks + 10 * cand.second.fold + 100 * cand.second.spec, us, cand.first);
-                    if (us >= 0.f && (best < 0.f || us < best)) { best = us; ch = cand.second; }
-                }
-                if (best < 0.f) OSG_FAIL(ctx, "osg_gemm: autotune could not time any configuration");
-                osg_tune::store(key, osg_tune::Choice{0, tune_cfg(ch), ch.nst, ch.splits, 0, best});
-            } else if (osg_tune::frozen())
-                osg_tune::remember(key, osg_tune::Choice{0, tune_cfg(ch), ch.nst, ch.splits, 0, -1.f});
-        }
-    } else {
-        if (p.w8) {
-            V2Form form;
-            form.conv = CONV; form.geglu = p.act == OSG_ACT_GEGLU; form.w8 = true;
-            auto r = rank_v2(ctx, p.M, p.N, p.K, batch, allow_split, form);
-            ch = r.empty() ? V2Choice{0, 4, 1} : r[0].second;
-        } else
-        ch = choose_v2(ctx, p.M, p.N, p.K, batch);
-        if (const char* e = getenv("OSG_GEMM_CFG")) ch.cfg = atoi(e);
-        if (const char* e = getenv("OSG_GEMM_SPLITS")) ch.splits = atoi(e);
-        if (!allow_split) ch.splits = 1;
-        if (const char* e = getenv("OSG_GEMM_NST")) ch.nst = atoi(e);
-        if (const char* e = getenv("OSG_GEMM_KS")) ch.ks = atoi(e) == 2 ? 2 : 1;
-        if (const char* e = getenv("OSG_GEMM_SPEC")) ch.spec = atoi(e) != 0;   // (tests / probes: four loader waves, tiles 0 and 4 with a 4-stage ring)
-        if (const char* e = getenv("OSG_GEMM_FOLD")) ch.fold = atoi(e) != 0;   // (tests / probes: finish a forced split inside the kernel)
-    }
+    if (forced) return launch_v2_choice<CONV>(ctx, p, batch, *forced);
+    const SelectEnv env = select_env(ctx);
+    const V2Form form = v2_form(p, CONV);
+    if (env.measured && !apply_knobs<V2Choice>(kGemmKnobs, nullptr))
+        return run_measured(ctx, tune_key(CONV ? 2 : 0, select_shape(p, batch), key_form(p)), p, CONV ? "conv" : "gemm",
+                            [&] { return gemm_candidates(env, p.M, p.N, p.K, batch, form); },
+                            [&](const osg_tune::Choice& row) { return launch_v2_choice<CONV>(ctx, p, batch, row_v2(row)); });
+    V2Choice ch = model_choice(env, p.M, p.N, p.K, batch, form);
+    apply_knobs(kGemmKnobs, &ch);
+    if (!v2_allows_split(form)) ch.splits = 1;   // (an override included)
     return launch_v2_choice<CONV>(ctx, p, batch, ch);
 }
 
@@ -536,7 +488,7 @@ int run_gemm(osg_ctx* ctx, GemmParams p, int batch, const V2Choice* forced = nul
     if (epi_check(ctx, p)) return 1;
     {
         static const bool force_v1 = getenv("OSG_GEMM_V1") != nullptr;
-        const bool shape_ok = p.K % 64 == 0 && (CONV ? p.Cin % 64 == 0 : p.lda % 8 == 0);
+        const bool shape_ok = v2_takes(select_shape(p, batch), CONV);
         const bool align_ok = (((uintptr_t)p.A | (uintptr_t)p.Bt) & 15) == 0 && (p.strideA % 8 == 0) && (p.strideB % 8 == 0);
         const double a_ext = CONV ? (double)p.a_bytes_l : ((double)(p.M - 1) * p.lda + p.K) * 2.0;
         const double b_ext = (double)p.N * p.K * (p.w8 ? 1.0 : 2.0);
@@ -550,28 +502,11 @@ int run_gemm(osg_ctx* ctx, GemmParams p, int batch, const V2Choice* forced = nul
         if (p.act == OSG_ACT_GEGLU) OSG_FAIL(ctx, "osg_gemm: GEGLU epilogue needs 16-byte aligned operands (direct-to-LDS kernel only)");
         if (p.ln_c1 || p.rs_out) OSG_FAIL(ctx, "osg_gemm_ln / osg_gemm_rowstats: need K % 64 == 0 and 16-byte aligned operands (direct-to-LDS kernel only)");
     }
+    // the register-staged kernel: tile and k-slices by choose_v1 (osg_gemm_select.h), over 32-deep k-tiles
     const bool vec = CONV ? (p.Cin % 8 == 0) : (p.K % 8 == 0 && p.lda % 8 == 0);
-    // ---- tile / split-K selection -------------------------------------------------------------------------
-    auto tiles = [&](int bm, int bn) { return (long)((p.M + bm - 1) / bm) * ((p.N + bn - 1) / bn) * batch; };
-    const long cu = ctx->num_cu;
-    int cfg;  // 0: 128x128x32, 1: 128x64x32, 2: 64x64x32
-    if (tiles(128, 128) >= cu && p.N % 128 == 0) cfg = 0;
-    else if (tiles(128, 64) >= cu && p.M >= 128) cfg = 1;
-    else cfg = 2;
-    const int bm = cfg == 2 ? 64 : 128, bn = cfg == 0 ? 128 : 64;
-    long t = tiles(bm, bn);
-    int splits = 1;
-    const int BK = 32;
-    if (t < cu && p.K >= 1024) {
-        splits = (int)((2 * cu + t - 1) / t);
-        int max_splits = p.K / 256;
-        if (splits > max_splits) splits = max_splits;
-        if (splits > 32) splits = 32;
-        if (splits < 1) splits = 1;
-    }
-    int ktiles = (p.K + BK - 1) / BK;
-    int kt_per = (ktiles + splits - 1) / splits;
-    splits = (ktiles + kt_per - 1) / kt_per;
+    const V1Choice v1 = choose_v1(ctx->num_cu, p.M, p.N, p.K, batch);
+    const int cfg = v1.cfg, BK = 32;
+    const auto [splits, kt_per] = split_slices((p.K + BK - 1) / BK, v1.splits);
     p.splits = splits;
     p.k_per_split = kt_per * BK;
     if (splits > 1) {
@@ -964,48 +899,21 @@ static int conv2d_route(osg_ctx* ctx, GemmParams& p, int N, int Cin, int Cout, i
         return run_gemm<false>(ctx, p, 1);
     }
     if (KH == 3) {
-        const bool env_forced = getenv("OSG_CONV3X3_BN") || getenv("OSG_CONV3X3_SPLITS") || getenv("OSG_CONV3X3_DBG") || getenv("OSG_GEMM_CFG") ||
-                                getenv("OSG_GEMM_SPLITS") || getenv("OSG_GEMM_NST");
+        // (both lists of override variables force the halo kernel's model choice: osg_conv3x3_run leaves the OSG_GEMM_* ones to the implicit GEMM it falls back to)
+        const bool env_forced = apply_knobs<Halo3Choice>(kHalo3Knobs, nullptr) || apply_knobs<V2Choice>(kGemmKnobs, nullptr) || getenv("OSG_CONV3X3_DBG");
         if (!ctx->autotune || env_forced) {
             int rc3 = osg_conv3x3_run(ctx, p);
             if (rc3 >= 0) return rc3;
         } else if (osg_conv3x3_prepare(ctx, p) == 0) {
-            // measured choice between the halo-reuse kernel's (BN, splits) and the implicit-GEMM kernel's (tile, stages, splits)
-            const osg_tune::Key key = tune_key(ctx, 1, p, 1);
-            osg_tune::Choice tc;
-            if (!osg_tune::lookup(key, &tc)) {
-                auto r3 = osg_conv3x3_rank(ctx, p);
-                tc = osg_tune::Choice{1, 0, 0, r3.empty() ? 1 : r3[0].second.second % 1000, r3.empty() ? 128 : r3[0].second.first, -1.f};
-                if (!ctx->capturing && tune_safe(p) && !osg_tune::frozen()) {
-                    float best = -1.f;
-                    static const bool dump3 = getenv("OSG_TUNE_DUMP") != nullptr;
-                    for (auto& c : r3)
-                        for (int nl : {4, 8}) {   // (nst of a conv3x3 row = loader waves of the halo kernel)
-                            static const bool no8 = getenv("OSG_TUNE_NO_NL8") != nullptr;   // (A/B runs)
-                            if (nl == 8 && (no8 || p.w8)) continue;   // (uint8 weight codes: the 4-loader kernel only)
-                            const int fold3 = c.second.second >= 1000;   // (osg_conv3x3_rank: splits + 1000 = the same split, folded in the kernel)
-                            const int s3 = c.second.second % 1000;
-                            const float us = osg_tune::time_us(ctx, [&] { return osg_conv3x3_launch(ctx, p, c.second.first, s3, nl, fold3); });
-                            if (dump3) fprintf(stderr, "[tune] conv3x3 N*H*W=%d Cin=%d Cout=%d W=%d: halo bn=%d splits=%d loaders=%d -> %.2f us\n", p.M, p.Cin, p.N, p.W, c.second.first, c.second.second, nl, us);
-                            if (us >= 0.f && (best < 0.f || us < best)) { best = us; tc = osg_tune::Choice{1, tune_cfg(V2Choice{0, nl, s3, 1, fold3}), nl, s3, c.second.first, us}; }
-                        }
-                    V2Form form3;
-                    form3.conv = true; form3.w8 = p.w8 != 0;
-                    auto r2 = rank_v2(ctx, p.M, p.N, p.K, 1, true, form3);
-                    if (r2.size() > 6) r2.resize(6);
-                    for (auto& c : r2) {
-                        const V2Choice ch = c.second;
-                        const float us = osg_tune::time_us(ctx, [&] { return run_gemm<true>(ctx, p, 1, &ch); });
-                        if (us >= 0.f && (best < 0.f || us < best)) { best = us; tc = osg_tune::Choice{0, tune_cfg(ch), ch.nst, ch.splits, 0, us}; }
-                    }
-                    if (best < 0.f) OSG_FAIL(ctx, "osg_conv2d_nhwc: autotune could not time any configuration");
-                    osg_tune::store(key, tc);
-                } else if (osg_tune::frozen())
-                    osg_tune::remember(key, tc);
-            }
-            const V2Choice ch = tune_choice(tc.cfg, tc.nst, tc.splits);
-            if (tc.family == 1) return osg_conv3x3_launch(ctx, p, tc.bn, tc.splits, tc.nst == 8 ? 8 : 4, ch.fold);
-            return run_gemm<true>(ctx, p, 1, &ch);
+            // measured choice between the halo-reuse kernel's (BN, splits, loader waves) and the implicit-GEMM kernel's (tile, stages, splits)
+            static const bool no_nl8 = getenv("OSG_TUNE_NO_NL8") != nullptr;   // (A/B runs)
+            return run_measured(ctx, tune_key(1, select_shape(p, 1), key_form(p)), p, "conv3x3",
+                                [&] { return conv3_candidates(select_env(ctx), select_shape(p, 1), no_nl8); },
+                                [&](const osg_tune::Choice& row) {
+                                    if (row.family == 1) return osg_conv3x3_launch(ctx, p, row_halo3(row));
+                                    const V2Choice ch = row_v2(row);
+                                    return run_gemm<true>(ctx, p, 1, &ch);
+                                });
         }
     }
     return run_gemm<true>(ctx, p, 1);

@@ -3,7 +3,7 @@
 #include <utility>
 #include <vector>
 #include "osg_common.h"
-#include "osg_gemm_routes.h"
+#include "osg_gemm_select.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -932,12 +932,46 @@ inline size_t splitk_fold_route(osg_ctx* ctx, GemmParams& p, long n_tiles, int b
     p.xcd_err = ctx->xcd_err_dev;       // (the bounded wait of the last arriver reports through it)
     return (size_t)n_tiles * p.splits * bm * bn * sizeof(float);
 }
+// what the launch choice (osg_gemm_select.h) reads of the context and the environment, built once per call.  OSG_SPLITK_FOLD is read per call, the A/B switches once.
+inline SelectEnv select_env(const osg_ctx* ctx) {
+    static const bool no_wide = getenv("OSG_TUNE_NO_WIDE") != nullptr, no_spec = getenv("OSG_TUNE_NO_SPEC") != nullptr, no_ks2 = getenv("OSG_TUNE_NO_KS2") != nullptr;
+    return SelectEnv{ctx->num_cu, ctx->autotune, splitk_fold_mode(), no_wide, no_spec, no_ks2};
+}
+inline SelectShape select_shape(const GemmParams& p, int batch) {
+    SelectShape s;
+    s.M = p.M; s.N = p.N; s.K = p.K; s.batch = batch; s.lda = p.lda;
+    s.H = p.H; s.W = p.W; s.Cin = p.Cin; s.Ho = p.Ho; s.Wo = p.Wo; s.KW = p.KW; s.sh = p.sh; s.sw = p.sw; s.pt = p.pt; s.pl = p.pl;
+    s.w8 = p.w8 != 0;
+    return s;
+}
+// The per-call override variables of a choice: one list per choice type, read by apply_knobs -- so "is the choice forced" and "what is it forced to" cannot differ.
+template <class C> struct Knob { const char* name; int C::*field; int (*value)(int); };
+inline int knob_int(int v) { return v; }
+inline int knob_flag(int v) { return v != 0; }
+inline constexpr Knob<V2Choice> kGemmKnobs[] = {
+    {"OSG_GEMM_CFG", &V2Choice::cfg, knob_int}, {"OSG_GEMM_SPLITS", &V2Choice::splits, knob_int}, {"OSG_GEMM_NST", &V2Choice::nst, knob_int},
+    {"OSG_GEMM_KS", &V2Choice::ks, [](int v) { return v == 2 ? 2 : 1; }},
+    {"OSG_GEMM_SPEC", &V2Choice::spec, knob_flag},   // (tests / probes: four loader waves, tiles 0 and 4 with a 4-stage ring)
+    {"OSG_GEMM_FOLD", &V2Choice::fold, knob_flag},   // (tests / probes: finish a forced split inside the kernel)
+};
+inline constexpr Knob<Halo3Choice> kHalo3Knobs[] = {
+    {"OSG_CONV3X3_BN", &Halo3Choice::bn, knob_int}, {"OSG_CONV3X3_SPLITS", &Halo3Choice::splits, knob_int},
+    {"OSG_CONV3X3_NL", &Halo3Choice::loaders, [](int v) { return v == 8 ? 8 : 4; }}, {"OSG_CONV3X3_FOLD", &Halo3Choice::fold, knob_flag},   // (tests / probes)
+};
+// sets the fields of *ch (where given) whose variable is set; returns whether any is
+template <class C, size_t N> bool apply_knobs(const Knob<C> (&knobs)[N], C* ch) {
+    bool any = false;
+    for (const Knob<C>& k : knobs)
+        if (const char* e = getenv(k.name)) {
+            any = true;
+            if (ch) ch->*k.field = k.value(atoi(e));
+        }
+    return any;
+}
 }  // namespace osg_mm
 
-// osg_conv3x3.hip: halo-reuse 3x3 / stride 1 / pad 1 convolution.  Returns -1 when the shape is not one it takes.
+// osg_conv3x3.hip: halo-reuse 3x3 / stride 1 / pad 1 convolution with the cost model's choice and the OSG_CONV3X3_* overrides.  Returns -1 when the shape is not one it takes.
 int osg_conv3x3_run(osg_ctx* ctx, osg_mm::GemmParams& p);
-// the same in pieces, for the measured configuration choice (osg_tune.h): shape gate, ranked (BN, splits) candidates, one launch
+// the same in pieces, for the measured configuration choice (osg_tune.h): shape gate (fills the buffer extents), one launch
 int osg_conv3x3_prepare(osg_ctx* ctx, osg_mm::GemmParams& p);
-std::vector<std::pair<double, std::pair<int, int>>> osg_conv3x3_rank(const osg_ctx* ctx, const osg_mm::GemmParams& p);
-int osg_conv3x3_launch(osg_ctx* ctx, osg_mm::GemmParams p, int bn, int splits, int loader_waves = 4, int fold = 0);   // fold: a 2 .. 4-way split finished by splitk_fold_acc
-int osg_conv3x3_supported(int N, int H, int W, int Cin, int Cout);
+int osg_conv3x3_launch(osg_ctx* ctx, osg_mm::GemmParams p, osg_mm::Halo3Choice ch);

@@ -1,5 +1,5 @@
 // libosgpu: which instantiations of the contraction kernels exist, and what a launch request runs -- the one list and the one resolution that the cost model and
-// the tuner (osg_gemm.hip rank_v2), the tune-table loader (osg_ctx.hip), the launchers (osg_gemm.hip launch_v2_choice, osg_conv3x3.hip osg_conv3x3_launch) and the
+// the tuner (osg_gemm_select.h rank_v2), the tune-table loader (osg_ctx.hip), the launchers (osg_gemm.hip launch_v2_choice, osg_conv3x3.hip osg_conv3x3_launch) and the
 // split-K fold sizing all read.  Host-only C++17 (no HIP): tests/cpp/contraction_routes.cpp compiles it with g++.
 //
 // A request names a tile, a ring depth and options; a form it asks for that has no instantiation runs the nearest one that does, by the fixed rules of resolve_v2 /

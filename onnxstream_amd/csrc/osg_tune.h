@@ -1,35 +1,19 @@
 // Measured configuration choice for the contraction launches (osg_gemm.hip, osg_conv3x3.hip).
 //
-// The tile / pipeline-depth / split-K choice of a GEMM or convolution is made by a small cost model (choose_v2, osg_conv3x3_run).  With
-// osg_set_autotune(ctx, 1) the first EAGER launch of a shape instead times every configuration the model considers legal on the caller's
-// own operands (HIP events on the compute stream, 1 warm + 2 timed launches each) and remembers the fastest; later launches -- including
+// The tile / pipeline-depth / split-K choice of a GEMM or convolution is made by a small cost model (osg_gemm_select.h: model_choice, model_halo3).  With
+// osg_set_autotune(ctx, 1) the first EAGER launch of a shape instead times every candidate of osg_gemm_select.h (gemm_candidates, conv3_candidates) on the
+// caller's own operands (HIP events on the compute stream; each candidate: 1 warm launch, then 3 launches behind a cache-evicting fill, the fastest counts --
+// OSG_TUNE_COLD=0: 1 warm + 2 back-to-back launches, their mean) and remembers the fastest; later launches -- including
 // the ones captured into a hipGraph -- reuse it.  The table is process-wide and keyed by the device, so every context (every Model) of a
 // process makes the same choice for the same shape: results stay bit-reproducible inside a process.  Contexts without autotune never
 // consult the table.  OSG_TUNE_CACHE=<file> persists the table across processes.  Nothing is tuned during graph capture (no synchronisation is allowed there): the model's choice is used.
+// The protocol itself (look up; frozen / capturing / unsafe to repeat: the first candidate; else time them all; store or remember) is run_measured in osg_gemm.hip.
 #pragma once
 #include <cstdlib>
-#include <tuple>
 #include "osg_common.h"
+#include "osg_gemm_select.h"   // Key, Choice: host-only
 
 namespace osg_tune {
-
-struct Key {
-    int kind;       // 0: GEMM, 1: 3x3/s1/p1 convolution (halo-reuse kernel and implicit GEMM compete), 2: other implicit-GEMM convolution
-    int device;
-    int M, N, K, batch;
-    int H, W, Cin, KW, sh, sw;
-    int flags;      // epilogue shape: act | residual << 4 | rowbias << 5 | bias_f32 << 6
-    bool operator<(const Key& o) const {
-        return std::tie(kind, device, M, N, K, batch, H, W, Cin, KW, sh, sw, flags) <
-               std::tie(o.kind, o.device, o.M, o.N, o.K, o.batch, o.H, o.W, o.Cin, o.KW, o.sh, o.sw, o.flags);
-    }
-};
-
-struct Choice {
-    int family;     // 0: gemm2 (cfg, nst, splits); 1: conv3x3 (bn, splits)
-    int cfg, nst, splits, bn;
-    float us;       // measured time of the winner
-};
 
 bool lookup(const Key& k, Choice* out);
 // OSG_TUNE_FROZEN=1: a shape the table does not hold is NOT timed -- it takes the cost model's first candidate (deterministic, nothing stored).  What the ranks of

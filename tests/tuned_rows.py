@@ -2,7 +2,7 @@
 and a float64 reference of every output element.  No GPU in here: tests/test_tuned_rows_cpu.py exercises it on the host, tests/tuned_rows_worker.py
 launches the rows (tests/test_tuned_rows.py).
 
-* Row -> call.  The 13 key fields as tune_key (osg_gemm.hip) forms them: kind 0 osg_gemm (lda == K; flags 128 osg_gemm_ln, with 256 on handed-over row
+* Row -> call.  The 13 key fields as tune_key (osg_gemm_select.h) forms them: kind 0 osg_gemm (lda == K; flags 128 osg_gemm_ln, with 256 on handed-over row
   statistics; 512 osg_gemm_rowstats; 1024 osg_gemm_w8 / osg_gemm_w8_v), kind 1 the 3 x 3 / stride 1 / pad 1 convolution, kind 2 any other convolution
   (KH = KW, pad KW // 2); low flag bits the activation, 16 a residual, 32 a per-image bias, 64 an f32 bias.  A bias is always passed.  uint8 rows on even
   table lines take scalar (scale, zero point), on odd lines with N % 4 == 0 per-column vectors.
