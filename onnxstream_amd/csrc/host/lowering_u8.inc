@@ -35,14 +35,19 @@
         if (t == "osg.qu8.AffineAct" || t == "osg.qu8.NormAffineAct") return lower_affine_act_u8(op);
         if (t == "Softmax") return lower_softmax_u8(op);
         if (t == "Reshape" || t == "Flatten" || t == "Unsqueeze" || t == "Squeeze" || t == "Transpose" || t == "Resize") {
-            // the codes are re-arranged, scale and zero point carried over (reference :4783, :5231, :6251)
+            // the codes are re-arranged, scale and zero point carried over (reference :4783, :5231, :6251, :8185) -- except by Squeeze and Unsqueeze, which
+            // hand the codes on WITHOUT them (reference :3901, :7470 copy type and data only): their output has scale 0 and zero point 0, whatever the input's
             const int x = in_val_raw(op.m_input[0]);
             if (t == "Reshape") lower_reshape(op);
             else if (t == "Flatten") lower_flatten(op);
             else if (t == "Unsqueeze" || t == "Squeeze") lower_squeeze(op, t == "Unsqueeze");
             else if (t == "Transpose") lower_transpose(op);
             else lower_resize(op);
-            P.share_q(P.by_name.at(op.m_output[0].m_name), x);
+            const int y = P.by_name.at(op.m_output[0].m_name);
+            if (t == "Unsqueeze" || t == "Squeeze") {
+                if (V(y).dtype == OSG_U8) P.own_q(y, 0.f, 0);
+            } else
+                P.share_q(y, x);
             return;
         }
         throw std::invalid_argument("Model::run: operation not implemented with uint8 arithmetic on the HIP backend: " + t);
@@ -153,7 +158,9 @@
             int pm[3] = {0, 2, 1};
             be.check(be.api.osg_transpose(be.ctx, 1, P.ptr(b), P.ptr(bt), 3, sh, pm), "MatMul");
         });
-        P.add_step("MatMul qu8 " + op.m_name, {a, bt}, {y}, [=, this] {
+        // (b is listed as read although the launch takes its codes from bt: the launch reads b's PARAMETERS, and a step that reads a value quantised per run has to
+        // lie in the eager prefix of the pass -- Plan::dyn_end goes by the reads)
+        P.add_step("MatMul qu8 " + op.m_name, {a, bt, b}, {y}, [=, this] {
             const Val &qa = P.qv(a), &qb = P.qv(b);
             be.check(be.api.osg_qu8_gemm(be.ctx, P.ptr(a), K, qa.qscale, qa.qzp, P.ptr(bt), qb.qscale, qb.qzp, nullptr, oq.scale, (int)oq.zero_point, P.ptr(y),
                                          (int)M, (int)Nn, (int)K, (int)n, M * K, Nn * K, M * Nn),
@@ -215,7 +222,6 @@
         const qu8::QParams oq = out_q(op);
         const int y = out_val_u8(op, os, olay, V(a).batched || V(b).batched, oq);
         const size_t prank = std::max(pa.size(), pb.size());
-        need(op, prank >= 1 || true, "");
         const size_t pr = std::max<size_t>(prank, 1);
         need(op, pr <= 6, "rank too large for the device broadcast kernel.");
         std::vector<long> sa(pr, 1), sb(pr, 1);

@@ -185,6 +185,7 @@ int Plan::alias(int v, const Shape& shape, Lay lay, const std::string& name) {
 
 const Val& Plan::qv(int v) const {
     for (int guard = 0; guard < 64; guard++) {
+        if (vals[v].qown) break;
         if (vals[v].qsrc >= 0) v = vals[v].qsrc;
         else if (vals[v].root >= 0) v = vals[v].root;
         else break;
@@ -195,15 +196,23 @@ const Val& Plan::qv(int v) const {
 void Plan::share_q(int dst, int src) {
     if (vals[src].dtype != OSG_U8 || dst == src) return;
     int s = src;
-    while (vals[s].qsrc < 0 && vals[s].root >= 0) s = vals[s].root;
-    if (vals[s].qsrc >= 0) s = vals[s].qsrc;
+    while (!vals[s].qown && vals[s].qsrc < 0 && vals[s].root >= 0) s = vals[s].root;
+    if (!vals[s].qown && vals[s].qsrc >= 0) s = vals[s].qsrc;
     int d = dst;
-    while (vals[d].root >= 0) d = vals[d].root;
+    while (!vals[d].qown && vals[d].root >= 0) d = vals[d].root;
     if (d == s) return;
     vals[d].qsrc = s;
     vals[d].qscale = vals[s].qscale;
     vals[d].qzp = vals[s].qzp;
     vals[d].qdyn = vals[s].qdyn;
+}
+
+void Plan::own_q(int v, float scale, int zp) {
+    vals[v].qown = true;
+    vals[v].qsrc = -1;
+    vals[v].qscale = scale;
+    vals[v].qzp = zp;
+    vals[v].qdyn = false;
 }
 
 long Plan::total_elems(int v) const { return vals[v].numel() * (vals[v].batched ? N : 1); }

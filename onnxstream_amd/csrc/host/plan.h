@@ -51,6 +51,7 @@ struct Val {
     int qzp = 0;                  //   dynamic quantisation of a pushed input)
     int qsrc = -1;                // >= 0: the val whose (qscale, qzp) this one shares (Reshape / Transpose / Resize carry them over) -- read at RUN time
     bool qdyn = false;            // parameters change from run to run (a pushed input and what merely re-arranges it)
+    bool qown = false;            // an alias with parameters of its OWN, not its root's (Squeeze / Unsqueeze: the reference hands the codes on without their parameters)
     int as_nk_u8 = -1;            // [N,K] twin of a [K,N] uint8 matrix
     // a VIRTUAL Expand (grouped-query attention's repeat_kv: [1,Hkv,1,S,d] -> [1,Hkv,rep,S,d], read only by ScaledDotProductAttention through a Reshape):
     // never materialised -- the attention launch reads `rep_src` with Hkv heads (plan.cpp lower_expand / lower_sdpa)
@@ -349,6 +350,7 @@ struct Plan {
     void add_step(const std::string& what, std::vector<int> reads, std::vector<int> writes, std::function<void()> fn);
     const Val& qv(int v) const;    // the val holding v's quantisation parameters
     void share_q(int dst, int src); // dst carries src's quantisation parameters
+    void own_q(int v, float scale, int zp);   // v (an alias) gets fixed parameters of its own
     int ensure_plain(int v);
     int ensure_nhwc(int v);
     // a device constant that survives this plan (ConstPool::derived) -- *fresh tells the caller to fill it; plan-owned (always fresh) in

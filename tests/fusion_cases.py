@@ -1050,7 +1050,7 @@ def bound16(case, o, level=None):
 # case -> a substring of the reference's refusal: restatement-only cases
 REF_REFUSES = {}
 
-# the fp16 passes of run_fusions() and the two lowering-time merges; the uint8 passes (fuse_u8_*) need range data and are out of scope
+# the fp16 passes of run_fusions() and the two lowering-time merges; the uint8 passes (fuse_u8_*) need range data: their table is tests/qu8_cases.py
 PASSES = ("fuse_sdpa", "fuse_rms_norm", "fuse_rope", "fuse_silu", "fuse_group_norm", "fuse_layer_norm", "fuse_geglu", "fuse_attention", "fuse_linear", "fuse_residual",
           "fuse_conv_act", "fuse_linear_geglu", "fuse_tblock_tail", "cse_silu", "fuse_gemm_act", "fuse_image_bias", "plan_linear_groups", "ln_fold")
 LEVELS = (0, 1, 2)

@@ -69,7 +69,7 @@ def test_table_is_well_formed():
 
 def test_every_pass_has_cases():
     src = open(os.path.join(REPO, "onnxstream_amd", "csrc", "host", "lowering_graph.inc")).read()
-    passes = {m for m in re.findall(r"void ((?:fuse_|cse_)\w+)\(", src) if not m.startswith("fuse_u8_")}     # (the uint8 passes need range data: DESIGN 6.2)
+    passes = {m for m in re.findall(r"void ((?:fuse_|cse_)\w+)\(", src) if not m.startswith("fuse_u8_")}     # (the uint8 passes need range data: tests/qu8_cases.py)
     assert passes, "no pass found in lowering_graph.inc"
     assert passes <= set(fc.PASSES), sorted(passes - set(fc.PASSES))
     for p in sorted(passes | {"plan_linear_groups", "ln_fold"}):

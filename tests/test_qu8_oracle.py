@@ -64,3 +64,25 @@ def test_dynamic_input_quantisation_matches_push_tensor(shape, threads):
     q, s, z0 = Q.quantize_dynamic(z, threads=threads)
     assert np.float32(s) == np.float32(scale.value) and z0 == zp.value
     assert np.array_equal(q.ravel(), ref_codes)
+
+
+def test_squeeze_and_unsqueeze_hand_the_codes_on_without_their_parameters():
+    """the reference's Squeeze and Unsqueeze copy type and data to the output and nothing else (src/onnxstream.cpp:3901, :7470; Reshape, Transpose, Resize and Flatten
+    also copy m_scale and m_zero_point, :4783, :5231, :6251, :8185): under uint8 arithmetic their output has scale 0 and zero point 0, so whatever reads it dequantises
+    every code to 0 -- a Sigmoid behind it gives sigmoid(0) everywhere.  Found by tools/make_golden_qu8_cases.py (the interpreter of tests/qu8_cases.py carried the
+    parameters over); pinned here on the reference's stored tensors, which tests/test_qu8_lowering_cpu.py checks against a fresh run where oracle/_ref is built."""
+    import os
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import qu8_cases as qcs
+    for name in ("move/squeeze_conv", "move/squeeze_pushed", "move/unsqueeze_conv", "move/unsqueeze_pushed"):
+        case = qcs.by_name(name)
+        moved, scale, zp = qcs.reference(case, "mvo")
+        assert (float(scale), zp) == (0.0, 0) and not moved.any(), name
+        out, so, zo = qcs.reference(case, "out")
+        half = qcs.deq(np.asarray(np.rint(np.float32(0.5) * (np.float32(1) / so)) + zo, np.uint8), so, zo)
+        assert np.array_equal(out, np.full(out.shape, half, np.float32)), name
+        want = qcs.want(case, 0)
+        assert (float(want["mvo"][1]), want["mvo"][2]) == (0.0, 0) and np.array_equal(qcs.deq(*want["out"]), out), name
+    kept, scale, zp = qcs.reference(qcs.by_name("move/flatten_pushed"), "mvo")
+    assert float(scale) > 0 and kept.any()
