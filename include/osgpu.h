@@ -206,6 +206,11 @@ int osg_gemm_rowstats(osg_ctx* ctx, const void* A, const void* B_nk, const void*
  *   out[2] the k-slices that ran;  out[3] 1 = the split was folded in the kernel
  *   out[4] the reduce kernel that finished the split: 0 none, 1 splitk_reduce_kernel, 2 / 3 splitk_reduce4_kernel<4 / 8>, 4 / 5 splitk_reduce_stats_kernel<4 / 8> */
 int osg_last_route(const osg_ctx* ctx, int out[5]);
+/* The epilogue variant of the most recent gemm2_kernel launch (family 0 of osg_last_route; other families leave {-1, -1}): a record of its own, so osg_last_route
+ * keeps its five fields.
+ *   out[0] the index into kLeanEntries (osg_gemm_epi.h) of the lean instantiation that ran, -1 = the entry's EPI_ANY instantiation
+ *   out[1] its EPI mask (-1 = EPI_ANY) */
+int osg_last_epilogue(const osg_ctx* ctx, int out[2]);
 /* The same kind of record for the attention and normalisation entry points -- osg_attention / osg_attention_strided / osg_sdpa, osg_group_norm_nhwc,
  * osg_group_norm_stats_nhwc, osg_layer_norm, osg_instance_norm, osg_tblock_tail, osg_qu8_*: what the most recent of these calls on ctx launched.  A sibling of osg_last_route and not
  * more family codes of it: the two records are independent (a contraction does not clear this one, nor the reverse) and this one has eight fields.  Host

@@ -24,6 +24,7 @@ struct osg_ctx {
     bool tuning = false, sink_fused = false;
     // what the most recent contraction launch ran (osg_last_route): family, instantiation, k-slices, folded in the kernel, reduce kernel
     int last_route[5] = {-1, -1, 0, 0, 0};
+    int last_epi[2] = {-1, -1};         // ... and its epilogue variant (osg_last_epilogue): lean instantiation, EPI mask
     // what the most recent attention / normalisation launch ran (osg_last_kernel): family, then the family's fields (include/osgpu.h)
     int last_kernel[8] = {-1, 0, 0, 0, 0, 0, 0, 0};
     hipEvent_t ev_t0 = nullptr, ev_t1 = nullptr;
@@ -68,6 +69,7 @@ inline bool osg_first_on_device(unsigned long long& mask) {
 inline void osg_set_route(osg_ctx* ctx, int family, int instantiation, int splits, int fold) {
     int* r = ctx->last_route;
     r[0] = family; r[1] = instantiation; r[2] = splits; r[3] = fold; r[4] = 0;
+    ctx->last_epi[0] = ctx->last_epi[1] = -1;
 }
 
 // record what an attention / normalisation entry point launches (osg_last_kernel): plain host stores at launch time, nothing on the stream

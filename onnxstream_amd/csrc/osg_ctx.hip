@@ -240,6 +240,12 @@ int osg_last_route(const osg_ctx* c, int out[5]) {
     return 0;
 }
 
+int osg_last_epilogue(const osg_ctx* c, int out[2]) {
+    if (!c || !out) return 1;
+    out[0] = c->last_epi[0]; out[1] = c->last_epi[1];
+    return 0;
+}
+
 int osg_last_kernel(const osg_ctx* c, int out[8]) {
     if (!c || !out) return 1;
     for (int i = 0; i < 8; i++) out[i] = c->last_kernel[i];

@@ -461,8 +461,15 @@ int launch_v2_choice(osg_ctx* ctx, GemmParams p, int batch, V2Choice ch) {
     const double a_unique = CONV ? (double)p.a_bytes : (double)p.M * p.K * 2.0;
     p.n_major = (double)p.N * p.K * (p.w8 ? 1.0 : 2.0) > a_unique;
     static constexpr int (*units[4])(int, osg_ctx*, GemmParams&, int) = {launch_v2_unit<0>, launch_v2_unit<1>, launch_v2_unit<2>, launch_v2_unit<3>};
-    if (const int rc = units[v2_unit(e)](r.entry, ctx, p, batch)) return rc;
+    // the epilogue variant (osg_gemm_epi.h): the lean instantiation compiled for exactly this launch's form, else the entry as it stands
+    const EpiLaunch el = epi_launch_of(p, batch);
+    const int lean = select_epi(r.entry, el, epi_generic_forced());
+    if (OSG_UNLIKELY(getenv("OSG_EPI_LOG") != nullptr))   // (tools/epilogue_forms_table.py: one line per launch)
+        fprintf(stderr, "[epi] entry=%d form=%d whole=%d lean=%d capturing=%d tuning=%d M=%d N=%d K=%d splits=%d\n", r.entry, epi_form(el), (int)epi_whole(el, e.bm, e.bn), lean,
+                (int)ctx->capturing, (int)ctx->tuning, p.M, p.N, p.K, p.splits);
+    if (const int rc = lean >= 0 ? launch_v2_lean(lean, ctx, p, batch) : units[v2_unit(e)](r.entry, ctx, p, batch)) return rc;
     osg_set_route(ctx, 0, r.entry, p.splits, p.fold_acc);
+    ctx->last_epi[0] = lean; ctx->last_epi[1] = lean >= 0 ? kLeanEntries[lean].mask : EPI_ANY;
     if (p.splits > 1 && !p.fold_acc) return launch_splitk_reduce(ctx, p, batch);
     return 0;
 }

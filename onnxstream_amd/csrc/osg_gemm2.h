@@ -1,5 +1,6 @@
 // libosgpu: the direct-to-LDS pipelined contraction kernel (gemm2_kernel) and its launcher, shared by the translation units that instantiate it -- each the
-// entries of osg_gemm_routes.h that v2_unit assigns to it (osg_gemm.hip, osg_gemm_wide.hip, osg_gemm_w8.hip, osg_gemm_w8_conv.hip).
+// entries of osg_gemm_routes.h that v2_unit assigns to it (osg_gemm.hip, osg_gemm_wide.hip, osg_gemm_w8.hip, osg_gemm_w8_conv.hip), and osg_gemm_lean.hip the
+// lean epilogue variants of osg_gemm_epi.h.
 #pragma once
 #include "osg_gemm_common.h"
 #include "osg_tune.h"
@@ -48,7 +49,9 @@ using namespace osg_mm;
 // exactly once.  A lane's fragment of a 32-deep half is ONE ds_read_b64 (8 codes: k = 32 ks + 8 (lane >> 4) .., the same k the A fragment holds) and 8 VALU
 // operations (osg_gemm_common.h w8_frag); the B stage is half as large, half the DMA requests, half the bytes through the LDS port per k-tile.  The accumulators
 // are scaled once, before any epilogue (w8_scale_acc): split-K slabs, GEGLU, statistics sinks see finished f32 values.  Not with LN (gamma folds into f16 weights).
-template <int BM, int BN, int NST, bool CONV, int MODE = 0, int SPEC = 0, int LN = 0, int NCH = 5, int KS = 1, int WGN = 2, int WQ = 0>
+// EPI (osg_gemm_epi.h): EPI_ANY = every decision of the epilogue at run time; a lean mask = exactly the named features, whole tiles, aligned rows, one unbatched
+// launch -- what the mask does not name is compiled out, here and in the shared epilogue (osg_gemm_common.h EPI_ON / EPI_ALWAYS / EPI_NEVER).  Same statements, same bits.
+template <int BM, int BN, int NST, bool CONV, int MODE = 0, int SPEC = 0, int LN = 0, int NCH = 5, int KS = 1, int WGN = 2, int WQ = 0, int EPI = EPI_ANY>
 __global__ __launch_bounds__((SPEC || KS == 2) ? 512 : 256) void gemm2_kernel(const void* A, const void* Bt, int M, int N, int K, int k_per_split, unsigned a_bytes, unsigned b_bytes,
                                                                               int grid, int lda, unsigned sp_nm, GemmParams pk) {
     // the tile mapping and the DMA addressing of both operands arrive in user SGPRs (kernel-argument preload, osg_gemm_common.h kernarg_pack): 13 dwords, no scalar
@@ -126,7 +129,7 @@ __global__ __launch_bounds__((SPEC || KS == 2) ? 512 : 256) void gemm2_kernel(co
 
     const f16* Ab = p.A;
     const f16* Bb = p.Bt;
-    if (OSG_UNLIKELY(sp_nm & kPackBatch)) {         // (an unbatched launch -- every GEMM of the UNet pass -- does not wait for the strides)
+    if (OSG_UNLIKELY(EPI_NEVER((sp_nm & kPackBatch) != 0))) {         // (an unbatched launch -- every GEMM of the UNet pass -- does not wait for the strides)
         Ab += (long)zb * kernarg_rare(pk.strideA);
         Bb += (long)zb * kernarg_rare(pk.strideB);
     }
@@ -142,16 +145,16 @@ __global__ __launch_bounds__((SPEC || KS == 2) ? 512 : 256) void gemm2_kernel(co
     for (int j = 0; j < A_LD; j++) {
         const int m = m0 + (j * 4 + wave) * 8 + rsub;
         if (CONV) {
-            const int mm = m < p.M ? m : 0;
+            const int mm = EPI_ALWAYS(m < p.M) ? m : 0;
             const int hw = p.Ho * p.Wo;
             const int n_img = mm / hw;
             const int r2 = mm - n_img * hw;
             const int ho = r2 / p.Wo, wo = r2 - ho * p.Wo;
-            a_hi0[j] = m < p.M ? ho * p.sh - p.pt : -0x40000000;
+            a_hi0[j] = EPI_ALWAYS(m < p.M) ? ho * p.sh - p.pt : -0x40000000;
             a_wi0[j] = wo * p.sw - p.pl;
             a_base[j] = (((n_img * p.H + (ho * p.sh - p.pt)) * p.W + (wo * p.sw - p.pl)) * p.Cin + gch * 8) * 2;
         } else {
-            a_base[j] = m < p.M ? (int)(((long)m * p.lda + gch * 8) * 2) : (int)OOB;
+            a_base[j] = EPI_ALWAYS(m < p.M) ? (int)(((long)m * p.lda + gch * 8) * 2) : (int)OOB;
             a_hi0[j] = a_wi0[j] = 0;
         }
     }
@@ -160,10 +163,10 @@ __global__ __launch_bounds__((SPEC || KS == 2) ? 512 : 256) void gemm2_kernel(co
     for (int j = 0; j < B_LD; j++) {
         if constexpr (WQ) {
             const int nl = (j * 4 + wave) * 16 + (lane >> 2), n = n0 + nl;
-            b_base[j] = (n < p.N && (BNP == BN || nl < BN)) ? (int)((long)n * p.K + (((lane & 3) ^ ((lane >> 4) & 3)) << 4)) : (int)OOB;
+            b_base[j] = (EPI_ALWAYS(n < p.N) && (BNP == BN || nl < BN)) ? (int)((long)n * p.K + (((lane & 3) ^ ((lane >> 4) & 3)) << 4)) : (int)OOB;
         } else {
             const int nl = (j * 4 + wave) * 8 + rsub, n = n0 + nl;
-            b_base[j] = (n < p.N && (BNP == BN || nl < BN)) ? (int)(((long)n * p.K + gch * 8) * 2) : (int)OOB;
+            b_base[j] = (EPI_ALWAYS(n < p.N) && (BNP == BN || nl < BN)) ? (int)(((long)n * p.K + gch * 8) * 2) : (int)OOB;
         }
     }
 
@@ -232,7 +235,8 @@ __global__ __launch_bounds__((SPEC || KS == 2) ? 512 : 256) void gemm2_kernel(co
         asm volatile("" ::: "memory");
     }
 
-    constexpr bool EPRE = TM * TN <= 8;    // (64x64 / 128x64 / 64x128 tiles; the 128x128 tile keeps its on-demand loads: no registers to spare)
+    // (64x64 / 128x64 / 64x128 tiles; the 128x128 tile keeps its on-demand loads: no registers to spare.  A lean variant: where its form always prefetches)
+    constexpr bool EPRE = EPI == EPI_ANY ? TM * TN <= 8 : epi_lean_prefetch(EPI, TM * TN <= 8, CONV, LN);
     W8Ops<WQ ? TN : 1, true> w8;
     if constexpr (WQ) { if (math) w8_prefetch<TN, true>(p, w8, n0, wn0, lane); }
     if (loads) {
@@ -249,7 +253,7 @@ __global__ __launch_bounds__((SPEC || KS == 2) ? 512 : 256) void gemm2_kernel(co
 #endif
     EpiOps<TM, TN, CONV, EPRE> epre;
     epre.have = false;
-    if (math && !p.ln_c1 && grp == 0) epi_prefetch<TM, TN, CONV, EPRE>(p, epre, m0, n0, wm0, wn0, lane, zb);
+    if (math && EPI_ALWAYS(!p.ln_c1) && grp == 0) epi_prefetch<TM, TN, CONV, EPRE, EPI>(p, epre, m0, n0, wm0, wn0, lane, zb);
     kdbg_stamp(p, 1);
     if constexpr (WQ) { if (math) w8_finalize<TN, true>(w8); }
 
@@ -329,18 +333,26 @@ __global__ __launch_bounds__((SPEC || KS == 2) ? 512 : 256) void gemm2_kernel(co
         }
     }
     if constexpr (LN != 0) ln_apply<TM, TN, LN == 1>(p, acc, ls, lq, n0, wn0, lane);
-    if (OSG_UNLIKELY_IF(!SPEC, p.act == OSG_ACT_GEGLU)) {
-        if constexpr (TN % 2 == 0) gemm_epilogue_geglu<TM, TN>(p, acc, m0, n0, wm0, wn0, lane, zb);
+    if constexpr (EPI != EPI_ANY && (LN != 0 || WQ != 0)) {
+        // EPI_ANY adds the bias behind a run-time branch, to the ROUNDED product rstd * (...) (uint8 codes: acc * scale).  With the branch settled at compile time the
+        // multiplication and the addition meet in one block, where the compiler would contract them into one fma -- one rounding less, other bits.  Keep them apart.
+#pragma unroll
+        for (int i = 0; i < TM; i++)
+#pragma unroll
+            for (int j = 0; j < TN; j++) asm volatile("" : "+v"(acc[i][j]));
+    }
+    if (OSG_UNLIKELY_IF(!SPEC, (EPI_ON(EPI_GEGLU, p.act == OSG_ACT_GEGLU)))) {
+        if constexpr (TN % 2 == 0) gemm_epilogue_geglu<TM, TN, EPI>(p, acc, m0, n0, wm0, wn0, lane, zb);
         return;
     }
     kdbg_stamp(p, 4);
     float* stat_lds = nullptr;
-    if (OSG_UNLIKELY_IF(!SPEC, p.sink[0].table || p.sink[1].table)) {   // (launch_v2 leaves the sinks set only where this epilogue can serve them: one k-slice, 4-aligned shapes)
+    if (OSG_UNLIKELY_IF(!SPEC, (EPI_ON(EPI_SINKS, p.sink[0].table || p.sink[1].table)))) {   // (launch_v2 leaves the sinks set only where this epilogue can serve them: one k-slice, 4-aligned shapes)
         __builtin_amdgcn_s_barrier();           // every wave is done with the ring: its first bytes become the waves' staging areas
         stat_lds = reinterpret_cast<float*>(smem2) + wave * (WN * 2);
     }
     if constexpr (KS == 1 && !SPEC && LN == 0 && MODE == 0) {
-        if (OSG_UNLIKELY_IF(!SPEC, p.splits > 1 && p.fold_acc)) {
+        if (OSG_UNLIKELY_IF(!SPEC, (EPI_ON(EPI_FOLD, p.splits > 1 && p.fold_acc)))) {
             // split-K, folded by the last workgroup to arrive at the tile (osg_gemm_common.h splitk_fold_acc): it then runs the fused epilogue of an unsplit launch
             if (!splitk_fold_acc<TM, TN>(p, acc, (zb * p.mt + m_tile) * p.nt + n_tile, zs, reinterpret_cast<int*>(smem2), tid)) return;
             EpiOps<TM, TN, CONV, false> none;
@@ -349,17 +361,17 @@ __global__ __launch_bounds__((SPEC || KS == 2) ? 512 : 256) void gemm2_kernel(co
             return;
         }
     }
-    gemm_epilogue<TM, TN, CONV, EPRE, !SPEC>(p, acc, m0, n0, wm0, wn0, lane, zb, zb * p.splits + zs, epre, stat_lds);   // (SPEC: 512 threads, 256 registers per lane -- the on-demand operands one block at a time)
+    gemm_epilogue<TM, TN, CONV, EPRE, !SPEC, EPI>(p, acc, m0, n0, wm0, wn0, lane, zb, zb * p.splits + zs, epre, stat_lds);   // (SPEC: 512 threads, 256 registers per lane -- the on-demand operands one block at a time)
     kdbg_stamp(p, 5);
     if (OSG_UNLIKELY_IF(!SPEC, p.kdbg != nullptr)) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); kdbg_stamp(p, 6); }
 }
 
-template <int BM, int BN, int NST, bool CONV, int MODE = 0, int SPEC = 0, int LN = 0, int NCH = 5, int KS = 1, int WGN = 2, int WQ = 0>
+template <int BM, int BN, int NST, bool CONV, int MODE = 0, int SPEC = 0, int LN = 0, int NCH = 5, int KS = 1, int WGN = 2, int WQ = 0, int EPI = EPI_ANY>
 int launch_v2(osg_ctx* ctx, GemmParams& p, int batch) {
     constexpr size_t smem = WQ ? (size_t)NST * KS * (BM * 128 + (BN + 63) / 64 * 64 * 64) : (size_t)NST * KS * (BM + (BN + 31) / 32 * 32) * 128;
     static_assert(smem <= 160 * 1024, "LDS budget");
     static_assert(KS == 1 || (size_t)4 * ((BM / 32) * (BN / 32) + 1) * 1024 <= smem, "KS = 2: the accumulator hand-over must fit the ring");
-    auto kern = gemm2_kernel<BM, BN, NST, CONV, MODE, SPEC, LN, NCH, KS, WGN, WQ>;
+    auto kern = gemm2_kernel<BM, BN, NST, CONV, MODE, SPEC, LN, NCH, KS, WGN, WQ, EPI>;
     static unsigned long long attr_mask = 0;   // (per device: hipFuncSetAttribute is, and a process may hold several)
     if (osg_first_on_device(attr_mask)) {
         OSG_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));

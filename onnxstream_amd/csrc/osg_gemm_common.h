@@ -4,6 +4,7 @@
 #include <vector>
 #include "osg_common.h"
 #include "osg_gemm_select.h"
+#include "osg_gemm_epi.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -139,6 +140,20 @@ inline int kernarg_pack(osg_ctx* ctx, long lda, int splits, int n_major, bool kd
 #define OSG_UNLIKELY(x) __builtin_expect(!!(x), 0)
 // (h = false: no hint -- the 512- / 768-thread kernels, whose 256 / 168 registers per lane spill under a different block order)
 #define OSG_UNLIKELY_IF(h, x) ((h) ? __builtin_expect(!!(x), 0) : !!(x))
+// ---- the EPI template argument of the epilogue (osg_gemm_epi.h).  Every uniform decision of the epilogue goes through one of these, inside a template that has EPI:
+// with EPI_ANY it is the run-time expression, token for token what it always was (a conditional on a constant: the compiler emits the live arm only, so the EPI_ANY
+// instantiations are the code they were); a lean mask settles it at compile time -- EPI_ON / EPI_OFF: the feature is there exactly when the mask names it; EPI_ALWAYS /
+// EPI_NEVER: a bound or a rare case that whole, aligned tiles of an unbatched launch make true / false; EPI_CLAMP: an address clamp such tiles never need;
+// EPI_ACT: the one activation a lean mask names.  The statements the decisions guard are the same for every EPI.
+#define EPI_ON(bits, x) (EPI == EPI_ANY ? (x) : ((EPI & (bits)) != 0))
+#define EPI_OFF(bits, x) (EPI == EPI_ANY ? (x) : ((EPI & (bits)) == 0))
+#define EPI_ALWAYS(x) (EPI == EPI_ANY ? (x) : true)
+#define EPI_NEVER(x) (EPI == EPI_ANY ? (x) : false)
+#define EPI_CLAMP(v, hi) (EPI == EPI_ANY ? min(v, hi) : (v))
+#define EPI_ACT(a) (EPI == EPI_ANY ? (int)(a) : (int)OSG_ACT_SILU)
+// does a lean variant fetch its epilogue operands before the k loop (epi_prefetch)?  Where the run-time rule of EPI_ANY always says yes for the form: a tile with
+// registers to spare (on), no folded LayerNorm, no split, a per-image bias only in the convolution kernels
+constexpr bool epi_lean_prefetch(int epi, bool on, bool conv, int ln) { return on && ln == 0 && !(epi & (EPI_SPLIT | EPI_FOLD | EPI_GEGLU)) && (conv || !(epi & EPI_ROWBIAS)); }
 
 // ---- W8A16: uint8 weight codes resident in HBM, dequantised between the LDS tile and the MFMA (round 6) ----------------------------------------------------
 // The [BN][64] weight tile travels HBM -> L2 -> LDS as CODES (half the bytes of the f16 tile on every hop, and half the bytes through the LDS port the k loop is
@@ -280,31 +295,31 @@ struct EpiOps {
     f16x4 rb[ON && RB ? TM : 1][ON && RB ? TN : 1];
     f16x4 res[ON ? TM : 1][ON ? TN : 1];
 };
-template <int TM, int TN, bool RB, bool ON>
+template <int TM, int TN, bool RB, bool ON, int EPI = EPI_ANY>
 __device__ __forceinline__ void epi_prefetch(const GemmParams& p, EpiOps<TM, TN, RB, ON>& e, int m0, int n0, int wm0, int wn0, int lane, int zb) {
     const int N = p.N;
-    e.have = ON && !p.no_epre && p.splits == 1 && (N & 3) == 0 && p.act != OSG_ACT_GEGLU && N >= 4 && (RB || !p.rowbias);
+    e.have = ON && EPI_ALWAYS(!p.no_epre && p.splits == 1 && (N & 3) == 0 && p.act != OSG_ACT_GEGLU && N >= 4 && (RB || !p.rowbias));   // (lean: ON is epi_lean_prefetch)
     if constexpr (!ON) return;
     if (__builtin_expect(!e.have, 0)) return;
-    const f16* __restrict__ R = p.residual ? p.residual + zb * p.strideC : nullptr;
+    const f16* __restrict__ R = EPI_ON(EPI_RESIDUAL, p.residual != nullptr) ? p.residual + zb * p.strideC : nullptr;
 #pragma unroll
     for (int j = 0; j < TN; j++) {
-        const int n = min(n0 + wn0 + j * 16 + (lane >> 4) * 4, N - 4);
-        if (p.bias) {
-            if (p.bias_f32) e.bias32[j] = *reinterpret_cast<const f32x4*>((const float*)p.bias + n);
+        const int n = EPI_CLAMP(n0 + wn0 + j * 16 + (lane >> 4) * 4, N - 4);
+        if (EPI_ON(EPI_BIAS16 | EPI_BIAS32, p.bias != nullptr)) {
+            if (EPI_ON(EPI_BIAS32, p.bias_f32 != 0)) e.bias32[j] = *reinterpret_cast<const f32x4*>((const float*)p.bias + n);
             else e.bias16[j] = *reinterpret_cast<const f16x4*>((const f16*)p.bias + n);
         }
     }
 #pragma unroll
     for (int i = 0; i < TM; i++) {
-        const int m = min(m0 + wm0 + i * 16 + (lane & 15), p.M - 1);
+        const int m = EPI_CLAMP(m0 + wm0 + i * 16 + (lane & 15), p.M - 1);
 #pragma unroll
         for (int j = 0; j < TN; j++) {
-            const int n = min(n0 + wn0 + j * 16 + (lane >> 4) * 4, N - 4);
+            const int n = EPI_CLAMP(n0 + wn0 + j * 16 + (lane >> 4) * 4, N - 4);
             if constexpr (RB) {
-                if (p.rowbias) e.rb[i][j] = *reinterpret_cast<const f16x4*>(p.rowbias + (long)(m / p.rb_rows) * p.rb_ld + n);
+                if (EPI_ON(EPI_ROWBIAS, p.rowbias != nullptr)) e.rb[i][j] = *reinterpret_cast<const f16x4*>(p.rowbias + (long)(m / p.rb_rows) * p.rb_ld + n);
             }
-            if (R) e.res[i][j] = *reinterpret_cast<const f16x4*>(R + (long)m * N + n);
+            if (EPI_ON(EPI_RESIDUAL, R != nullptr)) e.res[i][j] = *reinterpret_cast<const f16x4*>(R + (long)m * N + n);
         }
     }
     asm volatile("" ::: "memory");
@@ -419,23 +434,23 @@ inline int epi_check(osg_ctx* ctx, GemmParams& p) {
     return 0;
 }
 
-template <int TM, int TN, bool RB, bool ON, bool BATCH = true>
+template <int TM, int TN, bool RB, bool ON, bool BATCH = true, int EPI = EPI_ANY>
 __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&acc)[TM][TN], int m0, int n0, int wm0, int wn0, int lane, int zb,
                                                    const EpiOps<TM, TN, RB, ON>& pre, float* stat_lds = nullptr) {
     // every uniform decision (which operands exist, which activation, a second destination) is taken ONCE, around a whole loop over the wave's tiles --
     // inside the unrolled loops the compiler would clone the tile code for every combination of them
     const int N = p.N;
     f16* __restrict__ C = p.C + zb * p.strideC;
-    const f16* __restrict__ R = p.residual ? p.residual + zb * p.strideC : nullptr;
+    const f16* __restrict__ R = EPI_ON(EPI_RESIDUAL, p.residual != nullptr) ? p.residual + zb * p.strideC : nullptr;
     const long ldc = p.ldc ? p.ldc : (long)N;
     const int nb = n0 + wn0 + (lane >> 4) * 4;
     const int mb = m0 + wm0 + (lane & 15);
     bool done = false;
     if constexpr (ON) {
-        if (pre.have) {
+        if (EPI_ALWAYS(pre.have)) {   // (lean: ON is epi_lean_prefetch)
             done = true;
-            if (p.bias) {
-                if (p.bias_f32) {
+            if (EPI_ON(EPI_BIAS16 | EPI_BIAS32, p.bias != nullptr)) {
+                if (EPI_ON(EPI_BIAS32, p.bias_f32 != 0)) {
 #pragma unroll
                     for (int i = 0; i < TM; i++)
 #pragma unroll
@@ -450,7 +465,7 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
                 }
             }
             if constexpr (RB) {
-                if (p.rowbias) {
+                if (EPI_ON(EPI_ROWBIAS, p.rowbias != nullptr)) {
 #pragma unroll
                     for (int i = 0; i < TM; i++)
 #pragma unroll
@@ -459,7 +474,7 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
                             for (int r = 0; r < 4; r++) acc[i][j][r] += (float)pre.rb[i][j][r];
                 }
             }
-            if (R) {
+            if (EPI_ON(EPI_RESIDUAL, R != nullptr)) {
 #pragma unroll
                 for (int i = 0; i < TM; i++)
 #pragma unroll
@@ -475,7 +490,8 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
         // if (R) ...` each operand was waited for at the end of its block, three dependent trips to memory in a row on the critical path of the launch.  Same bits.
         // Through buffer descriptors: an absent operand gets an EMPTY descriptor (every load returns 0, no memory traffic), rows / columns outside the matrix are out of
         // range, and the TN blocks of a row are one address register + immediate offsets.
-        const bool hb32 = p.bias && p.bias_f32, hb16 = p.bias && !p.bias_f32, hrb = p.rowbias != nullptr, hres = R != nullptr;
+        const bool hb32 = EPI_ON(EPI_BIAS32, p.bias && p.bias_f32), hb16 = EPI_ON(EPI_BIAS16, p.bias && !p.bias_f32), hrb = EPI_ON(EPI_ROWBIAS, p.rowbias != nullptr),
+                   hres = EPI_ON(EPI_RESIDUAL, R != nullptr);
         typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         const unsigned nbytes = (unsigned)N * 2u;
@@ -544,7 +560,7 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
 #pragma unroll
                         for (int r = 0; r < 4; r++) {
                             float x = acc[i0 + ii][j0 + jj][r];
-                            x += p.bias ? (hb32 ? b32[j0 + jj][r] : (float)b16[j0 + jj][r]) : -0.0f;
+                            x += EPI_ON(EPI_BIAS16 | EPI_BIAS32, p.bias != nullptr) ? (hb32 ? b32[j0 + jj][r] : (float)b16[j0 + jj][r]) : -0.0f;
                             x += hrb ? (float)rbv[ii][jj][r] : -0.0f;
                             x += hres ? (float)rsv[ii][jj][r] : -0.0f;
                             acc[i0 + ii][j0 + jj][r] = x;
@@ -553,12 +569,12 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
         }
     }
     if constexpr (!BATCH) if (!done) {   // (the 512- / 768-thread halo convolution: 256 / 168 registers per lane, no room for the batch) operands on demand (clamped addresses: the loads are unconditional, the stores below are not)
-        if (p.bias) {
+        if (EPI_ON(EPI_BIAS16 | EPI_BIAS32, p.bias != nullptr)) {
 #pragma unroll
             for (int j = 0; j < TN; j++) {
                 const int n = min(nb + j * 16, N - 4);
                 f32x4 bv;
-                if (p.bias_f32) bv = *reinterpret_cast<const f32x4*>((const float*)p.bias + n);
+                if (EPI_ON(EPI_BIAS32, p.bias_f32 != 0)) bv = *reinterpret_cast<const f32x4*>((const float*)p.bias + n);
                 else {
                     const f16x4 b16 = *reinterpret_cast<const f16x4*>((const f16*)p.bias + n);
 #pragma unroll
@@ -568,7 +584,7 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
                 for (int i = 0; i < TM; i++) acc[i][j] += bv;
             }
         }
-        if (p.rowbias) {
+        if (EPI_ON(EPI_ROWBIAS, p.rowbias != nullptr)) {
 #pragma unroll
             for (int i = 0; i < TM; i++) {
                 const long ro = (long)(min(mb + i * 16, p.M - 1) / p.rb_rows) * p.rb_ld;
@@ -580,7 +596,7 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
                 }
             }
         }
-        if (R) {
+        if (EPI_ON(EPI_RESIDUAL, R != nullptr)) {
 #pragma unroll
             for (int i = 0; i < TM; i++) {
                 const long ro = (long)min(mb + i * 16, p.M - 1) * N;
@@ -593,8 +609,8 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
             }
         }
     }
-    if (OSG_UNLIKELY_IF(BATCH, p.act != OSG_ACT_NONE)) {
-        const int act = p.act;
+    if (OSG_UNLIKELY_IF(BATCH, (EPI_ON(EPI_SILU, p.act != OSG_ACT_NONE)))) {
+        const int act = EPI_ACT(p.act);
 #pragma unroll
         for (int i = 0; i < TM; i++)
 #pragma unroll
@@ -624,11 +640,11 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
 #pragma unroll
             for (int j = 0; j < TN; j++) {
                 const int n = nb + j * 16;
-                const unsigned off = (r < rows_left && n < N) ? ((unsigned)r * (unsigned)ldc + (unsigned)n) * 2u : kEpiOob;
+                const unsigned off = EPI_ALWAYS(r < rows_left && n < N) ? ((unsigned)r * (unsigned)ldc + (unsigned)n) * 2u : kEpiOob;
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o[i][j]), rsC, off, 0, OSG_EPI_STORE_AUX);
             }
         }
-        if (OSG_UNLIKELY_IF(BATCH, p.C2 != nullptr)) {
+        if (OSG_UNLIKELY_IF(BATCH, (EPI_ON(EPI_C2, p.C2 != nullptr)))) {
             __amdgpu_buffer_rsrc_t rsC2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.C2 + (long)m0 * p.ldc2), 0, epi_extent(rows_left, p.ldc2, N), 0x00020000);
 #pragma unroll
             for (int i = 0; i < TM; i++) {
@@ -636,7 +652,7 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
 #pragma unroll
                 for (int j = 0; j < TN; j++) {
                     const int n = nb + j * 16;
-                    const unsigned off = (r < rows_left && n < N) ? ((unsigned)r * (unsigned)p.ldc2 + (unsigned)n) * 2u : kEpiOob;
+                    const unsigned off = EPI_ALWAYS(r < rows_left && n < N) ? ((unsigned)r * (unsigned)p.ldc2 + (unsigned)n) * 2u : kEpiOob;
                     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, o[i][j]), rsC2, off, 0, OSG_EPI_STORE_AUX);
                 }
             }
@@ -665,21 +681,21 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
         }
     }
 #endif
-    if (OSG_UNLIKELY_IF(BATCH, stat_lds != nullptr)) gemm_colstats<TM, TN>(p, o, m0 + wm0, n0 + wn0, lane, stat_lds);
-    if (OSG_UNLIKELY_IF(BATCH, p.rs_out != nullptr)) {
+    if (OSG_UNLIKELY_IF(BATCH, (EPI_ON(EPI_SINKS, stat_lds != nullptr)))) gemm_colstats<TM, TN>(p, o, m0 + wm0, n0 + wn0, lane, stat_lds);
+    if (OSG_UNLIKELY_IF(BATCH, (EPI_ON(EPI_ROWSTATS, p.rs_out != nullptr)))) {
         // osg_gemm_rowstats: sums over this wave's 32-column slots of every row, of the ROUNDED outputs.  The four 16-lane groups of a row hold
         // different columns of the same slot pair: 2-step butterfly, one lane group stores
 #pragma unroll
         for (int i = 0; i < TM; i++) {
             const int m = mb + i * 16;
-            if (m >= p.M) continue;
+            if (!EPI_ALWAYS(m < p.M)) continue;
 #pragma unroll
             for (int h = 0; h < TN / 2; h++) {
                 float s = 0.f, q = 0.f;
 #pragma unroll
                 for (int jj = 0; jj < 2; jj++) {
                     const int j = 2 * h + jj;
-                    if (nb + j * 16 < N) {
+                    if (EPI_ALWAYS(nb + j * 16 < N)) {
 #pragma unroll
                         for (int r = 0; r < 4; r++) {
                             const float f = (float)o[i][j][r];
@@ -691,7 +707,7 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
                 s += __shfl_xor(s, 16, 64); q += __shfl_xor(q, 16, 64);
                 s += __shfl_xor(s, 32, 64); q += __shfl_xor(q, 32, 64);
                 const int slot = ((n0 + wn0) >> 5) + h;
-                if ((lane >> 4) == 0 && slot < p.rs_np) {
+                if ((lane >> 4) == 0 && EPI_ALWAYS(slot < p.rs_np)) {
                     float* d = p.rs_out + ((long)m * p.rs_np + slot) * 2;
                     d[0] = s;
                     d[1] = q;
@@ -701,13 +717,13 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmParams& p, f32x4 (&
     }
 }
 
-template <int TM, int TN, bool RB, bool ON, bool BATCH = true>
+template <int TM, int TN, bool RB, bool ON, bool BATCH = true, int EPI = EPI_ANY>
 __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[TM][TN], int m0, int n0, int wm0, int wn0, int lane,
                                               int zb, int zslab, const EpiOps<TM, TN, RB, ON>& pre, float* stat_lds = nullptr) {
     const int N = p.N;
-    if (OSG_LIKELY(p.splits == 1)) {
-        if (OSG_LIKELY((N & 3) == 0 && ((p.ldc | p.ldc2) & 3) == 0)) {   // every 4-aligned shape: compact code (see gemm_epilogue_fast)
-            gemm_epilogue_fast<TM, TN, RB, ON, BATCH>(p, acc, m0, n0, wm0, wn0, lane, zb, pre, stat_lds);
+    if (OSG_LIKELY(EPI_OFF(EPI_SPLIT, p.splits == 1))) {
+        if (OSG_LIKELY(EPI_ALWAYS((N & 3) == 0 && ((p.ldc | p.ldc2) & 3) == 0))) {   // every 4-aligned shape: compact code (see gemm_epilogue_fast)
+            gemm_epilogue_fast<TM, TN, RB, ON, BATCH, EPI>(p, acc, m0, n0, wm0, wn0, lane, zb, pre, stat_lds);
             return;
         }
         // ragged N (conv_out's 3 / 4 channels, odd test shapes): element by element
@@ -741,12 +757,12 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
 #pragma unroll
         for (int i = 0; i < TM; i++) {
             const int m = m0 + wm0 + i * 16 + (lane & 15);
-            if (m >= p.M) continue;
+            if (!EPI_ALWAYS(m < p.M)) continue;
 #pragma unroll
             for (int j = 0; j < TN; j++) {
                 const int n = n0 + wn0 + j * 16 + (lane >> 4) * 4;
-                if (n >= N) continue;
-                if ((N & 3) == 0) {
+                if (!EPI_ALWAYS(n < N)) continue;
+                if (EPI_ALWAYS((N & 3) == 0)) {
                     *reinterpret_cast<f32x4*>(P + (long)m * N + n) = acc[i][j];
                 } else {
 #pragma unroll
@@ -769,7 +785,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmParams& p, f32x4 (&acc)[
 // ---- fused GEGLU epilogue (act == OSG_ACT_GEGLU): the weight rows were pair-interleaved in blocks of 16 at plan time, so MFMA
 // tile 2j holds 16 "value" columns and tile 2j+1 the matching 16 "gate" columns; out[m][c] = (v + bv) * gelu_erf(g + bg), written
 // to a [M, N/2] matrix.  Replaces Add(bias) + Slice,Slice,Div,Erf,Add,Mul,Mul,Mul (reference src/onnxstream.cpp:6499,4001,...).
-template <int TM, int TN>
+template <int TM, int TN, int EPI = EPI_ANY>
 __device__ __forceinline__ void gemm_epilogue_geglu(const GemmParams& p, f32x4 (&acc)[TM][TN], int m0, int n0, int wm0, int wn0, int lane,
                                                     int zb) {
     static_assert(TN % 2 == 0, "GEGLU epilogue needs value/gate tile pairs");
@@ -777,29 +793,29 @@ __device__ __forceinline__ void gemm_epilogue_geglu(const GemmParams& p, f32x4 (
     f16* __restrict__ C = p.C + zb * p.strideC;
     // round 6: the bias of the wave's TN column blocks by ONE vector load each, all in flight together (rounds 1-5: eight 2-byte loads per output quad, on demand);
     // unconditional and clamped, an absent bias reads A and enters as -0.0 (the exact neutral element): same sums, same bits
-    const bool hb32 = p.bias && p.bias_f32, hb16 = p.bias && !p.bias_f32;
+    const bool hb32 = EPI_ON(EPI_BIAS32, p.bias && p.bias_f32), hb16 = EPI_ON(EPI_BIAS16, p.bias && !p.bias_f32);
     f32x4 b32[TN];
     f16x4 b16[TN];
 #pragma unroll
     for (int j = 0; j < TN; j++) {
-        const int n = min(n0 + wn0 + j * 16 + (lane >> 4) * 4, p.N - 4);
+        const int n = EPI_CLAMP(n0 + wn0 + j * 16 + (lane >> 4) * 4, p.N - 4);
         b32[j] = *reinterpret_cast<const f32x4*>(hb32 ? (const float*)p.bias + n : (const float*)p.A);
         b16[j] = *reinterpret_cast<const f16x4*>(hb16 ? (const f16*)p.bias + n : p.A);
     }
 #pragma unroll
     for (int i = 0; i < TM; i++) {
         const int m = m0 + wm0 + i * 16 + (lane & 15);
-        if (m >= p.M) continue;
+        if (EPI_NEVER(m >= p.M)) continue;
 #pragma unroll
         for (int j = 0; j < TN; j += 2) {
             const int n = n0 + wn0 + j * 16 + (lane >> 4) * 4;      // column of the value tile in the interleaved space
-            if (n >= p.N) continue;
+            if (EPI_NEVER(n >= p.N)) continue;
             const int c = ((n0 + wn0 + j * 16) >> 1) + (lane >> 4) * 4;   // output column
             f16x4 o;
 #pragma unroll
             for (int r = 0; r < 4; r++) {
-                const float v = acc[i][j][r] + (p.bias ? (hb32 ? b32[j][r] : (float)b16[j][r]) : -0.0f);
-                const float g = acc[i][j + 1][r] + (p.bias ? (hb32 ? b32[j + 1][r] : (float)b16[j + 1][r]) : -0.0f);
+                const float v = acc[i][j][r] + (EPI_ON(EPI_BIAS16 | EPI_BIAS32, p.bias != nullptr) ? (hb32 ? b32[j][r] : (float)b16[j][r]) : -0.0f);
+                const float g = acc[i][j + 1][r] + (EPI_ON(EPI_BIAS16 | EPI_BIAS32, p.bias != nullptr) ? (hb32 ? b32[j + 1][r] : (float)b16[j + 1][r]) : -0.0f);
                 o[r] = (f16)(v * osg_gelu_erf(g));
             }
             *reinterpret_cast<f16x4*>(C + (long)m * No + c) = o;
@@ -898,6 +914,24 @@ __device__ __forceinline__ bool splitk_fold_acc(const GemmParams& p, f32x4 (&acc
 }
 
 int launch_splitk_reduce(osg_ctx* ctx, const GemmParams& p, int batch);   // osg_gemm.hip
+inline int no_epi_prefetch();
+// what select_epi (osg_gemm_epi.h) reads of a launch: p as launch_v2_choice hands it to the kernel's launcher (k-slices and fold decided)
+inline EpiLaunch epi_launch_of(const GemmParams& p, int batch) {
+    EpiLaunch l;
+    l.M = p.M; l.N = p.N; l.batch = batch; l.splits = p.splits; l.fold = p.fold_acc != 0;
+    l.bias = p.bias != nullptr; l.bias_f32 = p.bias_f32 != 0; l.rowbias = p.rowbias != nullptr; l.residual = p.residual != nullptr; l.c2 = p.C2 != nullptr;
+    l.rowstats = p.rs_out != nullptr; l.sinks = p.sink[0].table || p.sink[1].table; l.act = (int)p.act;
+    l.other = no_epi_prefetch() != 0;
+    l.ldc = p.ldc; l.ldc2 = p.C2 ? p.ldc2 : 0; l.rb_ld = p.rb_ld; l.rs_np = p.rs_np;
+    l.align_or = (uintptr_t)p.C | (uintptr_t)p.C2 | (uintptr_t)p.residual | (uintptr_t)p.rowbias | (uintptr_t)p.bias | (uintptr_t)p.rs_out;
+    return l;
+}
+// OSG_EPI_GENERIC=1 (A/B, read per call): every launch runs the EPI_ANY instantiation of its entry
+inline bool epi_generic_forced() {
+    const char* e = getenv("OSG_EPI_GENERIC");
+    return e && atoi(e) != 0;
+}
+int launch_v2_lean(int lean, osg_ctx* ctx, GemmParams& p, int batch);     // osg_gemm_lean.hip: entry `lean` of kLeanEntries
 // launch entry `entry` of kV2Entries / kV3Entries (osg_gemm_routes.h): defined by the translation unit v2_unit / v3_unit names, which instantiates its entries
 template <int UNIT> int launch_v2_unit(int entry, osg_ctx* ctx, GemmParams& p, int batch);
 template <> int launch_v2_unit<0>(int entry, osg_ctx* ctx, GemmParams& p, int batch);   // osg_gemm.hip

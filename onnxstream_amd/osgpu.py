@@ -24,7 +24,7 @@ EXPORTS = [
     "osg_device_count", "osg_init", "osg_destroy", "osg_last_error", "osg_device_name", "osg_stream", "osg_set_autotune", "osg_tune_misses",
     "osg_malloc", "osg_free", "osg_upload", "osg_upload_sync", "osg_host_register", "osg_host_unregister", "osg_upload_pinned", "osg_upload_pinned_async", "osg_copy_fence", "osg_download", "osg_copy", "osg_memset", "osg_sync",
     "osg_graph_begin", "osg_graph_end", "osg_graph_launch", "osg_graph_destroy", "osg_timer_start", "osg_timer_stop",
-    "osg_conv2d_nhwc", "osg_conv2d_nhwc_rb", "osg_conv2d_nhwc_v", "osg_gemm", "osg_gemm_ln", "osg_gemm_rowstats", "osg_last_route", "osg_last_kernel", "osg_gemm_kernarg_check", "osg_attention_kernarg_check", "osg_gemm_w8", "osg_conv2d_nhwc_w8", "osg_gemm_w8_v", "osg_conv2d_nhwc_w8_v", "osg_transpose_kn_to_nk", "osg_attention", "osg_attention_strided", "osg_sdpa", "osg_rms_norm", "osg_rope",
+    "osg_conv2d_nhwc", "osg_conv2d_nhwc_rb", "osg_conv2d_nhwc_v", "osg_gemm", "osg_gemm_ln", "osg_gemm_rowstats", "osg_last_route", "osg_last_epilogue", "osg_last_kernel", "osg_gemm_kernarg_check", "osg_attention_kernarg_check", "osg_gemm_w8", "osg_conv2d_nhwc_w8", "osg_gemm_w8_v", "osg_conv2d_nhwc_w8_v", "osg_transpose_kn_to_nk", "osg_attention", "osg_attention_strided", "osg_sdpa", "osg_rms_norm", "osg_rope",
     "osg_instance_norm", "osg_group_norm_nhwc", "osg_layer_norm", "osg_reduce_mean_last", "osg_softmax_last",
     "osg_unary", "osg_binary", "osg_geglu", "osg_transpose", "osg_copy_2d", "osg_concat2", "osg_resize_nearest", "osg_gather_rows",
     "osg_maxpool_nhwc", "osg_convert", "osg_sampler_prepare", "osg_sampler_cfg_euler_a", "osg_sampler_cfg_multistep", "osg_sampler_prepare_rescale",
@@ -112,6 +112,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.osg_gemm_rowstats.argtypes = [vp, vp, vp, vp, ci, vp, vp, ci, ci, ci, ci, vp]
     lib.osg_last_route.argtypes = [vp, ctypes.POINTER(ci)]
     lib.osg_last_kernel.argtypes = [vp, ctypes.POINTER(ci)]
+    if hasattr(lib, "osg_last_epilogue"):          # (absent from a library of an older tree that OSGPU_LIB names in an A/B run)
+        lib.osg_last_epilogue.argtypes = [vp, ctypes.POINTER(ci)]
     if hasattr(lib, "osg_gemm_kernarg_check"):     # (absent from a library of an older tree that OSGPU_LIB names in an A/B run)
         lib.osg_gemm_kernarg_check.argtypes = [vp, cl, ci]
         lib.osg_attention_kernarg_check.argtypes = [vp, cl, ci, ci]
@@ -234,6 +236,12 @@ class Gpu:
         """osg_last_route: (family, instantiation, k-slices, folded, reduce kernel) of the most recent contraction call"""
         r = (ctypes.c_int * 5)()
         self._ck(self.lib.osg_last_route(self.ctx, r))
+        return tuple(r)
+
+    def last_epilogue(self):
+        """osg_last_epilogue: (lean instantiation or -1, EPI mask or -1) of the most recent gemm2_kernel launch"""
+        r = (ctypes.c_int * 2)()
+        self._ck(self.lib.osg_last_epilogue(self.ctx, r))
         return tuple(r)
 
     def last_kernel(self):
