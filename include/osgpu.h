@@ -419,6 +419,38 @@ int osg_sampler_euler_a_single(osg_ctx* ctx, float* x, const float* eps, const f
 int osg_sampler_multistep_single(osg_ctx* ctx, int form, float* x, const float* eps, float* h0, const float* h1, const float* h2, const float* h3,
                                  int prompts, long L, float c_out, float sigma, float k0, float k1, float k2, float k3, float k4, double da,
                                  double db);
+/* The update forms of osg_sampler_cfg_stochastic: the one-evaluation samplers of src/samplers.h that add fresh noise per step (the
+ * ORIGINAL_SAMPLER_ALGORITHMS branch).  den as in osg_sampler_cfg_euler_a; k0..k6 are the step's scalars (the reference's per-element std::sqrt /
+ * std::exp / std::log calls act on scalars: the host hoists them with the same expression tree, each operation rounded to float); history holds den:
+ *   LINEAR  x' = (x*k0) + (den*k1)                                               DDPM / DDPM-a (src/samplers.h:1050-1051, :1059: k0 = a, k1 = b)
+ *   DEN     x' = den                                                             LCM (:1411, :1421); DPM++ 3M SDE at si1 == 0 (:443)
+ *   EULER   x' = x + (((x - den) / sigma) * k0)                                  the reference's SDXL last-step rule for DPM++ 3M SDE (src/sd.cpp:1711-1716,
+ *                                                                                src/samplers.h:125: k0 = si1 - sigma_i); OSG_MS_EULER_D without the history store
+ *   DDIM_A  mo = ((k0 + x) - den) / sigma;  po = ((x*k1) - (mo*k2)) / k1;        DDIM-a (:1123-1129: k0 = autozero, k1 = sqrt(alpha_t), k2 = sqrt(beta_t),
+ *           x' = (k3*po) + (mo*k4)                                               k3 = sqrt(alpha_prev), k4 = sqrt(1 - alpha_prev - variance*eta*eta))
+ *   TCD     mo = (x - den) / sigma;  po = x - (k0*mo);  x' = (k1*po) + (k2*mo)   TCD / TCD-a (:1190-1192: k0 = sqrt(beta)/sqrt(alpha), k1 = sqrt(alpha_s),
+ *                                                                                k2 = sqrt(beta_s))
+ *   SDE0    h0 = den;  x' = (k0*x) - (k1*den)                                    DPM++ 3M SDE, step 0 (:470-472: k0 = exp(-h_eta), k1 = expm1(-h_eta))
+ *   SDE1    SDE0, then x' = x' + (k3*((den - h1) / k2))                          step 1 (:461-468: k2 = r, k3 = phi_2)
+ *   SDE2    SDE0, then d10 = (den - h1)/k2;  d11 = (h1 - h2)/k3;  df = d10 - d11;  d1 = d10 + ((df*k2)/k4);  d2 = df/k4;
+ *           x' = x' + ((k5*d1) - (k6*d2))                                        steps >= 2 (:446-459: k2 = r, k3 = r2, k4 = r + r2, k5 = phi_2, k6 = phi_3)
+ * and then, only with noise != NULL, the reference's noise add:  x = x' + (noise*n0)  (:1071, :1154, :537, :1421);  TCD: x = (n1*x') + (n0*noise)  (:1219). */
+typedef enum {
+    OSG_ST_LINEAR = 0, OSG_ST_DEN = 1, OSG_ST_EULER = 2, OSG_ST_DDIM_A = 3, OSG_ST_TCD = 4, OSG_ST_SDE0 = 5, OSG_ST_SDE1 = 6, OSG_ST_SDE2 = 7,
+    OSG_ST_FORMS = 8
+} osg_stochastic_form;
+/* One such step with the CFG combine (src/sd.cpp:1545-1556), in place on x:[prompts,L]; eps:[2*prompts,L]; noise:[prompts,L] or NULL (the step draws
+ * none); h0..h2:[prompts,L], distinct buffers (NULL where the form does not touch them; an unknown form or a missing pointer fails).  fp32, every
+ * product, sum and IEEE division rounded separately, i.e. bit-identical to the host loop (src/samplers.h:1039-1076, :1102-1158, :1160-1223,
+ * :1406-1428, :412-541). */
+int osg_sampler_cfg_stochastic(osg_ctx* ctx, int form, float* x, const float* eps, const float* noise, float* h0, const float* h1, const float* h2,
+                               int prompts, long L, float c_out, float guidance, float sigma, float k0, float k1, float k2, float k3, float k4, float k5,
+                               float k6, float n0, float n1);
+/* The same without the guidance pair (Turbo mode, src/sd.cpp:1537-1541): den = eps[p]*c_out + x, eps:[prompts,L]; the same samplers of
+ * src/samplers.h:1039-1076, :1102-1158, :1160-1223, :1406-1428, :412-541. */
+int osg_sampler_stochastic_single(osg_ctx* ctx, int form, float* x, const float* eps, const float* noise, float* h0, const float* h1, const float* h2,
+                                  int prompts, long L, float c_out, float sigma, float k0, float k1, float k2, float k3, float k4, float k5, float k6,
+                                  float n0, float n1);
 
 /* ---- latents -> image on the device: what surrounds the VAE decoder pass ------------------------------------------ */
 /* The tile grid both entry points share (Txt2Img.decode_tiled, after sd_tiled_decoder src/sd.cpp:1258-1346): along an axis of n latent pixels the

@@ -277,6 +277,44 @@ class Model:
                     dcoef.size, ctypes.byref(ms)))
         return ms.value
 
+    def _sampler_loop_stochastic(self, fname: str, sample: str, timestep: str, out: str, x, c_in, c_out, t, sigma, form, draws, coef, noise, guidance):
+        import numpy as np
+        f = getattr(self._lib, "model_" + fname)
+        fp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)
+        f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, ip, ip, fp,
+                      ctypes.c_ulonglong, fp] + ([ctypes.c_float] if guidance is not None else []) + [ctypes.POINTER(ctypes.c_double)]
+        f.restype = ctypes.c_void_p
+        assert x.dtype == np.float32 and x.flags.c_contiguous
+        arrs = [np.ascontiguousarray(a, np.float32) for a in (c_in, c_out, t, sigma)]
+        steps = len(arrs[0])
+        if any(len(a) != steps for a in arrs) or len(form) != steps or len(draws) != steps:
+            raise OnnxStreamError(f"{fname}: c_in, c_out, t, sigma, form and draws need one entry per step")
+        form, draws = np.ascontiguousarray(form, np.int32), np.ascontiguousarray(draws, np.int32)
+        coef = np.ascontiguousarray(coef, np.float32)
+        if noise is not None:
+            noise = np.ascontiguousarray(noise, np.float32)
+            if noise.size != steps * x.size:
+                raise OnnxStreamError(f"{fname}: noise must hold steps * x.size floats")
+        ms = ctypes.c_double(0)
+        self._err(f(self._h, self._name(sample), self._name(timestep), self._name(out), steps, x.shape[0], x.ctypes.data_as(fp),
+                    *[a.ctypes.data_as(fp) for a in arrs], form.ctypes.data_as(ip), draws.ctypes.data_as(ip), coef.ctypes.data_as(fp), coef.size,
+                    noise.ctypes.data_as(fp) if noise is not None else None, *([guidance] if guidance is not None else []), ctypes.byref(ms)))
+        return ms.value
+
+    def hip_sampler_loop_stochastic(self, sample: str, timestep: str, out: str, x, c_in, c_out, t, sigma, form, draws, coef, noise=None,
+                                    guidance: float = 7.0) -> float:
+        """The denoising loop with a one-evaluation sampler that adds fresh noise per step (DDPM(-a), DDIM-a, TCD(-a), LCM, DPM++ 3M SDE(-a)) on the
+        device, one host sync at the end.  c_in, c_out, t, sigma: `steps` float32 entries; form: `steps` ints (osg_stochastic_form); draws: `steps`
+        ints, != 0 where the step adds noise; coef: float32 [steps, 10] (pipeline.Txt2Img.stochastic_table makes the three); noise: float32
+        [steps, prompts, ...] or None when no step draws.  x: float32 [prompts, ...], updated IN PLACE.  Returns the loop's device ms."""
+        return self._sampler_loop_stochastic("hip_sampler_loop_stochastic", sample, timestep, out, x, c_in, c_out, t, sigma, form, draws, coef, noise,
+                                             float(guidance))
+
+    def hip_sampler_loop_stochastic_single(self, sample: str, timestep: str, out: str, x, c_in, c_out, t, sigma, form, draws, coef, noise=None) -> float:
+        """hip_sampler_loop_stochastic for a plan with ONE UNet sample per prompt (see hip_sampler_loop_single): the same arguments without `guidance`."""
+        return self._sampler_loop_stochastic("hip_sampler_loop_stochastic_single", sample, timestep, out, x, c_in, c_out, t, sigma, form, draws, coef,
+                                             noise, None)
+
     def hip_decode(self, in_name: str, out_name: str, latents, factor: float, image=None, pixels=None) -> float:
         """Latents -> image on the device (model_hip_decode): the latents are uploaded, scaled by `factor` and cut into the decoder's tiles, the
         resident pass runs, the tiles are blended and (y + 1) * 127.5 applied -- one call, one host sync.  latents: float32 [images, 4, h, w].

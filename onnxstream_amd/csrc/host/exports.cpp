@@ -380,6 +380,34 @@ char* model_hip_sampler_loop_multistep_single(Handle* h, char* sample_name, char
         return dup_cstr(e.what());
     }
 }
+// the same loop with a one-evaluation sampler that adds fresh noise per step (ddpm, ddpm_a, ddim_a, tcd, tcd_a, lcm, dpm++3msde, dpm++3msde_a;
+// src/samplers.h:1039-1223, :1406-1428, :412-541).  form: [steps] int, the osg_stochastic_form (include/osgpu.h) of each step; draws: [steps] int,
+// != 0 where the step adds noise; coef: [steps, 10] float = k0..k6, n0, n1 of the form and the prescale factor of x (prescale_sample, :38-60; 1 = none);
+// n_coef: its length; noise: [steps, prompts, L] or NULL when no step draws.  The *_single form is for a plan with one sample per prompt.
+char* model_hip_sampler_loop_stochastic(Handle* h, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, float* x,
+                                        const float* c_in, const float* c_out, const float* t, const float* sigma, const int* form, const int* draws,
+                                        const float* coef, unsigned long long n_coef, const float* noise, float guidance, double* ms) {
+    try {
+        const double v = Plan::run_sampler_loop_stochastic(h->model, sample_name, timestep_name, out_name, steps, prompts, x, c_in, c_out, t, sigma, form,
+                                                            draws, coef, (size_t)n_coef, noise, guidance);
+        if (ms) *ms = v;
+        return nullptr;
+    } catch (const std::exception& e) {
+        return dup_cstr(e.what());
+    }
+}
+char* model_hip_sampler_loop_stochastic_single(Handle* h, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, float* x,
+                                               const float* c_in, const float* c_out, const float* t, const float* sigma, const int* form,
+                                               const int* draws, const float* coef, unsigned long long n_coef, const float* noise, double* ms) {
+    try {
+        const double v = Plan::run_sampler_loop_stochastic(h->model, sample_name, timestep_name, out_name, steps, prompts, x, c_in, c_out, t, sigma, form,
+                                                            draws, coef, (size_t)n_coef, noise, 0.f, 1);
+        if (ms) *ms = v;
+        return nullptr;
+    } catch (const std::exception& e) {
+        return dup_cstr(e.what());
+    }
+}
 // latents -> image on the device (decoder_solver / sd_tiled_decoder / sdxl_decoder around the VAE pass, src/sd.cpp:1174-1346, :2357-2516, and Mat::to_pixels
 // :340-364): latents [images, 4, h, w] fp32 host -> image [images, 3, u*h, u*w] fp32 and / or pixels [images, u*h, u*w, 3] uint8, either may be NULL (not
 // made, not downloaded).  The tile size and u come from the plan's input / output shapes; the plan must have been built by a run() with images * tiles pushes

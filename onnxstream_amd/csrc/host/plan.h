@@ -203,7 +203,20 @@ struct Plan {
                                              int n_steps, int prompts, int sampler, float* x, const float* c_in, const float* c_out, const float* t,
                                              const float* sigma, const int* order, const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef,
                                              float guidance, int branches = 2);
-    static double run_sampler_loop(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
+    // the same loop with one of the one-evaluation samplers that add fresh noise per step (DDPM(-a), DDIM-a, TCD(-a), LCM, DPM++ 3M SDE(-a);
+    // src/samplers.h:1039-1223, :1406-1428, :412-541): per step a prepare launch (with the in-place prescale of x where coef[i][9] != 1, prescale_sample
+    // :38-60), the pass, and one osg_sampler_cfg_stochastic / osg_sampler_stochastic_single launch of form[i] (osg_stochastic_form).  coef: [steps, 10]
+    // float = k0..k6, n0, n1 of the form and the prescale factor; n_coef its length; noise: [steps, prompts, L] fp32 host or NULL, row i is read
+    // when draws[i].  The history ring [3, prompts, L] (create_buffers, :14) exists when an SDE form occurs; OSG_ST_SDE1 / OSG_ST_SDE2 must follow one /
+    // two steps that wrote history, so a call never reads an entry an earlier image left behind.
+    double sampler_loop_stochastic(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps, int prompts,
+                                   float* x, const float* c_in, const float* c_out, const float* t, const float* sigma, const int* form, const int* draws,
+                                   const float* coef, size_t n_coef, const float* noise, float guidance, int branches = 2);
+    static double run_sampler_loop_stochastic(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name,
+                                              int n_steps, int prompts, float* x, const float* c_in, const float* c_out, const float* t, const float* sigma,
+                                              const int* form, const int* draws, const float* coef, size_t n_coef, const float* noise, float guidance,
+                                              int branches = 2);
+    static double run_sampler_loop(Model& m,const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
                                    int prompts, float* x, const float* noise, const float* c_in, const float* c_out, const float* t, const float* sigma,
                                    const float* d_sigma, const float* sigma_up, const float* clip, int branches);
     // latents -> image without leaving the device (the VAE decoder plan): upload the latents [images, 4, H, W], osg_decode_gather cuts and scales the
@@ -297,9 +310,9 @@ struct Plan {
 
     void* samp_x = nullptr;       // sampler_loop state: latents [prompts, L] and the pre-drawn noise [steps, prompts, L], device fp32
     void* samp_noise = nullptr;
-    void* samp_hist = nullptr;    // sampler_loop_multistep: history ring [H, prompts, L], device fp32
+    void* samp_hist = nullptr;    // sampler_loop_multistep, sampler_loop_stochastic: history ring [H, prompts, L], device fp32
     size_t samp_x_bytes = 0, samp_noise_bytes = 0, samp_hist_bytes = 0;
-    // the prologue the two sampler loops share (plan_run.cpp): state and batch checks, the tensors a loop reads and writes, growing a state buffer
+    // the prologue the sampler loops share (plan_run.cpp): state and batch checks, the tensors a loop reads and writes, growing a state buffer
     struct SamplerIO { const In* in_s = nullptr; const In* in_t = nullptr; const Out* out = nullptr; long L = 0, TL = 0; };
     void sampler_check_state(const std::string& fn, int prompts, int branches) const;
     SamplerIO sampler_io(const std::string& fn, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name) const;

@@ -624,7 +624,87 @@ double Plan::sampler_loop_multistep(const std::string& sample_name, const std::s
     return ms;
 }
 
-double Plan::run_sampler_loop(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
+double Plan::sampler_loop_stochastic(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
+                                     int prompts, float* x, const float* c_in, const float* c_out, const float* t, const float* sigma, const int* form,
+                                     const int* draws, const float* coef, size_t n_coef, const float* noise, float guidance, int branches) {
+    const bool pair = branches == 2;
+    const std::string fn = pair ? "Model::hip_sampler_loop_stochastic: " : "Model::hip_sampler_loop_stochastic_single: ";
+    sampler_check_state(fn, prompts, branches);
+    if (n_steps < 0 || n_coef != (size_t)n_steps * 10) throw std::invalid_argument(fn + "the coefficient table must hold steps * 10 floats.");
+    auto sde = [](int f) { return f == OSG_ST_SDE0 || f == OSG_ST_SDE1 || f == OSG_ST_SDE2; };
+    bool ring = false, any_draw = false;
+    for (int i = 0; i < n_steps; i++) {
+        if (form[i] < 0 || form[i] >= OSG_ST_FORMS) throw std::invalid_argument(fn + "unknown form " + std::to_string(form[i]) + " at step " + std::to_string(i) + ".");
+        // entries of earlier steps (h1, h2) the form reads: each must have been written by an SDE form of this image
+        const int r = form[i] == OSG_ST_SDE2 ? 2 : form[i] == OSG_ST_SDE1 ? 1 : 0;
+        for (int k = 1; k <= r; k++)
+            if (i - k < 0 || !sde(form[i - k]))
+                throw std::invalid_argument(fn + "form " + std::to_string(form[i]) + " at step " + std::to_string(i) + " is not available.");
+        ring = ring || sde(form[i]);
+        any_draw = any_draw || draws[i];
+    }
+    if (any_draw && !noise) throw std::invalid_argument(fn + "a step draws noise but no noise was given.");
+    FlightGuard flight(in_flight);
+    const SamplerIO io = sampler_io(fn, sample_name, timestep_name, out_name);
+    const long L = io.L;
+    float *sample = (float*)ptr(io.in_s->staging), *tstep = (float*)ptr(io.in_t->staging);
+    const float* eps = (const float*)ptr(io.out->f32val);
+    const int H = ring ? 3 : 0;       // create_buffers, src/samplers.h:14
+    const size_t xb = (size_t)prompts * L * sizeof(float), nb = (size_t)n_steps * xb, hb = (size_t)H * xb;
+    sampler_grow(samp_x, samp_x_bytes, xb);
+    if (any_draw) sampler_grow(samp_noise, samp_noise_bytes, nb);
+    if (H) sampler_grow(samp_hist, samp_hist_bytes, hb);
+    be.check(be.api.osg_upload(be.ctx, samp_x, x, xb), "osg_upload");
+    if (any_draw) be.check(be.api.osg_upload(be.ctx, samp_noise, noise, nb), "osg_upload");
+    // history entry k of step i lives in ring slot (i - k) mod H, as in sampler_loop_multistep: the reference's shift (src/samplers.h:422) is a rotation
+    auto slot = [&](int i, int k) -> float* { return (float*)samp_hist + (size_t)(((i - k) % H + H) % H) * prompts * L; };
+    be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");
+    for (int i = 0; i < n_steps; i++) {
+        const float* k = coef + (size_t)i * 10;
+        if (!pair)
+            be.check(be.api.osg_sampler_prepare_single(be.ctx, (float*)samp_x, sample, tstep, prompts, L, k[9], c_in[i], t[i], io.TL), "osg_sampler_prepare_single");
+        else if (k[9] != 1.f)
+            be.check(be.api.osg_sampler_prepare_rescale(be.ctx, (float*)samp_x, sample, tstep, prompts, L, k[9], c_in[i], t[i], io.TL),
+                     "osg_sampler_prepare_rescale");
+        else
+            be.check(be.api.osg_sampler_prepare(be.ctx, (const float*)samp_x, sample, tstep, prompts, L, c_in[i], t[i], io.TL), "osg_sampler_prepare");
+        if (graph) be.check(be.api.osg_graph_launch(be.ctx, graph), "osg_graph_launch");
+        else run_steps();
+        const int f = form[i];
+        float* h0 = sde(f) ? slot(i, 0) : nullptr;
+        const float *h1 = f == OSG_ST_SDE1 || f == OSG_ST_SDE2 ? slot(i, 1) : nullptr, *h2 = f == OSG_ST_SDE2 ? slot(i, 2) : nullptr;
+        const float* nz = draws[i] ? (const float*)samp_noise + (size_t)i * prompts * L : nullptr;
+        if (pair)
+            be.check(be.api.osg_sampler_cfg_stochastic(be.ctx, f, (float*)samp_x, eps, nz, h0, h1, h2, prompts, L, c_out[i], guidance, sigma[i], k[0], k[1], k[2],
+                                                       k[3], k[4], k[5], k[6], k[7], k[8]),
+                     "osg_sampler_cfg_stochastic");
+        else
+            be.check(be.api.osg_sampler_stochastic_single(be.ctx, f, (float*)samp_x, eps, nz, h0, h1, h2, prompts, L, c_out[i], sigma[i], k[0], k[1], k[2], k[3],
+                                                          k[4], k[5], k[6], k[7], k[8]),
+                     "osg_sampler_stochastic_single");
+    }
+    float ms = 0;
+    be.check(be.api.osg_timer_stop(be.ctx, &ms), "osg_timer_stop");
+    be.check(be.api.osg_download(be.ctx, x, samp_x, xb), "osg_download");
+    runs += n_steps;
+    m_last_ms = n_steps > 0 ? ms / n_steps : 0;
+    return ms;
+}
+
+double Plan::run_sampler_loop_stochastic(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name,
+                                         int n_steps, int prompts, float* x, const float* c_in, const float* c_out, const float* t, const float* sigma,
+                                         const int* form, const int* draws, const float* coef, size_t n_coef, const float* noise, float guidance,
+                                         int branches) {
+    if (!m.m_plan)
+        throw std::runtime_error(std::string(branches == 2 ? "Model::hip_sampler_loop_stochastic" : "Model::hip_sampler_loop_stochastic_single") +
+                                 ": no plan (call run() first).");
+    const double ms = m.m_plan->sampler_loop_stochastic(sample_name, timestep_name, out_name, n_steps, prompts, x, c_in, c_out, t, sigma, form, draws, coef,
+                                                        n_coef, noise, guidance, branches);
+    m.m_last_ms = m.m_plan->last_ms();
+    return ms;
+}
+
+double Plan::run_sampler_loop(Model& m,const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
                               int prompts, float* x, const float* noise, const float* c_in, const float* c_out, const float* t, const float* sigma,
                               const float* d_sigma, const float* sigma_up, const float* clip, int branches) {
     if (!m.m_plan) throw std::runtime_error("Model::hip_sampler_loop_single: no plan (call run() first).");

@@ -6,6 +6,8 @@
 //                              samplers.h:66, selects:  x = x + ((x - d) / sigma_i) * (sigma_down - sigma_i) + r * sigma_up)
 //   osg_sampler_cfg_multistep   <- the same CFG combine, then one step of DPM++ 2M / 2M v2, iPNDM / iPNDM_v / iPNDM_vo, Taylor3 or DDIM
 //                                  (src/samplers.h:339-377, :543-582, :688-940, :942-1034, :1078-1100) with a history ring per prompt
+//   osg_sampler_cfg_stochastic  <- the same CFG combine, then one step of DDPM(-a), DDIM-a, TCD(-a), LCM or DPM++ 3M SDE(-a) with the step's noise add
+//                                  (src/samplers.h:1039-1076, :1102-1158, :1160-1223, :1406-1428, :412-541)
 //   osg_sampler_prepare_rescale <- osg_sampler_prepare after DDIM's in-place prescale of x (prescale_sample, src/samplers.h:27-59)
 //   osg_sampler_*_single        <- the same three steps without the guidance pair: CFGDenoiser_CompVisDenoiser returns the cond branch alone in
 //                                  Turbo mode (src/sd.cpp:1537-1541), so the pass holds ONE sample per prompt and den = eps[p]*c_out + x
@@ -203,6 +205,83 @@ __global__ __launch_bounds__(256) void sampler_cfg_multistep_kernel(float* __res
     }
 }
 
+// The one-evaluation samplers of src/samplers.h that add fresh noise per step (DDPM, DDIM-a, TCD, LCM, DPM++ 3M SDE; ORIGINAL_SAMPLER_ALGORITHMS
+// branch): the same den, one of the update forms of include/osgpu.h (osg_stochastic_form), each its own straight-line instantiation, then the
+// reference's noise add when `noise` is given.  History holds den: the SDE forms write h0 and read h1, h2 (other ring slots, never h0).
+template <int F, int B>
+__global__ __launch_bounds__(256) void sampler_cfg_stochastic_kernel(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ noise,
+                                                                     float* __restrict__ h0, const float* __restrict__ h1, const float* __restrict__ h2,
+                                                                     int prompts, long L, float c_out, float guidance, float sigma, float k0, float k1,
+                                                                     float k2, float k3, float k4, float k5, float k6, float n0, float n1) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)prompts * L) return;
+    const long p = i / L, e = i - p * L;
+    const float xv = x[i];
+    const float den = sampler_denoised<B>(eps, p, L, e, xv, c_out, guidance);
+    float nx;
+    if constexpr (F == OSG_ST_LINEAR) {
+        const float ax = xv * k0;
+        const float bd = den * k1;
+        nx = ax + bd;
+    } else if constexpr (F == OSG_ST_DEN) {
+        nx = den;
+    } else if constexpr (F == OSG_ST_EULER) {
+        const float d = (xv - den) / sigma;
+        const float s = d * k0;
+        nx = xv + s;
+    } else if constexpr (F == OSG_ST_DDIM_A) {
+        const float az = k0 + xv;
+        const float mo = (az - den) / sigma;
+        const float xa = xv * k1;
+        const float mb = mo * k2;
+        const float po = (xa - mb) / k1;
+        const float u = k3 * po;
+        const float w = mo * k4;
+        nx = u + w;
+    } else if constexpr (F == OSG_ST_TCD) {
+        const float mo = (xv - den) / sigma;
+        const float km = k0 * mo;
+        const float po = xv - km;
+        const float u = k1 * po;
+        const float w = k2 * mo;
+        nx = u + w;
+    } else {
+        static_assert(F == OSG_ST_SDE0 || F == OSG_ST_SDE1 || F == OSG_ST_SDE2, "unknown stochastic form");
+        h0[i] = den;
+        const float ax = k0 * xv;
+        const float bd = k1 * den;
+        nx = ax - bd;
+        if constexpr (F == OSG_ST_SDE1) {
+            const float d1 = (den - h1[i]) / k2;
+            const float w = k3 * d1;
+            nx = nx + w;
+        } else if constexpr (F == OSG_ST_SDE2) {
+            const float b1 = h1[i];
+            const float d10 = (den - b1) / k2;
+            const float d11 = (b1 - h2[i]) / k3;
+            const float df = d10 - d11;
+            const float dr = df * k2;
+            const float d1 = d10 + dr / k4;
+            const float d2 = df / k4;
+            const float u = k5 * d1;
+            const float w = k6 * d2;
+            nx = nx + (u - w);
+        }
+    }
+    if (noise) {
+        if constexpr (F == OSG_ST_TCD) {
+            const float a = n1 * nx;
+            const float b = n0 * noise[i];
+            nx = a + b;
+        } else {
+            const float nz = noise[i] * n0;
+            nx = nx + nz;
+        }
+    }
+    x[i] = nx;
+}
+
 // the launches behind the entry points, one per step of the loop, each for both branch counts; `fn` names the entry point in error texts
 // x_scale == 1 is the launch without DDIM's prescale: x is not written
 template <int B>
@@ -261,6 +340,32 @@ int launch_multistep(osg_ctx* ctx, const char* fn, int form, float* x, const flo
     return 0;
 }
 
+template <int B>
+int launch_stochastic(osg_ctx* ctx, const char* fn, int form, float* x, const float* eps, const float* noise, float* h0, const float* h1, const float* h2,
+                      int prompts, long L, float c_out, float guidance, float sigma, float k0, float k1, float k2, float k3, float k4, float k5, float k6,
+                      float n0, float n1) {
+    if (form < 0 || form >= OSG_ST_FORMS) OSG_FAIL(ctx, std::string(fn) + ": unknown form " + std::to_string(form));
+    const int need = form == OSG_ST_SDE2 ? 3 : form == OSG_ST_SDE1 ? 2 : form == OSG_ST_SDE0 ? 1 : 0;    // history pointers the form touches: h0 .. h(need-1)
+    const float* hs[3] = {h0, h1, h2};
+    for (int k = 0; k < need; k++)
+        if (!hs[k]) OSG_FAIL(ctx, std::string(fn) + ": form " + std::to_string(form) + " needs history pointer h" + std::to_string(k));
+    if (prompts <= 0 || L <= 0) return 0;
+    const long total = (long)prompts * L;
+    const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+#define OSG_ST_CASE(F)                                                                                                                                  \
+    case F:                                                                                                                                             \
+        hipLaunchKernelGGL((sampler_cfg_stochastic_kernel<F, B>), grid, block, 0, ctx->compute, x, eps, noise, h0, h1, h2, prompts, L, c_out, guidance, \
+                           sigma, k0, k1, k2, k3, k4, k5, k6, n0, n1);                                                                                  \
+        break;
+    switch (form) {
+        OSG_ST_CASE(OSG_ST_LINEAR) OSG_ST_CASE(OSG_ST_DEN) OSG_ST_CASE(OSG_ST_EULER) OSG_ST_CASE(OSG_ST_DDIM_A) OSG_ST_CASE(OSG_ST_TCD)
+        OSG_ST_CASE(OSG_ST_SDE0) OSG_ST_CASE(OSG_ST_SDE1) OSG_ST_CASE(OSG_ST_SDE2)
+    }
+#undef OSG_ST_CASE
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -301,6 +406,20 @@ int osg_sampler_multistep_single(osg_ctx* ctx, int form, float* x, const float* 
                                  double db) {
     return launch_multistep<1>(ctx, "osg_sampler_multistep_single", form, x, eps, h0, h1, h2, h3, prompts, L, c_out, 0.f, sigma, k0, k1, k2, k3, k4,
                                da, db);
+}
+
+int osg_sampler_cfg_stochastic(osg_ctx* ctx, int form, float* x, const float* eps, const float* noise, float* h0, const float* h1, const float* h2,
+                               int prompts, long L, float c_out, float guidance, float sigma, float k0, float k1, float k2, float k3, float k4, float k5,
+                               float k6, float n0, float n1) {
+    return launch_stochastic<2>(ctx, "osg_sampler_cfg_stochastic", form, x, eps, noise, h0, h1, h2, prompts, L, c_out, guidance, sigma, k0, k1, k2, k3, k4,
+                                k5, k6, n0, n1);
+}
+
+int osg_sampler_stochastic_single(osg_ctx* ctx, int form, float* x, const float* eps, const float* noise, float* h0, const float* h1, const float* h2,
+                                  int prompts, long L, float c_out, float sigma, float k0, float k1, float k2, float k3, float k4, float k5, float k6,
+                                  float n0, float n1) {
+    return launch_stochastic<1>(ctx, "osg_sampler_stochastic_single", form, x, eps, noise, h0, h1, h2, prompts, L, c_out, 0.f, sigma, k0, k1, k2, k3, k4,
+                                k5, k6, n0, n1);
 }
 
 }  // extern "C"

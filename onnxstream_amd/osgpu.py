@@ -28,7 +28,7 @@ EXPORTS = [
     "osg_instance_norm", "osg_group_norm_nhwc", "osg_layer_norm", "osg_reduce_mean_last", "osg_softmax_last",
     "osg_unary", "osg_binary", "osg_geglu", "osg_transpose", "osg_copy_2d", "osg_concat2", "osg_resize_nearest", "osg_gather_rows",
     "osg_maxpool_nhwc", "osg_convert", "osg_sampler_prepare", "osg_sampler_cfg_euler_a", "osg_sampler_cfg_multistep", "osg_sampler_prepare_rescale",
-    "osg_sampler_prepare_single", "osg_sampler_euler_a_single", "osg_sampler_multistep_single",
+    "osg_sampler_prepare_single", "osg_sampler_euler_a_single", "osg_sampler_multistep_single", "osg_sampler_cfg_stochastic", "osg_sampler_stochastic_single",
     "osg_decode_gather", "osg_decode_blend",
     "osg_range_push", "osg_range_pop", "osg_marker_record", "osg_copy_wait_marker", "osg_timer_mark", "osg_timer_between", "osg_set_stat_sinks", "osg_group_norm_stats_nhwc", "osg_qu8_conv2d_nhwc", "osg_qu8_conv2d_nhwc_t", "osg_qu8_conv_tap_sums", "osg_qu8_gemm", "osg_qu8_lut", "osg_qu8_binary", "osg_qu8_instance_norm", "osg_qu8_instance_norm_nhwc", "osg_qu8_affine_act", "osg_qu8_norm_affine_act_nhwc", "osg_qu8_softmax_last", "osg_kdbg_read",
     "osg_tblock_tail_supported", "osg_tblock_tail", "osg_tblock_kv_pack_elems", "osg_tblock_kv_pack_jobs", "osg_tblock_pack_weight", 
@@ -124,6 +124,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.osg_sampler_prepare_single.argtypes = [vp, vp, vp, vp, ci, cl, cf, cf, cf, cl]
     lib.osg_sampler_euler_a_single.argtypes = [vp, vp, vp, vp, ci, cl, cf, cf, cf, cf, cf]
     lib.osg_sampler_multistep_single.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, cl, cf, cf, cf, cf, cf, cf, cf, ctypes.c_double, ctypes.c_double]
+    lib.osg_sampler_cfg_stochastic.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, cl] + [cf] * 12
+    lib.osg_sampler_stochastic_single.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, cl] + [cf] * 11
     lib.osg_decode_gather.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf]
     lib.osg_decode_blend.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci]
     lib.osg_set_stat_sinks.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, ci]

@@ -42,19 +42,25 @@ expf, logf = _libm_float_fn("exp"), _libm_float_fn("log")
 expm1f, sqrtf = _libm_float_fn("expm1"), _libm_float_fn("sqrt")
 powf = _libm_float_fn("pow", 2)
 
-# the samplers of the reference's --sampler (src/sd.cpp:41-63) that sample() and sample_device() run: the default Euler-Ancestral, Euler, and the
-# one-evaluation, noise-free multistep samplers of src/samplers.h (the ORIGINAL_SAMPLER_ALGORITHMS branch)
+# samplers of the reference's --sampler (src/sd.cpp:41-63) that sample() and sample_device() run: the default Euler-Ancestral, Euler, and the
+# one-evaluation, noise-free multistep samplers of src/samplers.h (the ORIGINAL_SAMPLER_ALGORITHMS branch); STOCHASTIC below holds eight more
 SAMPLERS = ("euler_a", "euler", "dpm++2m", "dpm++2mv2", "ipndm", "ipndm_v", "ipndm_vo", "taylor3", "ddim")
 # multistep sampler -> loop form of model_hip_sampler_loop_multistep (exports.cpp)
 MULTISTEP = {"dpm++2m": 0, "dpm++2mv2": 0, "ipndm": 1, "ipndm_v": 2, "ipndm_vo": 3, "taylor3": 4, "ddim": 5}
 # loop form -> (history depth as src/samplers.h create_buffers, the osg_multistep_form of each order); the table of Plan::sampler_loop_multistep
 # (order 2 of loop form 0 is the plain Euler step the reference substitutes on the last step of an SDXL image, src/sd.cpp:1705-1719)
 _MS_LOOP = {0: (1, (0, 1, 2)), 1: (4, (2, 3, 5, 6)), 2: (4, (2, 4, 5, 6)), 3: (4, (2, 7, 8, 9)), 4: (3, (2, 10, 11)), 5: (0, (12,))}
+# the one-evaluation samplers that add fresh noise per step (src/samplers.h:1039-1223, :1406-1428, :412-541) -> eta, the randomness the reference sets
+# for the name (0: the sampler draws nothing; dpm++3msde_a takes 0.5 in Turbo mode, :414-417).  lcm has no eta; it draws on every step but the last.
+STOCHASTIC = {"ddpm": 0.0, "ddpm_a": 1.0, "ddim_a": 1.0, "tcd": 0.0, "tcd_a": 0.5, "lcm": 0.0, "dpm++3msde": 0.0, "dpm++3msde_a": 1.0}
+# osg_stochastic_form (include/osgpu.h)
+ST_LINEAR, ST_DEN, ST_EULER, ST_DDIM_A, ST_TCD, ST_SDE0, ST_SDE1, ST_SDE2 = range(8)
+_ST_SDE = (ST_SDE0, ST_SDE1, ST_SDE2)
 
 
 def _check_sampler(sampler: str) -> None:
-    if sampler not in SAMPLERS:
-        raise ValueError(f"unknown sampler {sampler!r}; valid names: {', '.join(SAMPLERS)}")
+    if sampler not in SAMPLERS + tuple(STOCHASTIC):
+        raise ValueError(f"unknown sampler {sampler!r}; valid names: {', '.join(SAMPLERS + tuple(STOCHASTIC))}")
 
 
 # pow(2.f, -p - .5f) with the reference's constexpr p = 0 (src/samplers.h:101-103), stated as the constant the compiler folds it to: the correctly
@@ -128,6 +134,44 @@ def multistep_update(form: int, x: np.ndarray, den: np.ndarray, hist, sigma, k, 
         raise ValueError(f"unknown multistep form {form}")
     hist[0][...] = d
     return (x + s).astype(f32)
+
+
+def stochastic_update(form: int, x: np.ndarray, den: np.ndarray, hist, sigma, k, noise) -> np.ndarray:
+    """One step of osg_stochastic_form `form` (include/osgpu.h) on the host, in the kernel's operation order: every fp32 operation rounded on its own.
+    hist = [h0, h1, h2] (arrays or None); the SDE forms overwrite h0 with den.  k = k0..k6, n0, n1; noise: the step's draw, or None.  Returns the new x."""
+    k0, k1, k2, k3, k4, k5, k6, n0, n1 = (f32(v) for v in k[:9])
+    sigma = f32(sigma)
+    if form == ST_LINEAR:
+        nx = (x * k0) + (den * k1)
+    elif form == ST_DEN:
+        nx = den
+    elif form == ST_EULER:
+        nx = x + (((x - den) / sigma) * k0)
+    elif form == ST_DDIM_A:
+        mo = ((k0 + x) - den) / sigma
+        po = ((x * k1) - (mo * k2)) / k1
+        nx = (k3 * po) + (mo * k4)
+    elif form == ST_TCD:
+        mo = (x - den) / sigma
+        po = x - (k0 * mo)
+        nx = (k1 * po) + (k2 * mo)
+    elif form in _ST_SDE:
+        hist[0][...] = den
+        nx = (k0 * x) - (k1 * den)
+        if form == ST_SDE1:
+            nx = nx + (k3 * ((den - hist[1]) / k2))
+        elif form == ST_SDE2:
+            d10 = (den - hist[1]) / k2
+            d11 = (hist[1] - hist[2]) / k3
+            df = d10 - d11
+            d1 = d10 + ((df * k2) / k4)
+            d2 = df / k4
+            nx = nx + ((k5 * d1) - (k6 * d2))
+    else:
+        raise ValueError(f"unknown stochastic form {form}")
+    if noise is not None:
+        nx = ((n1 * nx) + (n0 * noise)) if form == ST_TCD else (nx + (noise * n0))
+    return nx.astype(f32)
 
 
 def log_sigmas_table() -> np.ndarray:
@@ -355,6 +399,8 @@ class Txt2Img:
         sampler="euler": the plain Euler step of the same branch (src/samplers.h:116-126): x += (x - d) / sigma_i * (sigma_{i+1} - sigma_i), no noise.
         The multistep samplers of MULTISTEP (DPM++ 2M / 2M v2, iPNDM, iPNDM_v, iPNDM_vo, Taylor3, DDIM) take their per-step scalars from
         multistep_table() and step with multistep_update(), the host restatement of the device kernel; they draw no noise.
+        The samplers of STOCHASTIC (DDPM(-a), DDIM-a, TCD(-a), LCM, DPM++ 3M SDE(-a)) take theirs from stochastic_table() and step with
+        stochastic_update(); step_noise(i) is asked for on the steps that draw, which are a prefix of the image.
         extra_cond / extra_uncond: SDXL's micro-conditioning, as denoise() takes it.  xl: the reference's `--xl` (the DPM++ pair takes the Euler step on
         the last step, multistep_table()).  turbo: `--turbo` -- implies xl; one UNet sample per prompt and no guidance (uncond may be None), the
         Turbo forms of sigma_reshaper / sigma_reshaper_sharp and of DDIM's prescale, any steps >= 1 (src/sd.cpp:2923)."""
@@ -375,6 +421,22 @@ class Txt2Img:
                 den = self.denoise(x, float(sig[i]), cond, uncond, **dn)
                 hist = [ring[(i - k) % depth] if depth and k <= order[i] else None for k in range(4)]
                 x = multistep_update(forms[order[i]], x, den, hist, sig[i], coef[i], dcoef[i])
+                if on_step:
+                    on_step(i, x)
+            return x
+        if sampler in STOCHASTIC:
+            form, draws, coef = self.stochastic_table(sig, sampler, xl=xl, turbo=turbo)
+            depth = 3 if any(f in _ST_SDE for f in form) else 0       # create_buffers, src/samplers.h:14
+            ring = [np.zeros(x.shape, f32) for _ in range(depth)]
+            for i in range(steps):
+                if coef[i, 9] != 1:       # prescale_sample (src/samplers.h:27-59), before the denoiser sees x
+                    x = (x * coef[i, 9]).astype(f32)
+                den = self.denoise(x, float(sig[i]), cond, uncond, **dn)
+                hist = [ring[(i - k) % depth] if depth else None for k in range(3)]
+                noise = None
+                if draws[i]:
+                    noise = rng.standard_normal(latent_shape, dtype=f32) if step_noise is None else np.asarray(step_noise(i), f32).reshape(latent_shape)
+                x = stochastic_update(form[i], x, den, hist, sig[i], coef[i], noise)
                 if on_step:
                     on_step(i, x)
             return x
@@ -503,15 +565,111 @@ class Txt2Img:
                     coef[i, 1:4] = f32(one / dt_prev), f32(dd / two), f32(f32(dd * dt) / f32(6))
                 dt_prev = dt
             else:                                                         # ddim, src/samplers.h:1078-1100 and prescale_sample :27-59
-                root = sqrtf(f32(f32(s * s) + one))
-                if turbo and i:                                           # "soften correction for Turbo model": pow(scale, 0.9925f - 2.5f / steps / steps)
-                    root = powf(root, f32(f32(0.9925) - f32(f32(f32(2.5) / f32(steps)) / f32(steps))))
-                coef[i, 5] = f32(root / s) if i == 0 else root
+                coef[i, 5] = self._prescale(s, i, steps, turbo)
                 sn2 = float(f32(s1 * s1))
                 alpha = 1.0 / (sn2 + 1.0)
                 a = math.sqrt(1.0 - alpha) / float(s)
                 dcoef[i] = a, math.sqrt(alpha) - a
         return MULTISTEP[sampler], order, coef, dcoef
+
+    def stochastic_table(self, sig: np.ndarray, sampler: str, xl: bool = False, turbo: bool = False):
+        """Per-step scalars of a sampler of STOCHASTIC, as the reference's process_sample computes them (src/samplers.h, ORIGINAL_SAMPLER_ALGORITHMS): the
+        reference's expression tree in float, every operation rounded on its own, libm's float functions; its per-element std::log / std::exp /
+        std::sqrt calls act on scalars and are hoisted here.  DDPM and LCM read the raw sigma[i + 1], DDIM-a and TCD sigma_reshaper_sharp, DPM++ 3M SDE
+        the doubly averaged sigma_reshaper of :426-432.  xl (implied by turbo): the last step of DPM++ 3M SDE is the plain Euler step (src/sd.cpp:1711-1716).
+        Returns (form [steps] int32 = the step's osg_stochastic_form, draws [steps] int32 = 1 where the step adds noise, coef [steps, 10] float32 =
+        k0..k6, n0, n1 of the form and the prescale factor of x).  The drawing steps are a prefix of the image: the reference advances its noise seed on
+        drawing steps only, so noise i of the application's walk belongs to step i."""
+        if sampler not in STOCHASTIC:
+            raise ValueError(f"{sampler!r} is not a stochastic sampler; those are: {', '.join(STOCHASTIC)}")
+        steps = len(sig) - 1
+        form = np.zeros(steps, np.int32)
+        draws = np.zeros(steps, np.int32)
+        coef = np.zeros((steps, 10), f32)
+        coef[:, 8:] = 1
+        zero, one, two = f32(0), f32(1), f32(2)
+        xl = xl or turbo
+        eta = f32(0.5 if sampler == "dpm++3msde_a" and turbo else STOCHASTIC[sampler])
+        fmax = lambda a, b: b if a < b else a                             # std::max
+        for i in range(steps):
+            s, sn = f32(sig[i]), f32(sig[i + 1])
+            with np.errstate(divide="ignore", invalid="ignore"):
+                if sampler in ("ddpm", "ddpm_a"):                             # src/samplers.h:1039-1076
+                    s2, sn2 = f32(s * s), f32(sn * sn)
+                    scale_back, d = sqrtf(f32(s2 + one)), sqrtf(f32(sn2 + one))
+                    variance = zero if eta <= 0 else f32(f32(f32(f32(eta * sqrtf(f32(s2 - sn2))) / d) * sn) / s)
+                    form[i] = ST_LINEAR
+                    coef[i, :2] = f32(f32(f32(sn2 / s2) * scale_back) / d), f32(f32(f32(s2 - sn2) / d) / s2)
+                    if not variance <= 0:                                     # the reference's branch, :1053
+                        draws[i], coef[i, 7] = 1, variance
+                elif sampler == "lcm":                                        # :1406-1428
+                    form[i] = ST_DEN
+                    if sn > 0:
+                        draws[i], coef[i, 7] = 1, sn
+                elif sampler == "ddim_a":                                     # :1102-1158
+                    si1 = sigma_reshaper_sharp(sn, i, steps, turbo)
+                    a_t, a_prev = f32(one / f32(f32(s * s) + one)), f32(one / f32(f32(si1 * si1) + one))
+                    b_t, b_prev = f32(one - a_t), f32(one - a_prev)
+                    variance = f32(f32(b_prev / b_t) * f32(one - f32(a_t / a_prev)))
+                    autozero = f32(variance * zero)
+                    form[i], draws[i] = ST_DDIM_A, 1
+                    coef[i, :5] = autozero, sqrtf(a_t), sqrtf(b_t), sqrtf(a_prev), sqrtf(f32(f32(one - a_prev) - f32(f32(variance * eta) * eta)))
+                    coef[i, 7] = f32(eta * sqrtf(fmax(autozero, variance)))
+                    coef[i, 9] = self._prescale(s, i, steps, turbo)
+                elif sampler in ("tcd", "tcd_a"):                             # :1160-1223
+                    si1 = sigma_reshaper_sharp(sn, i, steps, turbo)
+                    si4 = f32(si1 * f32(one - eta))
+                    si3 = f32(sig[int(f32(f32(f32(steps - i - 1) * eta) + f32(i)) + one)])      # float arithmetic, then truncation (:1174)
+                    si2 = sqrtf(f32(sqrtf(f32(si3 * (f32(si3 * f32(si1 / sn)) if sn else si3))) * sqrtf(f32(si4 * sqrtf(f32(si3 * si4))))))
+                    a_n, a_s, alpha = f32(one / f32(f32(si1 * si1) + one)), f32(one / f32(f32(si2 * si2) + one)), f32(one / f32(f32(s * s) + one))
+                    beta, b_s = f32(one - alpha), f32(one - a_s)
+                    form[i] = ST_TCD
+                    coef[i, :3] = f32(sqrtf(beta) / sqrtf(alpha)), sqrtf(a_s), sqrtf(b_s)
+                    if eta > 0 and i < steps - 1:
+                        draws[i] = 1
+                        coef[i, 8], coef[i, 7] = sqrtf(f32(a_n / a_s)), sqrtf(fmax(f32(s * zero), f32(one - f32(a_n / a_s))))
+                    coef[i, 9] = self._prescale(s, i, steps, turbo)
+                elif xl and i == steps - 1:                                   # dpm++3msde(_a): the sampler IS Euler for this step, :119-125
+                    form[i] = ST_EULER
+                    coef[i, 0] = f32(sigma_reshaper(sn, i, steps, turbo) - s)
+                else:                                                         # dpm++3msde(_a), :412-541
+                    rs = lambda v, j: sigma_reshaper(v, j, steps, turbo)
+                    si1 = rs(sn, i)
+                    si1 = f32(f32(si1 + rs(si1, i)) / two)                    # "it seems that single correction is not enough", :430-432
+                    if not si1:
+                        form[i] = ST_DEN
+                        continue
+                    h = f32(logf(s) - logf(si1))
+                    h_eta = f32(h * f32(eta + one))
+                    form[i] = (ST_SDE0, ST_SDE1, ST_SDE2)[min(i, 2)]
+                    coef[i, :2] = expf(f32(-h_eta)), expm1f(f32(-h_eta))
+                    if i:
+                        si0 = rs(s, i - 1)
+                        si0 = f32(f32(si0 + rs(si0, i - 1)) / two)
+                        r = f32(f32(logf(f32(sig[i - 1])) - logf(si0)) / h)
+                        phi_2 = f32(f32(expm1f(f32(-h_eta)) / h_eta) + one)
+                        coef[i, 2:4] = r, phi_2
+                    if i > 1:
+                        sm1 = rs(f32(sig[i - 1]), i - 2)
+                        sm1 = f32(f32(sm1 + rs(sm1, i - 2)) / two)
+                        r2 = f32(f32(logf(f32(sig[i - 2])) - logf(sm1)) / h)
+                        coef[i, 3:7] = r2, f32(r + r2), phi_2, f32(f32(phi_2 / h_eta) - f32(0.5))
+                    if eta:
+                        draws[i] = 1
+                        coef[i, 7] = f32(si1 * sqrtf(fmax(f32(si1 * zero), f32(one - powf(f32(si1 / s), f32(two * eta))))))
+        nd = int(draws.sum())
+        assert draws[:nd].all() and not draws[nd:].any(), "the drawing steps must be a prefix of the image"
+        return form, draws, coef
+
+    @staticmethod
+    def _prescale(s, i: int, steps: int, turbo: bool):
+        """prescale_sample (src/samplers.h:27-59): the factor DDIM, DDIM-a and TCD scale x by before the denoiser sees it, softened after the first step
+        in Turbo mode (:50-59)"""
+        one = f32(1)
+        root = sqrtf(f32(f32(s * s) + one))
+        if turbo and i:                                           # "soften correction for Turbo model": pow(scale, 0.9925f - 2.5f / steps / steps)
+            root = powf(root, f32(f32(0.9925) - f32(f32(f32(2.5) / f32(steps)) / f32(steps))))
+        return f32(root / s) if i == 0 else root
 
     def sample_device(self, cond, uncond, steps: int = 20, seed: int = 42, latent_shape=(1, 4, 64, 64), guidance: float = 7.0,
                       init_latent: Optional[np.ndarray] = None, step_noise: Optional[Callable[[int], np.ndarray]] = None,
@@ -519,7 +677,8 @@ class Txt2Img:
         """sample() with the whole loop enqueued on the GPU (HIP backend only): per step a scaling kernel fills the UNet's input staging,
         the captured pass is launched, and one kernel does eps -> denoised, the CFG combine and the Euler-Ancestral update -- no host
         round trip until the last step.  Same schedule, same random stream, same fp32 operation order as sample(): the two agree bit
-        for bit.  The multistep samplers (MULTISTEP) run their update kernel (osg_sampler_cfg_multistep) with a history ring on the device.  cond / uncond: one context each, or lists with one entry per prompt (latent_shape[0] prompts).
+        for bit.  The multistep samplers (MULTISTEP) run their update kernel (osg_sampler_cfg_multistep) with a history ring on the device, the
+        samplers of STOCHASTIC theirs (osg_sampler_cfg_stochastic) with the ring and the pre-drawn noise of the steps that draw.  cond / uncond: one context each, or lists with one entry per prompt (latent_shape[0] prompts).
         extra_cond / extra_uncond, xl, turbo: as sample().  In Turbo mode the pass holds one sample per prompt and the guidance-free kernels
         (osg_sampler_*_single) run; the extras stay resident with the contexts and are refreshed with them when the plan is reused."""
         _check_sampler(sampler)
@@ -533,8 +692,13 @@ class Txt2Img:
         rng = np.random.default_rng(seed)
         x0 = rng.standard_normal(latent_shape, dtype=f32) if init_latent is None else np.asarray(init_latent, f32).reshape(latent_shape)
         x = np.ascontiguousarray(x0 * f32(sig[0]), f32)
-        c_in, c_out, ts, s_arr, d_sigma, s_up = self.loop_scalars(sig, "euler" if sampler in MULTISTEP else sampler, turbo=turbo)
-        if sampler not in MULTISTEP:
+        c_in, c_out, ts, s_arr, d_sigma, s_up = self.loop_scalars(sig, "euler" if sampler in MULTISTEP or sampler in STOCHASTIC else sampler, turbo=turbo)
+        if sampler in STOCHASTIC:
+            form, draws, coef = self.stochastic_table(sig, sampler, xl=xl, turbo=turbo)
+            noise = np.zeros((steps,) + tuple(latent_shape), f32) if draws.any() else None       # rows of the steps that draw nothing stay unread
+            for i in np.flatnonzero(draws):
+                noise[i] = rng.standard_normal(latent_shape, dtype=f32) if step_noise is None else np.asarray(step_noise(i), f32).reshape(latent_shape)
+        elif sampler not in MULTISTEP:
             noise = np.empty((steps,) + tuple(latent_shape), f32)
             for i in range(steps):
                 noise[i] = rng.standard_normal(latent_shape, dtype=f32) if step_noise is None else np.asarray(step_noise(i), f32).reshape(latent_shape)
@@ -560,6 +724,11 @@ class Txt2Img:
                 self.last_loop_ms = self.unet.hip_sampler_loop_multistep_single(*io, loop, c_in, c_out, ts, s_arr, order, coef, dcoef)
             else:
                 self.last_loop_ms = self.unet.hip_sampler_loop_multistep(*io, loop, c_in, c_out, ts, s_arr, order, coef, dcoef, guidance)
+        elif sampler in STOCHASTIC:
+            if turbo:
+                self.last_loop_ms = self.unet.hip_sampler_loop_stochastic_single(*io, c_in, c_out, ts, s_arr, form, draws, coef, noise)
+            else:
+                self.last_loop_ms = self.unet.hip_sampler_loop_stochastic(*io, c_in, c_out, ts, s_arr, form, draws, coef, noise, guidance)
         elif turbo:
             self.last_loop_ms = self.unet.hip_sampler_loop_single(*io, noise, c_in, c_out, ts, s_arr, d_sigma, s_up)
         else:
