@@ -328,6 +328,29 @@ int osg_rope(osg_ctx* ctx, osg_dtype dtype, const void* x, const void* cos_t, co
 int osg_sdpa(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, const void* v, const void* mask, void* o, int batch, int q_heads,
              int kv_heads, int Tq, int Tkv, int D, float scale);
 
+/* ---- greedy token loop on the device (the reference app's loop, src/llm.cpp:472-496, around a T = 1 pass over key/value caches of a fixed
+ * capacity).  Its state is four device int32: state[0] = row (the cache row the running pass appends = the position of its token), state[1] = len
+ * (cache rows that are valid once that pass has run), state[2] = n_tokens, state[3] = stop (0 running, 1 end-of-sequence token, 2 "Invalid result of
+ * the Argmax.").  The host starts it as (-1, length of the caches, 0, 0): until the first token is picked a pass appends nowhere.  Nothing on the device
+ * waits or polls. */
+/* The app's argmax (src/llm.cpp:355-370) over the LAST row of logits [T][V] fp32, quirks included: the scan starts from prev = -1.0f and takes an
+ * element when v >= prev, so the result is the largest index among the elements equal to the maximum of those that are >= -1; NaN is never taken;
+ * -1 when nothing qualifies.  Then, in one launch of one workgroup:
+ *   stop != 0 or n_tokens >= max_tokens: nothing is written;   tok < 0: stop = 2;   eos_id >= 0 and tok == eos_id: stop = 1;   otherwise
+ *   tokens[n_tokens++] = tok; input_ids[0] = tok; position_ids[0] = len; row = len; len = len + 1.
+ * input_ids / position_ids: the int64 staging buffers of the pass; tokens: device int64 [max_tokens]. */
+int osg_decode_pick(osg_ctx* ctx, const float* logits, long T, long V, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
+                    int64_t* tokens, long max_tokens);
+/* cache[h][*row][0..d) = src[h][0..d) for h < kv_heads: the new key or value row of every head, f16 [kv_heads][d], into a capacity buffer
+ * [kv_heads][cap][d] at the row a device int names (state + 0).  A row outside [0, cap) writes nothing. */
+int osg_kv_append_at(osg_ctx* ctx, const void* src, void* cache, const int* row, int kv_heads, long cap, int d);
+/* osg_sdpa for ONE query row over such capacity buffers: k / v [B][Hkv][cap][D] with the head and batch strides given (elements), the number of keys
+ * read from device memory at kernel entry (tkv = state + 1, clamped into [1, cap]); mask [cap] additive, required.  It launches the instantiation
+ * osg_sdpa launches for (Tq = 1, that Tkv, D, mask present) with the same arithmetic: the output has the bits of osg_sdpa on dense [B][Hkv][Tkv][D]
+ * copies.  Rows at and past the length are never read. */
+int osg_sdpa_len(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, const void* v, const void* mask, void* o, const int* tkv,
+                 long kv_head_stride, long kv_batch_stride, long cap, int batch, int q_heads, int kv_heads, int D, float scale);
+
 /* ---- normalisation / reductions ---------------------------------------------------------------------------- */
 /* InstanceNormalization on [rows, L] (reference input [1,G,L], onnxstream.cpp:4788-5055): per row mean/var in f32,
  * y = scale[row % n_scale]*(x-mean)/sqrt(var+eps)+bias[row % n_scale]; scale/bias are f32 (forced f32 at :4802). */

@@ -341,6 +341,56 @@ class Model:
                     ctypes.byref(ms)))
         return ms.value
 
+    def generate(self, max_new: int, n_caches: int, eos_id: int = -1, sync_every: int = 0, trace: bool = False, ids: str = "input_ids",
+                 pos: str = "position_ids", mask: str = "attention_mask", logits: str = "logits", cache_in: str = "pkv", cache_out: str = "opkv"):
+        """The LLM app's greedy token loop on the device (model_hip_generate): after a run() over the prompt has left `logits` (fp32) and the caches
+        `cache_out`<i> (fp16, i < n_caches) in the Model, up to max_new tokens are picked (the app's argmax) and run through the resident T = 1 plan
+        without a host round trip per token; the caches and the last logits are left as the host loop would leave them.  Returns
+        (tokens int64 [n_tokens], stop, trace float32 [n_tokens, V] or None, device ms); stop: 0 budget spent, 1 eos_id picked, 2 invalid argmax.
+        sync_every > 0: the stop code is read after every sync_every passes and the call ends early."""
+        import numpy as np
+        f = self._lib.model_hip_generate
+        cp, ip = ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)
+        f.argtypes = [ctypes.c_void_p, cp, cp, cp, cp, cp, cp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), ip, ip,
+                      ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)]
+        f.restype = ctypes.c_void_p
+        toks = np.zeros(max(int(max_new), 1), np.int64)
+        tr = None
+        if trace:
+            got = self.get_tensor(logits)          # (a copy: the Model keeps its tensor)
+            if got is None:
+                raise OnnxStreamError("Model::hip_generate: tensor not found: " + logits)
+            tr = np.zeros((max(int(max_new), 1), got[1][-1]), np.float32)
+        n, stop, ms = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0)
+        self._err(f(self._h, self._name(ids), self._name(pos), self._name(mask), self._name(logits), self._name(cache_in), self._name(cache_out), int(n_caches),
+                    int(max_new), int(eos_id), int(sync_every), toks.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), ctypes.byref(n), ctypes.byref(stop),
+                    tr.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if tr is not None else None, ctypes.byref(ms)))
+        return toks[:n.value].copy(), stop.value, (tr[:n.value].copy() if tr is not None else None), ms.value
+
+    def get_tensor_f16(self, name: str):
+        """The bits of a float16 tensor of Model::m_data (an output kept out of m_outputs_convert_set, e.g. a key/value cache of the LLM flow) as a
+        numpy float16 array; a device-resident tensor is copied from where it lies and stays there (model_hip_get_tensor_f16)."""
+        import numpy as np
+        f = self._lib.model_hip_get_tensor_f16
+        f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_ulonglong, ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_int)]
+        f.restype = ctypes.c_void_p
+        shape, rank = (ctypes.c_ulonglong * 8)(), ctypes.c_int(0)
+        self._err(f(self._h, self._name(name), None, 0, shape, ctypes.byref(rank)))
+        out = np.empty([int(shape[k]) for k in range(rank.value)], np.float16)
+        self._err(f(self._h, self._name(name), out.ctypes.data, out.size, shape, ctypes.byref(rank)))
+        return out
+
+    def hip_decode_plan_info(self) -> str:
+        """The decode plan `generate` built, as hip_plan_info gives a plan; its first line is "decode capacity <rows>"."""
+        f = self._lib.model_hip_decode_plan_info
+        f.argtypes = [ctypes.c_void_p]; f.restype = ctypes.c_void_p
+        p = f(self._h)
+        text = ctypes.cast(p, ctypes.c_char_p).value.decode("utf-8", "replace")
+        self._lib.model_free_buffer(p)
+        if text.startswith("ERROR: "):
+            raise OnnxStreamError(text[7:])
+        return text
+
     def set_upcast_substrings(self, subs):
         """Model::m_requires_upcast (a std::function in C++, src/llm.cpp:379-383): ops whose name contains one of `subs` run in fp32.  Works on
         libonnxstream_amd.so (model_hip_set_upcast_substrings) and on the oracle build of the reference (ref_set_upcast_substrings)."""

@@ -301,6 +301,34 @@ char* model_hip_fetch_tensor(Handle* h, char* name) {
         return dup_cstr(e.what());
     }
 }
+// the bits of a float16 tensor of m_data (an output kept out of m_outputs_convert_set: the LLM flow's caches), which model_get_tensor cannot hand out.
+// shape: [8] (receives the dims), *rank their number; dst (may be NULL: shape only) receives dst_elems halves, which must be the tensor's element count.
+// A device-resident tensor is read where it lies and stays there.
+char* model_hip_get_tensor_f16(Handle* h, char* name, unsigned short* dst, unsigned long long dst_elems, unsigned long long* shape, int* rank) {
+    try {
+        for (auto& t : h->model.m_data)
+            if (t.m_name == name) {
+                if (t.m_type != TensorDataType::float16) throw std::invalid_argument("Model::hip_get_tensor_f16: tensor is not float16: " + std::string(name));
+                if (t.m_shape.size() > 8) throw std::invalid_argument("Model::hip_get_tensor_f16: rank > 8.");
+                size_t n = 1;
+                for (size_t k = 0; k < t.m_shape.size(); k++) { shape[k] = t.m_shape[k]; n *= t.m_shape[k]; }
+                *rank = (int)t.m_shape.size();
+                if (!dst) return nullptr;
+                if (dst_elems != n) throw std::invalid_argument("Model::get_tensor_data: mismatch between tensor shape and data size.");
+                if (t.m_hip_resident) {
+                    if (t.m_hip_resident_bytes != n * 2) throw std::invalid_argument("Model::get_tensor_data: mismatch between tensor shape and data size.");
+                    Plan::read_resident(h->model, t, dst);
+                } else {
+                    if (t.get_vector<uint16_t>().size() != n) throw std::invalid_argument("Model::get_tensor_data: mismatch between tensor shape and data size.");
+                    std::memcpy(dst, t.get_vector<uint16_t>().data(), n * 2);
+                }
+                return nullptr;
+            }
+        throw std::invalid_argument("Model::hip_get_tensor_f16: tensor not found: " + std::string(name));
+    } catch (const std::exception& e) {
+        return dup_cstr(e.what());
+    }
+}
 int model_hip_rename_tensor(Handle* h, char* from, char* to) {
     for (auto& t : h->model.m_data)
         if (t.m_name == from) { t.m_name = to; return 1; }
@@ -421,6 +449,47 @@ char* model_hip_decode(Handle* h, char* in_name, char* out_name, int images, int
         return nullptr;
     } catch (const std::exception& e) {
         return dup_cstr(e.what());
+    }
+}
+// the reference LLM app's greedy token loop (src/llm.cpp:472-496) on the device: one call, one plan, one synchronisation for up to max_new tokens.  The Model is
+// configured as the app configures it (dynamic shapes, fp16 arithmetic, m_use_scaled_dp_attn_op, `logits_name` the only converted output, the caches extra
+// outputs) and a run() over the prompt has left the fp32 logits [1, T, V] and the fp16 caches <cache_out_prefix><i> [1, Hkv, P, d], i < n_caches, in m_data (host
+// tensors, or device-resident under hip_resident_outputs).  The call computes what this host loop computes:
+//     L = last row of logits
+//     for n in 0 .. max_new-1:
+//         tok = argmax(L)                    the app's scan, src/llm.cpp:355-370: starts at -1.0f, takes v >= prev (the LAST of equal maxima; NaN never; -1 if none)
+//         if tok < 0:        stop = 2; break
+//         if tok == eos_id:  stop = 1; break      (eos_id < 0: never)
+//         tokens[n_tokens++] = tok
+//         rename <cache_out_prefix><i> -> <cache_in_prefix><i>; push ids_name = [[tok]], pos_name = [[P]], mask_name = ones(1, P+1); run()
+//         P += 1;  L = last row of logits
+//     stop = 0 when the budget ran out
+// and leaves m_data as that loop would: the caches [1, Hkv, P_final, d] where they were (host or device), logits [1, 1, V] of the last pass that ran (both
+// untouched if none ran).  tokens: [max_new] int64; logits_trace (may be NULL): [max_new, V] fp32, row n = the logits of pass n (copied on the device per pass,
+// downloaded once).  sync_every > 0: the host reads the stop code after every sync_every passes and ends early; 0: everything is enqueued, one wait at the
+// end.  *ms (may be NULL) receives the device time of the loop.  The T = 1 plan behind it is built on the first call and kept while its cache capacity
+// (>= P + max_new) and the options suffice; run()'s own plan is not touched.
+char* model_hip_generate(Handle* h, const char* ids_name, const char* pos_name, const char* mask_name, const char* logits_name, const char* cache_in_prefix,
+                         const char* cache_out_prefix, int n_caches, int max_new, long long eos_id, int sync_every, long long* tokens, int* n_tokens, int* stop,
+                         float* logits_trace, double* ms) {
+    try {
+        Plan::DecodeSpec spec;
+        spec.ids = ids_name; spec.pos = pos_name; spec.mask = mask_name; spec.logits = logits_name;
+        spec.cache_in = cache_in_prefix; spec.cache_out = cache_out_prefix; spec.n_caches = n_caches;
+        static_assert(sizeof(long long) == sizeof(int64_t), "tokens are int64");
+        const double v = Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace);
+        if (ms) *ms = v;
+        return nullptr;
+    } catch (const std::exception& e) {
+        return dup_cstr(e.what());
+    }
+}
+// steps of the decode plan model_hip_generate built, as model_hip_plan_info gives them, after a first line "decode capacity <CAP>"; "ERROR: ..." on error
+char* model_hip_decode_plan_info(Handle* h) {
+    try {
+        return dup_cstr(Plan::decode_info(h->model));
+    } catch (const std::exception& e) {
+        return dup_cstr(std::string("ERROR: ") + e.what());
     }
 }
 // steps and arena placement of the current plan (malloc'ed text, free with model_free_buffer); "ERROR: ..." on error

@@ -1292,6 +1292,13 @@
                                      "ConstantOfShape", "Less", "Greater", "Equal", "And", "Where", "Expand", "Trilu"};
         bool known = false;
         for (auto* k : kOps) known |= t == k;
+        if (P.decode)   // decode plans: the token and its position exist on the device only -- a Gather may index with them, nothing else may read them
+            for (size_t k = 0; k < op.m_input.size(); k++) {
+                auto it = op.m_input[k].m_name.empty() || is_const_tensor(op.m_input[k]) ? P.by_name.end() : P.by_name.find(op.m_input[k].m_name);
+                if (it == P.by_name.end() || !P.vals[P.root_of(it->second)].dev_int || (t == "Gather" && k == 1)) continue;
+                throw std::runtime_error("Model::hip_generate: " + t + " (" + op.m_name + ") needs the value of '" + P.vals[P.root_of(it->second)].name +
+                                         "' while the plan is built; in the device token loop it exists on the device only.");
+            }
         if (!known || op.m_input.empty() || op.m_output.size() != 1) return false;
         std::vector<const Val*> in;
         bool any_value = false;

@@ -3,6 +3,8 @@
     void lower(const Operation& op) {
         const std::string& t = op.m_type;
         if (try_host_eval(op)) return;
+        if (P.decode && t != "Concat" && t != "ScaledDotProductAttention" && t != "Unsqueeze" && t != "Reshape" && t != "Expand")
+            for (auto& ti : op.m_input) if (reads_kv_cap(ti)) refuse_kv_cap(op);   // (only the length-aware launches may read a capacity buffer)
         if (P.u8) return lower_u8(op);
         if (t == "Gather") return lower_gather(op);
         if (t == "Cast") return lower_cast(op);
@@ -48,6 +50,18 @@
 
     static void need(const Operation& op, bool cond, const char* msg) {
         if (!cond) throw std::invalid_argument(op.m_type + ": " + msg);
+    }
+
+    // decode plans: does this operand live in a key/value capacity buffer (rows past the device-side length hold nothing)?
+    bool reads_kv_cap(const Tensor& t) const {
+        if (!P.decode || t.m_name.empty() || is_const_tensor(t)) return false;
+        auto it = P.by_name.find(t.m_name);
+        if (it == P.by_name.end()) return false;
+        const Val& v = P.vals[P.root_of(it->second)];
+        return v.kv_cap || (v.rep_src >= 0 && P.vals[P.root_of(v.rep_src)].kv_cap);
+    }
+    [[noreturn]] static void refuse_kv_cap(const Operation& op) {
+        throw std::runtime_error("Model::hip_generate: " + op.m_type + " (" + op.m_name + ") reads a key/value cache in a form the device token loop does not implement.");
     }
 
     // Conv (reference :4494-4707 -> XnnPack::convolution :1292): group 1, dilation 1, pads re-centred (:1315-1329)
@@ -725,6 +739,7 @@
             V(y).rep = os[2];
             return;
         }
+        if (reads_kv_cap(op.m_input[0])) refuse_kv_cap(op);
         const size_t prank = os.size() + 1;
         need(op, prank <= 6, "rank too large for the device broadcast kernel.");
         const long n_ones = prod(on);
@@ -1156,6 +1171,18 @@
         need(op, scale > 0.f, "a scale <= 0 is not implemented on the HIP backend.");
         const int y = out_val(op, Shape{Bq, Hq, T, Dv}, Lay::plain, V(q).batched);
         const long nb = Bq * B(q);
+        const bool k_cap = V(P.root_of(k)).kv_cap, v_cap = V(P.root_of(v)).kv_cap;
+        if (k_cap || v_cap) {
+            // decode plans: key and value are capacity buffers [Hkv][CAP][D] (S == CAP here), the number of keys is the device-side cache length
+            if (!(k_cap && v_cap && T == 1 && nb == 1 && S == P.dspec.cap && V(k).view_off == 0 && V(v).view_off == 0)) refuse_kv_cap(op);
+            const long cap = S;
+            P.add_step("ScaledDotProductAttention(len) " + op.m_name, {q, k, mk, v}, {y}, [=, this] {
+                be.check(be.api.osg_sdpa_len(be.ctx, OSG_F16, P.ptr(q), P.ptr(k), P.ptr(v), P.ptr(mk), P.ptr(y), P.dec_state + 1, cap * D, cap * D * Hkv, cap, 1, (int)Hq,
+                                             (int)Hkv, (int)D, scale),
+                         "ScaledDotProductAttention");
+            });
+            return;
+        }
         P.add_step("ScaledDotProductAttention " + op.m_name, {q, k, mk, v}, {y}, [=, this] {
             be.check(be.api.osg_sdpa(be.ctx, OSG_F16, P.ptr(q), P.ptr(k), P.ptr(v), P.ptr(mk), P.ptr(y), (int)nb, (int)Hq, (int)Hkv, (int)T, (int)S, (int)D, scale),
                      "ScaledDotProductAttention");
@@ -1393,6 +1420,29 @@
         const int rank = (int)V(xs[0]).shape.size();
         if (axis < 0) axis += rank;
         need(op, axis >= 0 && axis < rank, "invalid axis.");
+        if (P.decode) {
+            // decode plans: the cache Concat (axis 2; operands the graph input <cache_in><i> and the one new row; result <cache_out><i>) appends in place --
+            // the result aliases the capacity buffer, the row comes from the device-side state
+            const int ci = is_const_tensor(op.m_input[0]) ? -1 : P.cache_index(op.m_input[0].m_name, P.dspec.cache_in);
+            bool touches = false;
+            for (int x : xs) touches |= V(P.root_of(x)).kv_cap;
+            if (ci >= 0 && V(P.root_of(xs[0])).kv_cap) {
+                const int c = xs[0], r = xs.size() == 2 ? P.ensure_plain(xs[1]) : -1;
+                const Shape cs = V(c).shape;
+                need(op, r >= 0 && axis == 2 && rank == 4 && op.m_output.size() == 1 && P.cache_index(op.m_output[0].m_name, P.dspec.cache_out) == ci,
+                     "in the device token loop a cache is concatenated with one new row along axis 2 into its output.");
+                need(op, V(r).shape == Shape{1, cs[1], 1, cs[3]} && V(r).dtype == OSG_F16 && V(c).dtype == OSG_F16 && V(r).ld == 0, "invalid shape of the new cache row.");
+                const Shape os{1, cs[1], P.dspec.cap, cs[3]};
+                check_out(op, os);
+                const int y = P.alias(c, os, Lay::plain, op.m_output[0].m_name);
+                const long Hkv = cs[1], d = cs[3], cap = P.dspec.cap;
+                P.add_step("KVAppend " + op.m_name, {r, c}, {y}, [=, this] {
+                    be.check(be.api.osg_kv_append_at(be.ctx, P.ptr(r), P.ptr(y), P.dec_state, (int)Hkv, cap, (int)d), "osg_kv_append_at");
+                });
+                return;
+            }
+            if (touches) throw std::runtime_error("Model::hip_generate: Concat (" + op.m_name + ") reads a key/value cache in a form the device token loop does not implement.");
+        }
         bool all_nhwc = rank == 4 && axis == 1;
         for (int x : xs) all_nhwc &= V(x).lay == Lay::nhwc;
         bool batched = false;

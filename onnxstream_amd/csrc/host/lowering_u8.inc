@@ -436,8 +436,15 @@
             if (a.first == "axis") axis = std::stoi(a.second);
             else throw std::invalid_argument(op.m_type + ": unrecognized attribute: " + a.first + ".");
         }
-        const Val* iv = hval(op.m_input[1]);
-        need(op, iv && iv->dtype == OSG_I64 && iv->host_valid, "wrong data type of indices.");
+        // decode plans: the indices are a device value (the token / its position, Val::dev_int) -- the launch reads the staging buffer itself, and
+        // Plan::generate checks the table's rows against what the loop can produce (dec_tok_limit / dec_pos_limit)
+        int dev_idx = -1;
+        if (P.decode && !is_const_tensor(op.m_input[1])) {
+            auto it = P.by_name.find(op.m_input[1].m_name);
+            if (it != P.by_name.end() && V(P.root_of(it->second)).dev_int) dev_idx = it->second;
+        }
+        const Val* iv = dev_idx >= 0 ? &P.vals[dev_idx] : hval(op.m_input[1]);
+        need(op, iv && iv->dtype == OSG_I64 && (iv->host_valid || dev_idx >= 0), "wrong data type of indices.");
         int x = P.ensure_plain(in_val(op.m_input[0]));
         Shape xs = V(x).shape;
         if (axis < 0) axis += (int)xs.size();
@@ -469,15 +476,21 @@
             if (i < 0) i += dim;
             need(op, i >= 0 && i < dim, "invalid index in indices.");
         }
-        const int idev = P.new_val("", {(long)idx.size()}, OSG_I64, Lay::plain, false);
-        V(idev).is_const = true;
-        bool fresh;
-        std::string tag = "gather|" + op.m_name;
-        V(idev).dptr = P.const_alloc(tag, std::max<size_t>(idx.size() * 8, 8), &fresh);
-        be.check(be.api.osg_upload_sync(be.ctx, V(idev).dptr, idx.data(), idx.size() * 8), "osg_upload_sync");
+        int idev = dev_idx;
+        if (dev_idx >= 0) {
+            long& limit = V(P.root_of(dev_idx)).name == P.dspec.pos ? P.dec_pos_limit : P.dec_tok_limit;
+            limit = std::min(limit, dim);
+        } else {
+            idev = P.new_val("", {(long)idx.size()}, OSG_I64, Lay::plain, false);
+            V(idev).is_const = true;
+            bool fresh;
+            std::string tag = "gather|" + op.m_name;
+            V(idev).dptr = P.const_alloc(tag, std::max<size_t>(idx.size() * 8, 8), &fresh);
+            be.check(be.api.osg_upload_sync(be.ctx, V(idev).dptr, idx.data(), idx.size() * 8), "osg_upload_sync");
+        }
         int y = out_val(op, os, Lay::plain, V(x).batched, V(x).dtype);
         const int es = (int)esize(V(x).dtype);
-        const long nb = B(x), n_idx = (long)idx.size(), per_in = V(x).numel(), per_out = n_idx * els;
+        const long nb = B(x), n_idx = dev_idx >= 0 ? V(dev_idx).numel() : (long)idx.size(), per_in = V(x).numel(), per_out = n_idx * els;
         P.add_step("Gather " + op.m_name, {x, idev}, {y}, [=, this] {
             for (long b = 0; b < nb; b++)
                 be.check(be.api.osg_gather_rows(be.ctx, es, (const char*)P.ptr(x) + b * per_in * es, (const int64_t*)P.ptr(idev), (char*)P.ptr(y) + b * per_out * es, n_idx,

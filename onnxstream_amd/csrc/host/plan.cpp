@@ -157,6 +157,17 @@ int Plan::new_val(const std::string& name, const Shape& shape, osg_dtype dt, Lay
     return id;
 }
 
+int Plan::cache_index(const std::string& name, const std::string& prefix) const {
+    if (name.size() <= prefix.size() || name.compare(0, prefix.size(), prefix) != 0) return -1;
+    long i = 0;
+    for (size_t k = prefix.size(); k < name.size(); k++) {
+        if (name[k] < '0' || name[k] > '9' || (k == prefix.size() && name[k] == '0' && name.size() > k + 1)) return -1;
+        i = i * 10 + (name[k] - '0');
+        if (i >= dspec.n_caches) return -1;
+    }
+    return (int)i;
+}
+
 int Plan::root_of(int v) const {
     while (vals[v].root >= 0) v = vals[v].root;
     return v;
@@ -400,6 +411,9 @@ Plan::~Plan() {
     if (dec_lat) be.api.osg_free(be.ctx, dec_lat);
     if (dec_img) be.api.osg_free(be.ctx, dec_img);
     if (dec_pix) be.api.osg_free(be.ctx, dec_pix);
+    if (dec_state) be.api.osg_free(be.ctx, dec_state);
+    if (dec_tokens) be.api.osg_free(be.ctx, dec_tokens);
+    if (dec_trace) be.api.osg_free(be.ctx, dec_trace);
     if (ring) be.free(ring);
     for (void* p : owned) be.free(p);
     if (arena && !arena_pooled) be.free(arena);
@@ -477,7 +491,7 @@ void Plan::build() {
         }
         for (const std::string& iname : (reuse && !pool.in_names.empty()) ? pool.in_names : found) {
             Tensor* src = nullptr;
-            for (auto& t : m.m_data)
+            for (auto& t : build_inputs ? *build_inputs : m.m_data)
                 if (t.m_name == iname) { src = &t; break; }
             if (!src) throw std::invalid_argument("Model::get_tensor_data: input tensor not found: " + iname);
             if (src->m_type != TensorDataType::float32 && src->m_type != TensorDataType::int64 && !(src->m_type == TensorDataType::float16 && fp16 && !u8))
@@ -490,6 +504,15 @@ void Plan::build() {
             if (src->m_type == TensorDataType::int64) {
                 // token ids / positions / masks of the LLM graphs: values known now, consumed by plan-time evaluation (Lowering::try_host_eval)
                 if (u8 || N != 1) throw std::invalid_argument("Model::run: int64 graph inputs need one sample per pass and floating-point arithmetic (" + iname + ").");
+                if (decode && (iname == dspec.ids || iname == dspec.pos)) {
+                    // the token and its position change per pass and are written on the device (osg_decode_pick): a staging buffer, no plan-time value
+                    inp.staging = inp.val = new_val(iname, shape, OSG_I64, Lay::plain, false);
+                    vals[inp.val].dptr = small_alloc(std::max<size_t>(val_bytes(inp.val), 8));
+                    vals[inp.val].pinned = true;
+                    vals[inp.val].dev_int = true;
+                    inputs.push_back(std::move(inp));
+                    continue;
+                }
                 auto& iv = src->get_vector<int64_t>();
                 inp.ivals.assign(iv.begin(), iv.end());
                 inp.staging = inp.val = new_val(iname, shape, OSG_I64, Lay::plain, false);
@@ -515,7 +538,14 @@ void Plan::build() {
                 // opkv* -> pkv* renaming (src/llm.cpp:403-407).  Uploaded as it is, no rounding step.
                 if (N != 1) throw std::invalid_argument("Model::run: float16 graph inputs need one sample per pass (" + iname + ").");
                 inp.staging = inp.val = new_val(iname, shape, OSG_F16, Lay::plain, true);
-                vals[inp.val].dptr = small_alloc(val_bytes(inp.val));
+                if (decode && cache_index(iname, dspec.cache_in) >= 0) {
+                    // a cache of the decode plan: [1, Hkv, CAP - 1, d] by its shape, in a buffer of CAP rows per head -- the Concat appends in place (lower_concat)
+                    if (shape.size() != 4 || shape[0] != 1 || shape[2] != dspec.cap - 1)
+                        throw std::invalid_argument("Model::hip_generate: cache '" + iname + "' must be a [1, Hkv, P, d] tensor.");
+                    vals[inp.val].dptr = small_alloc((size_t)shape[1] * dspec.cap * shape[3] * 2);
+                    vals[inp.val].kv_cap = true;
+                } else
+                    vals[inp.val].dptr = small_alloc(val_bytes(inp.val));
                 vals[inp.val].pinned = true;
                 inputs.push_back(std::move(inp));
                 continue;
@@ -588,6 +618,13 @@ void Plan::build() {
             o.name = nme;
             o.val = v;
             for (long d : vals[v].shape) o.shape.push_back((size_t)d);
+            if (decode && vals[root_of(v)].kv_cap) {
+                // a cache output of the decode plan IS its capacity buffer: no copy per pass, Plan::generate compacts it into a tensor at the end of the call
+                o.f32val = v;
+                o.raw16 = true;
+                outputs.push_back(std::move(o));
+                continue;
+            }
             if (!outputs_convert_set.empty() && !outputs_convert_set.count(nme) && vals[v].dtype == OSG_F16) {
                 // m_outputs_convert_set (reference :8234): only the listed outputs are converted back to fp32 at the end of run(); the others
                 // stay in the arithmetic type (f16 bits; here always in the logical layout).  A pinned f16 copy is what the caller reads.

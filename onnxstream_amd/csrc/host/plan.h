@@ -57,6 +57,11 @@ struct Val {
     // never materialised -- the attention launch reads `rep_src` with Hkv heads (plan.cpp lower_expand / lower_sdpa)
     int rep_src = -1;
     long rep = 1;
+    // decode plans (Plan::generate): an int64 graph input whose VALUE lives on the device only (input_ids / position_ids, written by osg_decode_pick):
+    // a Gather reads it as its index buffer, nothing may evaluate it at plan time
+    bool dev_int = false;
+    // decode plans: a key/value cache in its capacity buffer [Hkv][CAP][d] -- valid rows are counted on the device (Plan::dec_state)
+    bool kv_cap = false;
     long numel() const { long n = 1; for (auto d : shape) n *= d; return n; }
 };
 
@@ -142,7 +147,13 @@ struct ConstPool {
         }
         spare.push_back({p, bytes});
     }
+    // the resident decode plan of the Model (Plan::generate): T = 1 over key/value caches of a fixed capacity, kept across generate calls while the
+    // capacity and the options it was built with (`decode_key`) still fit
+    Plan* decode_plan = nullptr;
+    std::string decode_key;
+    void drop_decode();          // (plan_run.cpp: Plan is incomplete here)
     void clear(HipBackend& be) {
+        drop_decode();           // (first: its buffers go back to the lists freed below)
         for (auto& kv : base) be.free(kv.second.dptr);
         for (auto& kv : derived) be.free(kv.second.first);
         for (auto& sp : spare) be.free(sp.first);
@@ -321,6 +332,28 @@ struct Plan {
     void* dec_img = nullptr;
     void* dec_pix = nullptr;
     size_t dec_lat_bytes = 0, dec_img_bytes = 0, dec_pix_bytes = 0;
+
+    // ---- decode mode: the resident T = 1 plan of the token loop (generate, below) ----
+    // Built by the ordinary lowering over `build_inputs` (stand-ins for the graph inputs: one token, caches of CAP - 1 rows, a mask of CAP ones) instead of
+    // m.m_data.  input_ids / position_ids are device values (Val::dev_int), the cache inputs live in capacity buffers [Hkv][CAP][d] (Val::kv_cap), a cache
+    // Concat is osg_kv_append_at in place and the attention over it osg_sdpa_len: the pass is the same launches for every token and every cache length.
+    struct DecodeSpec { std::string ids, pos, mask, logits, cache_in, cache_out; int n_caches = 0; long cap = 0; };
+    bool decode = false;
+    DecodeSpec dspec;
+    std::vector<Tensor>* build_inputs = nullptr;
+    int* dec_state = nullptr;                 // device int32[4]: row, len, n_tokens, stop (include/osgpu.h, osg_decode_pick)
+    long dec_pos_limit = 1L << 62, dec_tok_limit = 1L << 62;   // rows of the smallest table a Gather indexes with position_ids / input_ids
+    void* dec_tokens = nullptr;               // device int64 [max_new]
+    void* dec_trace = nullptr;                // device fp32 [max_new, V]
+    size_t dec_tokens_bytes = 0, dec_trace_bytes = 0;
+    int cache_index(const std::string& name, const std::string& prefix) const;   // i of "<prefix><i>", i < n_caches; -1 otherwise
+    // the reference app's token loop (src/llm.cpp:472-496) on the device: see model_hip_generate (exports.cpp) for the contract.  A static member of Plan
+    // for the reason given at run_sampler_loop_multistep; the decode plan itself is kept in the Model's ConstPool.
+    static double generate(Model& m, const DecodeSpec& names, int max_new, long long eos_id, int sync_every, int64_t* tokens, int* n_tokens, int* stop,
+                           float* logits_trace);
+    static std::string decode_info(Model& m);
+    // a copy of a device-resident tensor's bytes (Tensor::m_hip_resident) for the host; the tensor stays where it is (model_hip_get_tensor_f16)
+    static void read_resident(Model& m, const Tensor& t, void* dst);
 
     osg_graph* graph = nullptr;
     Lowering* lowering = nullptr;  // kept alive: the launch closures capture it

@@ -4,6 +4,7 @@
 #include "qu8.h"
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -807,9 +808,292 @@ double Plan::run_decode(Model& m, const std::string& in_name, const std::string&
     return ms;
 }
 
+void ConstPool::drop_decode() {
+    delete decode_plan;
+    decode_plan = nullptr;
+    decode_key.clear();
+}
+
+void Plan::read_resident(Model& m, const Tensor& t, void* dst) {
+    if (!m.m_backend) throw std::runtime_error("Model::hip_get_tensor_f16: no backend.");
+    m.m_backend->check(m.m_backend->api.osg_download(m.m_backend->ctx, dst, t.m_hip_resident.get(), t.m_hip_resident_bytes), "osg_download");
+}
+
+std::string Plan::decode_info(Model& m) {
+    if (!m.m_pool || !m.m_pool->decode_plan) throw std::runtime_error("Model::hip_decode_plan_info: no decode plan (call model_hip_generate first).");
+    return m.m_pool->decode_plan->info();
+}
+
+// The reference app's token loop (src/llm.cpp:472-496) with the argmax, the cache append and the cache length on the device: max_new x (osg_decode_pick + the
+// T = 1 pass of the Model's resident decode plan) enqueued back to back.  model_hip_generate (exports.cpp) states the contract.
+double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long eos_id, int sync_every, int64_t* tokens, int* n_tokens, int* stop,
+                      float* logits_trace) {
+    static const std::string fn = "Model::hip_generate: ";
+    if (n_tokens) *n_tokens = 0;
+    if (stop) *stop = 0;
+    if (max_new < 0) throw std::invalid_argument(fn + "max_new must be >= 0.");
+    if (names.n_caches <= 0) throw std::invalid_argument(fn + "needs at least one key/value cache.");
+    if (!m.m_plan || !m.m_backend || !m.m_pool || m.m_plan->runs < 1)
+        throw std::runtime_error(fn + "run() once first (the prompt's logits and key/value caches must be in the Model).");
+    if (m.m_use_uint8_arithmetic) throw std::runtime_error(fn + "not available with uint8 arithmetic.");
+    if (m.m_hip_stream_weights || m.m_cuda_options.m_vram_to_use > 0) throw std::runtime_error(fn + "not available in streamed-weights mode.");
+    if (!m.m_use_fp16_arithmetic) throw std::runtime_error(fn + "needs fp16 arithmetic (m_use_fp16_arithmetic).");
+    if (!m.m_use_scaled_dp_attn_op)
+        throw std::runtime_error(fn + "needs m_use_scaled_dp_attn_op (the op-by-op attention chain is not implemented in the device token loop).");
+    if (!m.m_support_dynamic_shapes) throw std::runtime_error(fn + "needs m_support_dynamic_shapes.");
+    if (tokens == nullptr && max_new > 0) throw std::invalid_argument(fn + "no buffer for the tokens.");
+    auto find = [&](const std::string& name) -> Tensor& {
+        for (auto& t : m.m_data)
+            if (t.m_name == name) return t;
+        throw std::invalid_argument(fn + "tensor not found: " + name);
+    };
+    // ---- what the previous run() left: the logits [1, T, V] fp32 and the caches [1, Hkv, P, d] fp16 (host or device-resident) ----
+    Tensor& lg = find(names.logits);
+    if (lg.m_type != TensorDataType::float32)
+        throw std::invalid_argument(fn + "the logits tensor '" + names.logits + "' must be float32 (list it in m_outputs_convert_set).");
+    if (lg.m_shape.size() < 2) throw std::invalid_argument(fn + "the logits tensor '" + names.logits + "' must be [1, T, V].");
+    size_t lead = 1;
+    for (size_t k = 0; k + 2 < lg.m_shape.size(); k++) lead *= lg.m_shape[k];
+    if (lead != 1 || lg.m_batch) throw std::invalid_argument(fn + "the batch must be 1.");
+    const long T0 = (long)lg.m_shape[lg.m_shape.size() - 2], V = (long)lg.m_shape.back();
+    if (T0 < 1 || V < 1 || lg.get_vector<float>().size() != (size_t)(T0 * V)) throw std::invalid_argument(fn + "the logits tensor '" + names.logits + "' is empty.");
+    long P = -1;
+    std::vector<std::array<long, 2>> geo;      // (Hkv, d) per cache
+    for (int i = 0; i < names.n_caches; i++) {
+        const std::string cn = names.cache_out + std::to_string(i);
+        Tensor& c = find(cn);
+        if (c.m_type != TensorDataType::float16) throw std::invalid_argument(fn + "cache '" + cn + "' must be float16 (keep it out of m_outputs_convert_set).");
+        if (c.m_shape.size() != 4) throw std::invalid_argument(fn + "cache '" + cn + "' must be a [1, Hkv, P, d] tensor.");
+        if (c.m_shape[0] != 1 || c.m_batch) throw std::invalid_argument(fn + "the batch must be 1.");
+        if (P >= 0 && (long)c.m_shape[2] != P) throw std::invalid_argument(fn + "the caches differ in length.");
+        P = (long)c.m_shape[2];
+        const size_t bytes = c.m_shape[1] * c.m_shape[2] * c.m_shape[3] * 2;
+        if (P < 1 || bytes == 0 || (c.m_hip_resident ? c.m_hip_resident_bytes : c.get_vector<uint16_t>().size() * 2) != bytes)
+            throw std::invalid_argument(fn + "cache '" + cn + "' is empty or its data does not match its shape.");
+        geo.push_back({(long)c.m_shape[1], (long)c.m_shape[3]});
+    }
+    if (max_new == 0) return 0.0;
+    HipBackend& be = *m.m_backend;
+    ConstPool& pool = *m.m_pool;
+    // ---- the resident decode plan: kept while its capacity and the options it was built with still fit ----
+    std::string key = names.ids + "|" + names.pos + "|" + names.mask + "|" + names.logits + "|" + names.cache_in + "|" + names.cache_out + "|" + std::to_string(names.n_caches) +
+                      "|" + std::to_string(V) + "|" + std::to_string(m.m_hip_fusion_level) + (m.m_hip_fuse_ln_gemm ? "l" : "-") + (m.m_hip_concat_views ? "c" : "-") +
+                      (m.m_hip_fuse_tblock ? "t" : "-") + (m.m_hip_autotune ? "a" : "-") + (m.m_hip_w8_resident ? "8" : "-") + (m.m_fuse_ops_in_attention ? "f" : "-") +
+                      (m.m_hip_resident_outputs ? "r" : "-") + "|" + std::to_string(m.m_hip_gn_stats) + "|";
+    for (auto& g : geo) key += std::to_string(g[0]) + "x" + std::to_string(g[1]) + ",";
+    key += "|";
+    for (auto& e : m.m_extra_outputs) key += e + ",";
+    key += "|";
+    for (auto& e : m.m_outputs_convert_set) key += e + ",";
+    key += "|";
+    if (m.m_requires_upcast)
+        for (auto& op : m.m_ops) key += m.m_requires_upcast(op.m_type, op.m_name) ? '1' : '0';
+    Plan* dp = pool.decode_plan;
+    if (dp && (pool.decode_key != key || dp->dspec.cap < P + max_new)) {
+        pool.drop_decode();
+        dp = nullptr;
+    }
+    if (!dp) {
+        const long cap = (P + max_new + 63) / 64 * 64;
+        std::vector<Tensor> fake;      // stand-ins for the graph inputs: shapes and types, the mask's ones; the token and its position have no plan-time value
+        auto push_i64 = [&](const std::string& name, std::vector<size_t> shape, size_t n, int64_t v) {
+            Tensor t;
+            t.m_name = name;
+            t.m_shape = std::move(shape);
+            t.set_vector(tensor_vector<int64_t>(n, v));
+            fake.push_back(std::move(t));
+        };
+        push_i64(names.ids, {1, 1}, 1, 0);
+        push_i64(names.pos, {1, 1}, 1, 0);
+        push_i64(names.mask, {1, (size_t)cap}, (size_t)cap, 1);
+        for (int i = 0; i < names.n_caches; i++) {
+            Tensor t;
+            t.m_name = names.cache_in + std::to_string(i);
+            t.m_shape = {1, (size_t)geo[i][0], (size_t)cap - 1, (size_t)geo[i][1]};
+            t.set_vector(tensor_vector<uint16_t>());
+            fake.push_back(std::move(t));
+        }
+        dp = new Plan(m, be, pool, 1);
+        dp->decode = true;
+        dp->dspec = names;
+        dp->dspec.cap = cap;
+        dp->build_inputs = &fake;
+        m.m_plans_built++;
+        try {
+            dp->dec_state = (int*)be.malloc(16);
+            dp->build();
+            dp->build_inputs = nullptr;
+            // the plan must really be the loop's: one in-place append per cache, the token and position inputs, the logits as an fp32 output
+            size_t appends = 0;
+            for (auto& s : dp->steps) appends += s.what.rfind("KVAppend ", 0) == 0;
+            if (appends != (size_t)names.n_caches)
+                throw std::invalid_argument(fn + "the graph appends to " + std::to_string(appends) + " caches named '" + names.cache_in + "<i>' -> '" + names.cache_out +
+                                            "<i>', the call names " + std::to_string(names.n_caches) + ".");
+            bool has_ids = false, has_pos = false, has_logits = false;
+            for (auto& in : dp->inputs) { has_ids |= in.name == names.ids; has_pos |= in.name == names.pos; }
+            for (auto& o : dp->outputs) has_logits |= o.name == names.logits && !o.raw16 && dp->vals[o.f32val].numel() == V;
+            if (!has_ids) throw std::invalid_argument(fn + "tensor not found: " + names.ids);
+            if (!has_pos) throw std::invalid_argument(fn + "tensor not found: " + names.pos);
+            if (!has_logits) throw std::invalid_argument(fn + "the graph has no fp32 output '" + names.logits + "' of " + std::to_string(V) + " elements per token.");
+        } catch (...) {
+            delete dp;
+            throw;
+        }
+        pool.decode_plan = dp;
+        pool.decode_key = key;
+    }
+    if (P + max_new > dp->dec_pos_limit)
+        throw std::invalid_argument(fn + "positions up to " + std::to_string(P + max_new - 1) + " are needed, the smallest table indexed by '" + names.pos + "' has " +
+                                    std::to_string(dp->dec_pos_limit) + " rows.");
+    if (V > dp->dec_tok_limit)
+        throw std::invalid_argument(fn + "the logits name " + std::to_string(V) + " tokens, the smallest table indexed by '" + names.ids + "' has " +
+                                    std::to_string(dp->dec_tok_limit) + " rows.");
+    const In *in_ids = nullptr, *in_pos = nullptr;
+    for (auto& in : dp->inputs) {
+        if (in.name == names.ids) in_ids = &in;
+        if (in.name == names.pos) in_pos = &in;
+    }
+    const Out* out_lg = nullptr;
+    std::vector<const In*> in_cache((size_t)names.n_caches, nullptr);
+    for (auto& o : dp->outputs)
+        if (o.name == names.logits) out_lg = &o;
+    for (auto& in : dp->inputs) {
+        const int ci = dp->cache_index(in.name, names.cache_in);
+        if (ci >= 0) in_cache[(size_t)ci] = &in;
+    }
+    for (auto* c : in_cache)
+        if (!c) throw std::invalid_argument(fn + "tensor not found: " + names.cache_in + "<i>");
+    const long cap = dp->dspec.cap;
+    FlightGuard flight(dp->in_flight);
+    // ---- entry: state, the caches into their capacity buffers (strided copies), the last row of the prompt's logits into the pass's logits buffer ----
+    dp->sampler_grow(dp->dec_tokens, dp->dec_tokens_bytes, (size_t)max_new * 8);
+    if (logits_trace) dp->sampler_grow(dp->dec_trace, dp->dec_trace_bytes, (size_t)max_new * V * sizeof(float));
+    std::vector<size_t> slot((size_t)names.n_caches + 1, 0);      // scratch for host-side caches, on the way in (P rows) and out (up to P + max_new rows)
+    for (int i = 0; i < names.n_caches; i++) slot[(size_t)i + 1] = slot[(size_t)i] + (((size_t)geo[i][0] * (P + max_new) * geo[i][1] * 2 + 255) & ~(size_t)255);
+    struct Scratch {
+        HipBackend& be; void* p = nullptr;
+        ~Scratch() { if (p) be.free(p); }
+    } scratch{be};
+    std::vector<char> was_resident((size_t)names.n_caches, 0);
+    // (a loop that stops at its first pick still runs its passes: they append nowhere -- row -1 -- and gather row 0 of the tables)
+    const int st0[4] = {-1, (int)P, 0, 0};
+    be.check(be.api.osg_upload(be.ctx, dp->dec_state, st0, sizeof st0), "osg_upload");
+    const int64_t zero = 0;
+    be.check(be.api.osg_upload(be.ctx, dp->ptr(in_ids->staging), &zero, 8), "osg_upload");
+    be.check(be.api.osg_upload(be.ctx, dp->ptr(in_pos->staging), &zero, 8), "osg_upload");
+    for (int i = 0; i < names.n_caches; i++) {
+        Tensor& c = find(names.cache_out + std::to_string(i));
+        const long Hkv = geo[i][0], d = geo[i][1];
+        const void* src = c.m_hip_resident.get();
+        was_resident[(size_t)i] = src != nullptr;
+        if (!src) {
+            if (!scratch.p) scratch.p = be.malloc(slot.back());
+            be.check(be.api.osg_upload(be.ctx, (char*)scratch.p + slot[(size_t)i], c.get_vector<uint16_t>().data(), (size_t)Hkv * P * d * 2), "osg_upload");
+            src = (char*)scratch.p + slot[(size_t)i];
+        }
+        be.check(be.api.osg_copy_2d(be.ctx, 2, src, P * d, 0, dp->ptr(in_cache[(size_t)i]->val), cap * d, 0, Hkv, P * d), "osg_copy_2d");
+    }
+    float* lg_dev = (float*)dp->ptr(out_lg->f32val);
+    be.check(be.api.osg_upload(be.ctx, lg_dev, lg.get_vector<float>().data() + (size_t)(T0 - 1) * V, (size_t)V * sizeof(float)), "osg_upload");
+    int64_t *ids_dev = (int64_t*)dp->ptr(in_ids->staging), *pos_dev = (int64_t*)dp->ptr(in_pos->staging);
+    // ---- the loop: nothing on the device waits -- once the stop code is set, a pick is a no-op and a pass recomputes the last token's pass (same inputs, same row) ----
+    int st[4] = {0, 0, 0, 0};
+    int passes = 0;
+    be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");
+    for (int n = 0; n < max_new; n++) {
+        be.check(be.api.osg_decode_pick(be.ctx, lg_dev, 1, V, eos_id, dp->dec_state, ids_dev, pos_dev, (int64_t*)dp->dec_tokens, max_new), "osg_decode_pick");
+        if (dp->graph && m.m_hip_use_graph) be.check(be.api.osg_graph_launch(be.ctx, dp->graph), "osg_graph_launch");
+        else if (dp->runs >= 1 && m.m_hip_use_graph) {
+            be.check(be.api.osg_graph_begin(be.ctx), "osg_graph_begin");
+            dp->in_capture = true;
+            try {
+                dp->run_steps();
+                dp->in_capture = false;
+            } catch (...) {
+                dp->in_capture = false;
+                osg_graph* g = nullptr;
+                be.api.osg_graph_end(be.ctx, &g);
+                if (g) be.api.osg_graph_destroy(g);
+                throw;
+            }
+            be.check(be.api.osg_graph_end(be.ctx, &dp->graph), "osg_graph_end");
+            be.check(be.api.osg_graph_launch(be.ctx, dp->graph), "osg_graph_launch");
+        } else
+            dp->run_steps();
+        dp->runs++;
+        passes++;
+        if (logits_trace) be.check(be.api.osg_copy(be.ctx, (char*)dp->dec_trace + (size_t)n * V * sizeof(float), lg_dev, (size_t)V * sizeof(float)), "osg_copy");
+        if (sync_every > 0 && (n + 1) % sync_every == 0 && n + 1 < max_new) {
+            be.check(be.api.osg_download(be.ctx, st, dp->dec_state, sizeof st), "osg_download");
+            if (st[3]) break;
+        }
+    }
+    float ms = 0;
+    be.check(be.api.osg_timer_stop(be.ctx, &ms), "osg_timer_stop");
+    // ---- exit: the state, the tokens, the trace; then m_data as the host loop would have left it ----
+    be.check(be.api.osg_download(be.ctx, st, dp->dec_state, sizeof st), "osg_download");
+    const int nt = st[2];
+    if (nt < 0 || nt > max_new || st[1] != P + nt) throw std::runtime_error(fn + "the device-side loop state is inconsistent.");
+    if (nt) be.check(be.api.osg_download(be.ctx, tokens, dp->dec_tokens, (size_t)nt * 8), "osg_download");
+    if (nt && logits_trace) be.check(be.api.osg_download(be.ctx, logits_trace, dp->dec_trace, (size_t)nt * V * sizeof(float)), "osg_download");
+    if (n_tokens) *n_tokens = nt;
+    if (stop) *stop = st[3];
+    dp->m_last_ms = passes ? ms / passes : 0;
+    m.m_last_ms = dp->m_last_ms;
+    m.m_last_kernels = dp->kernel_count();
+    if (nt == 0) return ms;          // no pass of the host loop ran: logits and caches stay as they are
+    const long Pf = P + nt;
+    auto replace = [&](Tensor&& t) {
+        for (size_t i = 0; i < m.m_data.size(); i++)
+            if (m.m_data[i].m_name == t.m_name) { m.m_data.erase(m.m_data.begin() + i); break; }
+        m.m_data.push_back(std::move(t));
+    };
+    {
+        Tensor t;
+        t.m_name = names.logits;
+        t.m_shape = lg.m_shape;
+        t.m_shape[t.m_shape.size() - 2] = 1;
+        tensor_vector<float> host((size_t)V);
+        be.check(be.api.osg_download(be.ctx, host.data(), lg_dev, (size_t)V * sizeof(float)), "osg_download");
+        t.set_vector(std::move(host));
+        replace(std::move(t));       // (`lg` is gone from here on)
+    }
+    for (int i = 0; i < names.n_caches; i++) {
+        const long Hkv = geo[i][0], d = geo[i][1];
+        const size_t bytes = (size_t)Hkv * Pf * d * 2;
+        const void* capbuf = dp->ptr(in_cache[(size_t)i]->val);
+        Tensor t;
+        t.m_name = names.cache_out + std::to_string(i);
+        t.m_shape = {1, (size_t)Hkv, (size_t)Pf, (size_t)d};
+        if (was_resident[(size_t)i]) {
+            const size_t cls = ConstPool::size_class(bytes);
+            void* dev = pool.take_class(be, cls);
+            HipBackend* bp = &be;
+            ConstPool* pp = &pool;
+            t.set_vector(tensor_vector<uint16_t>());
+            t.m_hip_resident = std::shared_ptr<void>(dev, [alive = std::weak_ptr<bool>(m.m_alive), bp, pp, cls](void* p) {
+                if (alive.lock()) pp->give_class(*bp, p, cls);
+            });
+            t.m_hip_resident_bytes = bytes;
+            be.check(be.api.osg_copy_2d(be.ctx, 2, capbuf, cap * d, 0, dev, Pf * d, 0, Hkv, Pf * d), "osg_copy_2d");
+        } else {
+            if (!scratch.p) scratch.p = be.malloc(slot.back());
+            void* tmp = (char*)scratch.p + slot[(size_t)i];
+            be.check(be.api.osg_copy_2d(be.ctx, 2, capbuf, cap * d, 0, tmp, Pf * d, 0, Hkv, Pf * d), "osg_copy_2d");
+            tensor_vector<uint16_t> host(bytes / 2);
+            be.check(be.api.osg_download(be.ctx, host.data(), tmp, bytes), "osg_download");
+            t.set_vector(std::move(host));
+        }
+        replace(std::move(t));
+    }
+    be.check(be.api.osg_sync(be.ctx), "osg_sync");
+    return ms;
+}
+
 std::string Plan::info() const {
     std::string out;
     char buf[128];
+    if (decode) out += "decode capacity " + std::to_string(dspec.cap) + "\n";
     for (size_t i = 0; i < steps.size(); i++) {
         const Step& s = steps[i];
         snprintf(buf, sizeof buf, "step %zu reads=", i);

@@ -67,7 +67,7 @@ __device__ __forceinline__ float row4_sum(float v) {
 
 // BKV: keys per tile (64, or 128 where registers and LDS allow: half the barriers, running-max updates and accumulator rescales per key)
 template <int DP, int DT, int QT, int BKV>
-__global__ __launch_bounds__(256) void attn_kernel(AttnParams p) {
+__device__ __forceinline__ void attn_body(const AttnParams& p) {
     constexpr int NT = BKV / 16;    // 16-key score tiles per KV tile
     constexpr int NS = BKV / 32;    // 32-deep contraction steps of P V
     constexpr int RPL = BKV / 64;   // KV rows staged per lane
@@ -283,6 +283,20 @@ __global__ __launch_bounds__(256) void attn_kernel(AttnParams p) {
             *reinterpret_cast<f16x4*>(O + (long)q * p.o_tok + d) = o;
         }
     }
+}
+
+template <int DP, int DT, int QT, int BKV>
+__global__ __launch_bounds__(256) void attn_kernel(AttnParams p) {
+    attn_body<DP, DT, QT, BKV>(p);
+}
+
+// osg_sdpa_len: the body above for ONE query row, the number of keys read from device memory at entry (the token loop's cache length) -- the
+// instantiation launch_attn picks for Tq = 1 (QT = 1, 64-key tiles), so the arithmetic and the bits are those of the per-call path.  The mask row is
+// indexed through min(q, Tq - 1) = 0, so its pitch (p.Tkv in the body) does not matter; keys are clamped to Tkv - 1: rows at and past the length are not read.
+template <int DP, int DT>
+__global__ __launch_bounds__(256) void attn_len_kernel(AttnParams p, const int* __restrict__ tkv, int cap) {
+    p.Tkv = min(max(*tkv, 1), cap);
+    attn_body<DP, DT, 1, 64>(p);
 }
 
 // =====================================================================================================================================
@@ -674,6 +688,28 @@ int launch_attn(osg_ctx* ctx, const AttnParams& p, int batch) {
     return 0;
 }
 
+template <int DP, int DT>
+int launch_attn_len(osg_ctx* ctx, const AttnParams& p, int batch, const int* tkv, int cap) {
+    dim3 grid(1, batch * p.heads);
+    osg_set_kernel(ctx, 0, 1, DP, DT, 1, 64, (int)grid.y);
+    hipLaunchKernelGGL((attn_len_kernel<DP, DT>), grid, dim3(256), 0, ctx->compute, p, tkv, cap);
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+// the head-dim ladder of dispatch_attn's masked route (a mask never goes to attn2_kernel)
+int dispatch_attn_len(osg_ctx* ctx, const AttnParams& p, int batch, const int* tkv, int cap) {
+    const int D = p.D;
+    if (D <= 32) return launch_attn_len<32, 2>(ctx, p, batch, tkv, cap);
+    if (D <= 48) return launch_attn_len<64, 3>(ctx, p, batch, tkv, cap);
+    if (D <= 64) return launch_attn_len<64, 4>(ctx, p, batch, tkv, cap);
+    if (D <= 80) return launch_attn_len<96, 5>(ctx, p, batch, tkv, cap);
+    if (D <= 96) return launch_attn_len<96, 6>(ctx, p, batch, tkv, cap);
+    if (D <= 128) return launch_attn_len<128, 8>(ctx, p, batch, tkv, cap);
+    if (D <= 160) return launch_attn_len<160, 10>(ctx, p, batch, tkv, cap);
+    OSG_FAIL(ctx, "osg_sdpa_len: head dim > 160 not implemented");
+}
+
 int dispatch_attn(osg_ctx* ctx, const AttnParams& p, int batch) {
     const int D = p.D;
     // the UNet's shapes: v2 (OSG_ATTN_V1=1: the round-2 kernel, for A/B).  K / V rows must be 16-byte aligned (checked by the callers); the DMA offsets are 32-bit
@@ -725,6 +761,23 @@ int osg_sdpa(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, const 
     AttnParams p{(const f16*)q, (const f16*)k, (const f16*)v, (f16*)o, D, qh, qh * q_heads, D, kh, kh * kv_heads, D, kh, kh * kv_heads,
                  D, qh, qh * q_heads, q_heads, Tq, Tkv, D, scale * 1.4426950408889634f, (const f16*)mask, 1.0f / scale, q_heads / kv_heads};
     return dispatch_attn(ctx, p, batch);
+}
+
+int osg_sdpa_len(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, const void* v, const void* mask, void* o, const int* tkv,
+                 long kv_head_stride, long kv_batch_stride, long cap, int batch, int q_heads, int kv_heads, int D, float scale) {
+    if (dtype != OSG_F16) OSG_FAIL(ctx, "osg_sdpa_len: only f16 arithmetic is implemented on the device");
+    if (batch <= 0 || q_heads <= 0 || kv_heads <= 0 || D <= 0 || cap <= 0 || cap > 0x7fffffffL) OSG_FAIL(ctx, "osg_sdpa_len: invalid shape of query, key or value.");
+    if (q_heads % kv_heads) OSG_FAIL(ctx, "osg_sdpa_len: query heads must be a multiple of key/value heads.");
+    if (!q || !k || !v || !o || !tkv) OSG_FAIL(ctx, "osg_sdpa_len: null operand");
+    if (!mask) OSG_FAIL(ctx, "osg_sdpa_len: a mask [cap] is required (the mask-less route of osg_sdpa is another kernel)");
+    if (!(scale > 0.f)) OSG_FAIL(ctx, "osg_sdpa_len: the fused kernel tracks the row maximum of the raw scores and needs scale > 0");
+    if (D % 8) OSG_FAIL(ctx, "osg_sdpa_len: head dim must be a multiple of 8");
+    if (kv_head_stride < cap * D || (kv_head_stride | kv_batch_stride) % 8 || (batch > 1 && kv_batch_stride < kv_head_stride * kv_heads))
+        OSG_FAIL(ctx, "osg_sdpa_len: the head stride must hold cap rows, strides must keep 16-byte alignment");
+    const long qh = D;
+    AttnParams p{(const f16*)q, (const f16*)k, (const f16*)v, (f16*)o, D, qh, qh * q_heads, D, kv_head_stride, kv_batch_stride, D, kv_head_stride,
+                 kv_batch_stride, D, qh, qh * q_heads, q_heads, 1, 1, D, scale * 1.4426950408889634f, (const f16*)mask, 1.0f / scale, q_heads / kv_heads};
+    return dispatch_attn_len(ctx, p, batch, tkv, (int)cap);
 }
 
 int osg_attention(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, const void* v, void* o, int heads, int Tq, int Tkv, int D,

@@ -29,7 +29,7 @@ EXPORTS = [
     "osg_unary", "osg_binary", "osg_geglu", "osg_transpose", "osg_copy_2d", "osg_concat2", "osg_resize_nearest", "osg_gather_rows",
     "osg_maxpool_nhwc", "osg_convert", "osg_sampler_prepare", "osg_sampler_cfg_euler_a", "osg_sampler_cfg_multistep", "osg_sampler_prepare_rescale",
     "osg_sampler_prepare_single", "osg_sampler_euler_a_single", "osg_sampler_multistep_single", "osg_sampler_cfg_stochastic", "osg_sampler_stochastic_single",
-    "osg_decode_gather", "osg_decode_blend",
+    "osg_decode_gather", "osg_decode_blend", "osg_decode_pick", "osg_kv_append_at", "osg_sdpa_len",
     "osg_range_push", "osg_range_pop", "osg_marker_record", "osg_copy_wait_marker", "osg_timer_mark", "osg_timer_between", "osg_set_stat_sinks", "osg_group_norm_stats_nhwc", "osg_qu8_conv2d_nhwc", "osg_qu8_conv2d_nhwc_t", "osg_qu8_conv_tap_sums", "osg_qu8_gemm", "osg_qu8_lut", "osg_qu8_binary", "osg_qu8_instance_norm", "osg_qu8_instance_norm_nhwc", "osg_qu8_affine_act", "osg_qu8_norm_affine_act_nhwc", "osg_qu8_softmax_last", "osg_kdbg_read",
     "osg_tblock_tail_supported", "osg_tblock_tail", "osg_tblock_kv_pack_elems", "osg_tblock_kv_pack_jobs", "osg_tblock_pack_weight", 
 ]
@@ -128,6 +128,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     lib.osg_sampler_stochastic_single.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, cl] + [cf] * 11
     lib.osg_decode_gather.argtypes = [vp, vp, vp, ci, ci, ci, ci, cf]
     lib.osg_decode_blend.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci]
+    if hasattr(lib, "osg_decode_pick"):            # (absent from a library of an older tree that OSGPU_LIB names in an A/B run)
+        lib.osg_decode_pick.argtypes = [vp, vp, cl, cl, ctypes.c_longlong, vp, vp, vp, vp, cl]
+        lib.osg_kv_append_at.argtypes = [vp, vp, vp, vp, ci, cl, ci]
+        lib.osg_sdpa_len.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, cl, cl, cl, ci, ci, ci, ci, cf]
     lib.osg_set_stat_sinks.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, ci]
     lib.osg_group_norm_stats_nhwc.argtypes = [vp, vp, vp, vp, vp, ci, ctypes.c_long, ci, ci, cf, ci, vp]
     lib.osg_qu8_conv2d_nhwc.argtypes = [vp, vp, cf, ci, vp, cf, ci, vp, cf, ci, vp] + [ci] * 13
@@ -488,6 +492,28 @@ class Gpu:
         o = self._out(out, q.shape, q.dtype)
         self._ck(self.lib.osg_sdpa(self.ctx, _NP2DT[q.dtype], q.ptr, k.ptr, v.ptr, self._p(mask), o.ptr, bsz, hq, hkv, tq, tkv, d, scale))
         return o
+
+    def sdpa_len(self, q: DevBuf, k: DevBuf, v: DevBuf, mask: DevBuf, state: DevBuf, scale: float, out: Optional[DevBuf] = None):
+        """osg_sdpa_len: q:[B,Hq,1,D], k,v: capacity buffers [B,Hkv,CAP,D], mask:[CAP]; the number of keys is state[1] (device int32[4], osg_decode_pick's state)"""
+        bsz, hq, tq, d = q.shape
+        hkv, cap = k.shape[1], k.shape[2]
+        assert tq == 1 and state.dtype == np.int32 and state.size >= 4
+        o = self._out(out, q.shape, q.dtype)
+        self._ck(self.lib.osg_sdpa_len(self.ctx, _NP2DT[q.dtype], q.ptr, k.ptr, v.ptr, self._p(mask), o.ptr, state.ptr + 4, cap * d, cap * d * hkv, cap, bsz, hq, hkv,
+                                       d, scale))
+        return o
+
+    def kv_append_at(self, src: DevBuf, cache: DevBuf, state: DevBuf):
+        """osg_kv_append_at: src f16 [Hkv, d] into cache [Hkv, CAP, d] at row state[0] (device int32[4]), in place"""
+        hkv, cap, d = cache.shape
+        assert src.size == hkv * d and state.dtype == np.int32 and state.size >= 4
+        self._ck(self.lib.osg_kv_append_at(self.ctx, src.ptr, cache.ptr, state.ptr, hkv, cap, d))
+
+    def decode_pick(self, logits: DevBuf, eos_id: int, state: DevBuf, ids: DevBuf, pos: DevBuf, tokens: DevBuf):
+        """osg_decode_pick over the last row of logits [T, V] fp32; state int32[4] = (row, len, n_tokens, stop); ids, pos int64 [1]; tokens int64 [max_tokens]"""
+        t, vv = logits.shape
+        assert logits.dtype == np.float32 and state.dtype == np.int32 and state.size >= 4 and ids.dtype == pos.dtype == tokens.dtype == np.int64
+        self._ck(self.lib.osg_decode_pick(self.ctx, logits.ptr, t, vv, int(eos_id), state.ptr, ids.ptr, pos.ptr, tokens.ptr, tokens.size))
 
     def instance_norm(self, x: DevBuf, scale: Optional[DevBuf], bias: Optional[DevBuf], eps: float, out: Optional[DevBuf] = None):
         rows, L = int(np.prod(x.shape[:-1])), x.shape[-1]

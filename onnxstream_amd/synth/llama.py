@@ -188,9 +188,10 @@ def forward(m, cfg: LlamaConfig, input_ids, past, fp16: bool = True):
 UPCAST = ("/input_layernorm/", "/post_attention_layernorm/")   # the ops src/llm.cpp:379-383 runs in fp32 (m_requires_upcast)
 
 
-def forward_resident(m, cfg: LlamaConfig, input_ids, first: bool, P: int, fp16: bool = True):
+def forward_resident(m, cfg: LlamaConfig, input_ids, first: bool, P: int, fp16: bool = True, keep_logits: bool = False):
     """The same call the way src/llm.cpp:386-428 really makes it: the caches never leave Model::m_data -- m_outputs_convert_set = {"logits"} keeps the
-    opkv* outputs in fp16, and the next call renames them to pkv* (:403-407) instead of pushing new tensors.  Returns logits only."""
+    opkv* outputs in fp16, and the next call renames them to pkv* (:403-407) instead of pushing new tensors.  Returns logits only.
+    keep_logits: leave the logits in m_data as well (what `generate` below starts from)."""
     T_new = len(input_ids)
     m.set_use_fp16_arithmetic(False)
     if first:
@@ -205,8 +206,17 @@ def forward_resident(m, cfg: LlamaConfig, input_ids, first: bool, P: int, fp16: 
     m.set_use_fp16_arithmetic(fp16)
     m.run()
     logits = m.get_tensor("logits")[0]
-    m.drop_tensor("logits")          # (get_output moves the result out of m_data, :342-353)
+    if not keep_logits:
+        m.drop_tensor("logits")      # (get_output moves the result out of m_data, :342-353)
     return logits
+
+
+def generate(m, cfg: LlamaConfig, max_new: int, eos_id: int = -1, sync_every: int = 0, trace: bool = False):
+    """The app's token loop (src/llm.cpp:472-496) on the device, after a forward_resident(..., keep_logits=True) over the prompt: greedy tokens picked and
+    run through the Model's resident T = 1 plan without a host round trip per token (bindings.Model.generate).  Leaves the caches opkv* and the logits of
+    the last pass in the Model, as the host loop would.  Returns (tokens, stop, logits trace [n_tokens, V] or None, device ms)."""
+    m.set_use_fp16_arithmetic(True)
+    return m.generate(max_new, 2 * cfg.layers, eos_id=eos_id, sync_every=sync_every, trace=trace)
 
 
 def configure(m, cfg: LlamaConfig, model_dir: str, sdpa: bool = False, ops_cache: bool = True, upcast: bool = False):

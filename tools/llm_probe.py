@@ -1,5 +1,6 @@
 """Dev tool (GPU box): the LLM flow (synth/llama.py, src/llm.cpp's loop shape) at TinyLlama-1.1B size -- 22 layers, hidden 2048, 32 query / 4 key-value
-heads of 64, MLP 5632, vocabulary 32000, random weights -- prefill of 32 tokens, then greedy decode; wall ms per call, caches resident in the Model (fp16, renamed)."""
+heads of 64, MLP 5632, vocabulary 32000, random weights -- prefill of 32 tokens, then greedy decode; wall ms per call, caches resident in the Model (fp16, renamed).
+--generate: instead, the host-driven resident loop against the device loop (Model.generate) in one process, 64 tokens each (profiles/llm_generate_probe.txt)."""
 import os, sys, time, tempfile
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -16,6 +17,59 @@ if not os.path.exists(d + ".complete"):
     llama.build_llama(DirSink(d), cfg)
     open(d + ".complete", "w").write("ok")
     print(f"emitted {cfg.name} in {time.time()-t0:.1f} s", flush=True)
+
+def generate_leg(n_new=64):
+    """--generate: ms per token of the host-driven resident loop (one run() per token: re-plan, 3 int64 inputs up, logits down, argmax on the host) against
+    the device loop (Model.generate: one call, one kept plan, one synchronisation) in the same process, n_new tokens after the 32-token prefill; greedy
+    tokens must agree.  The device loop is timed cold (the call that builds and captures its plan) and warm (a second prompt, the plan kept)."""
+    rng = np.random.default_rng(0)
+    prompt = [int(t) for t in rng.integers(0, cfg.vocab, 32)]
+
+    def fresh():
+        m = Model(b.LIB_HOST, 0, "ram+nocache")
+        m._set_option("hip_autotune", 0)
+        m._set_option("hip_resident_outputs", 1)
+        m.add_outputs_convert("logits")
+        llama.configure(m, cfg, d, sdpa=True, upcast=True)
+        return m
+
+    m = fresh()
+    lg = llama.forward_resident(m, cfg, prompt, True, 0)
+    host_toks, times, dev, P = [], [], [], len(prompt)
+    t_all = time.perf_counter()
+    for k in range(n_new):
+        nxt = int(np.argmax(lg[0, -1]))
+        host_toks.append(nxt)
+        t0 = time.perf_counter()
+        lg = llama.forward_resident(m, cfg, [nxt], False, P)
+        times.append((time.perf_counter() - t0) * 1e3)
+        dev.append(m.hip_last_pass_ms())
+        P += 1
+    host_ms = (time.perf_counter() - t_all) * 1e3 / n_new
+    print(f"host-driven loop, {n_new} tokens after a {len(prompt)}-token prefill: wall {host_ms:.2f} ms/token (median call {np.median(times):.2f}, min {min(times):.2f}), "
+          f"device {np.median(dev):.2f} ms/pass, {m.hip_last_kernel_count()} launches per token + 1 synchronisation, plans built {m.hip_plans_built()}", flush=True)
+    m.close()
+
+    m = fresh()
+    for leg in ("cold (builds and captures the plan)", "warm (plan kept)"):
+        m.clear_tensors()
+        llama.forward_resident(m, cfg, prompt, True, 0, keep_logits=True)
+        built = m.hip_plans_built()
+        t0 = time.perf_counter()
+        toks, stop, _, ms = llama.generate(m, cfg, n_new)
+        wall = (time.perf_counter() - t0) * 1e3
+        agree = sum(int(a == c) for a, c in zip(toks, host_toks))
+        print(f"device loop {leg}: wall {wall / n_new:.2f} ms/token ({wall:.1f} ms the call), device {ms / n_new:.2f} ms/token, {len(toks)} tokens, stop {stop}, "
+              f"{agree} of {n_new} tokens equal the host loop's, plans built by the call {m.hip_plans_built() - built}, "
+              f"{m.hip_last_kernel_count()} kernels per pass inside one graph launch: 2 host launches per token (pick + graph), 1 synchronisation per call", flush=True)
+    print(m.hip_decode_plan_info().splitlines()[0], flush=True)
+    m.close()
+
+
+if "--generate" in sys.argv:
+    generate_leg()
+    sys.exit(0)
+
 for sdpa in (True, False):
     m = Model(b.LIB_HOST, 0, "ram+nocache")
     m._set_option("hip_autotune", 0)
