@@ -169,6 +169,8 @@
         if (!ks.empty()) need(op, ks.size() == 2 && ks[0] == KH && ks[1] == KW, "kernel_shape does not match the weights.");
         const int ph = pads[0] + pads[2], pw = pads[1] + pads[3];
         const int pt = ph / 2, pb = ph - pt, pl = pw / 2, pr = pw - pl;
+        need(op, strides[0] >= 1 && strides[1] >= 1, "invalid pads/strides.");
+        need(op, H + ph >= KH && W + pw >= KW, "kernel larger than the padded input.");   // ((H + ph - KH) / stride would truncate the negative extent to 0: one output row)
         const long Ho = (H + ph - KH) / strides[0] + 1, Wo = (W + pw - KW) / strides[1] + 1;
         int bias = -1;
         if (nin >= 3 && !op.m_input[2].m_name.empty()) {

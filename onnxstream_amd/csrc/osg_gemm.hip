@@ -853,6 +853,8 @@ static int conv2d_v(osg_ctx* ctx, const W8Quant& q, const void* x, const void* w
     if ((y_ld && ((uintptr_t)y & 7)) || (y2 && ((uintptr_t)y2 & 7))) OSG_FAIL(ctx, "osg_conv2d_nhwc_v: output views must be 8-byte aligned");
     if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || KH <= 0 || KW <= 0 || sh <= 0 || sw <= 0)
         OSG_FAIL(ctx, "osg_conv2d_nhwc: invalid argument");
+    // (a kernel larger than the padded image: C's division truncates the negative extent towards 0, and a stride above 1 would make one output row of it)
+    if (H + pt + pb < KH || W + pl + pr < KW) OSG_FAIL(ctx, "osg_conv2d_nhwc: empty output");
     int Ho = (H + pt + pb - KH) / sh + 1;
     int Wo = (W + pl + pr - KW) / sw + 1;
     if (Ho <= 0 || Wo <= 0) OSG_FAIL(ctx, "osg_conv2d_nhwc: empty output");

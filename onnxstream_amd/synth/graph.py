@@ -163,20 +163,23 @@ class GraphBuilder:
         return txt
 
     # -- layer helpers (shapes are logical ONNX/NCHW shapes) ------------------------------------------
-    def conv(self, name, x: T, cout: int, k: int = 3, stride: int = 1, pad: Optional[int] = None, bias: bool = True,
-             std: Optional[float] = None) -> T:
+    def conv(self, name, x: T, cout: int, k=3, stride=1, pad=None, bias: bool = True, std: Optional[float] = None) -> T:
+        """k: one extent or (kh, kw); stride: one step or (sh, sw); pad: one width, or the four ONNX pads (top, left, bottom, right); None pads each axis by
+        half its kernel extent.  The output shape is the one ONNX names: the pads as given (the lowering re-centres them, which keeps their sums)."""
         n, cin, h, w = x.shape
-        pad = (k // 2) if pad is None else pad
-        std = std if std is not None else (1.0 / np.sqrt(cin * k * k))
-        wt = self.weight(f"{name}.weight", self.randn((cout, cin, k, k), std), conv=True)
+        kh, kw = (k, k) if isinstance(k, int) else k
+        sh, sw = (stride, stride) if isinstance(stride, int) else stride
+        pt, pl, pb, pr = (kh // 2, kw // 2, kh // 2, kw // 2) if pad is None else (pad,) * 4 if isinstance(pad, int) else pad
+        std = std if std is not None else (1.0 / np.sqrt(cin * kh * kw))
+        wt = self.weight(f"{name}.weight", self.randn((cout, cin, kh, kw), std), conv=True)
         ins = [x, wt]
         if bias:
             ins.append(self.weight(f"{name}.bias", self.randn((cout,), 0.02), allow_quant=False, q8_exempt=True))
-        ho = (h + 2 * pad - k) // stride + 1
-        wo = (w + 2 * pad - k) // stride + 1
+        ho = (h + pt + pb - kh) // sh + 1
+        wo = (w + pl + pr - kw) // sw + 1
         return self.op(name, "Conv", ins, (n, cout, ho, wo),
-                       {"dilations": "1,1", "group": "1", "kernel_shape": f"{k},{k}",
-                        "pads": f"{pad},{pad},{pad},{pad}", "strides": f"{stride},{stride}"})
+                       {"dilations": "1,1", "group": "1", "kernel_shape": f"{kh},{kw}",
+                        "pads": f"{pt},{pl},{pb},{pr}", "strides": f"{sh},{sw}"})
 
     def conv1d(self, name, x: T, cout: int, k: int = 3, stride: int = 1, pad: Optional[int] = None, bias: bool = True) -> T:
         """Conv over [N, C, L] as the ONNX exporter writes it: one-element dilations / kernel_shape / strides, two pads (the reference lifts it to 2-D,

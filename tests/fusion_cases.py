@@ -59,7 +59,8 @@ def _conv(x, wgt, b, pads, strides):
     if x.ndim == 3:                                                   # Conv1D: [1,C,L] with a [O,I,k,1] filter bank
         return _conv(x[..., None], wgt, b, (pads[0], 0, pads[1], 0), (strides[0], strides[0]))[..., 0]
     O, I, kh, kw = wgt.shape
-    xp = np.pad(x, ((0, 0), (0, 0), (pads[0], pads[2]), (pads[1], pads[3])))
+    ph, pw = pads[0] + pads[2], pads[1] + pads[3]                      # re-centred, the reference's form (op_cases.REF_DIFFERS, conv/pads_1100)
+    xp = np.pad(x, ((0, 0), (0, 0), (ph // 2, ph - ph // 2), (pw // 2, pw - pw // 2)))
     Ho, Wo = (xp.shape[2] - kh) // strides[0] + 1, (xp.shape[3] - kw) // strides[1] + 1
     out = np.zeros((x.shape[0], O, Ho, Wo))
     for dy in range(kh):
@@ -640,9 +641,14 @@ def _linear(w, x, bias="N", border="yb", res=None, rorder="yr", res2=None, out="
     return y
 
 
-def _conv3(w, x, bias=True, nm="/c", out=None, wgt=None):
+# a VAE encoder's down-sampling convolution: stride 2, pad on the bottom and the right only (8 x 8 -> 4 x 4)
+CONV3_DOWN = {"dilations": "1,1", "group": 1, "kernel_shape": "3,3", "pads": "0,0,1,1", "strides": "2,2"}
+DIMG = (1, CO, 4, 4)
+
+
+def _conv3(w, x, bias=True, nm="/c", out=None, wgt=None, attrs=None):
     ins = [x, w.c(nm + ".weight", WC3 if wgt is None else wgt, conv=True)] + ([w.c(nm + ".bias", BC)] if bias else [])
-    return w.op(nm, "Conv", ins, CONV3, out=out)
+    return w.op(nm, "Conv", ins, attrs or CONV3, out=out)
 
 
 for border in ("yb", "by"):
@@ -710,14 +716,15 @@ def _temb(w, t, nm="/t"):
     return w.unsqueeze(nm + "/Unsqueeze_1", w.unsqueeze(nm + "/Unsqueeze", t, 2), 3)
 
 
-def _conv_chain(w, steps, out="out", conv_extra=None, conv_twice=False, t_twice=False, t_const=False):
-    """steps: a string over s (SiLU), r (Add of an image), t (Add of Unsqueeze(Unsqueeze(t[1,C]))) applied to the convolution in that order"""
+def _conv_chain(w, steps, out="out", conv_extra=None, conv_twice=False, t_twice=False, t_const=False, down=False):
+    """steps: a string over s (SiLU), r (Add of an image), t (Add of Unsqueeze(Unsqueeze(t[1,C]))) applied to the convolution in that order; down: the convolution
+    is the one-sided-pad stride-2 form"""
     x = w.inp("x", IMG)
-    r = w.inp("r", OIMG) if "r" in steps else None
+    r = w.inp("r", DIMG if down else OIMG) if "r" in steps else None
     t = None
     if "t" in steps:
         t = w.c("/t.const", wt("/tconst", (1, CO))) if t_const else w.inp("t", (1, CO))
-    y = _conv3(w, x, out=conv_extra)
+    y = _conv3(w, x, out=conv_extra, attrs=CONV3_DOWN if down else None)
     y0 = y
     for n, st in enumerate(steps):
         o = out if n == len(steps) - 1 else None
@@ -748,6 +755,11 @@ add("conv_act/silu_then_residual", "fuse_conv_act", "partial", (lambda w: _conv_
     wrong=lambda w: _conv_chain(w, "rs"))                                                       # (the epilogue adds the residual BEFORE the activation)
 add("conv_act/conv_read_by_silu_and_another", "fuse_conv_act", "left", (lambda w: _conv_chain(w, "s", conv_twice=True)), IM, outs=("out", "neg"), plan=["Conv", "osg.SiLU", "Neg"],
     wrong={"neg": "unwritten"})
+# the three epilogue fusions behind the one-sided-pad stride-2 convolution: the residual's and the per-image bias's rows follow Ho x Wo = 4 x 4, not H x W
+add("conv_act/stride2_pads_0011_silu", "fuse_conv_act", "fires", (lambda w: _conv_chain(w, "s", down=True)), IM, plan=["Conv"])
+add("residual/conv_stride2_pads_0011", "fuse_residual", "fires", (lambda w: _conv_chain(w, "r", down=True)), {"x": IMG, "r": DIMG}, plan=["Conv"], rule="contraction",
+    cls_levels=(2,))
+add("image_bias/conv_stride2_pads_0011_add_t", "fuse_image_bias", "fires", (lambda w: _conv_chain(w, "t", down=True)), IMT, plan=["Conv"], rule="contraction", cls_levels=(2,))
 add("gemm_act/gemm_silu", "fuse_gemm_act", "fires", (lambda w: _gemm(w)), {"x": (1, C)}, plan=["Gemm"])
 add("gemm_act/gemm_is_extra_output", "fuse_gemm_act", "extra", (lambda w: _gemm(w, extra_name="gemm")), {"x": (1, C)}, extra=("gemm",), plan=["Gemm", "osg.SiLU"])
 add("gemm_act/no_bias", "fuse_gemm_act", "left", (lambda w: _gemm(w, bias=False)), {"x": (1, C)}, refuse="wrong number of inputs")

@@ -726,6 +726,118 @@ _pool("all_negative", (1, C8, 5, 6), 3, 1, (1, 1, 1, 1), gen=lambda k: -pos(55 +
 
 
 # ======================================================================================================================================
+# Conv (f16): every attribute form of lower_conv -- one-sided pads (re-centred as the reference does: top = (top + bottom) / 2, the odd cell at the bottom, and
+# the same from left to right), non-square kernels, strides per axis, attribute presence, layout, Conv1D.  Shapes pairwise distinct: C 8, H 7, W 6 -> 12 channels.
+# ======================================================================================================================================
+KC, KH_, KW_, KO = 8, 7, 6, 12
+KX = (1, KC, KH_, KW_)
+KB = wt("/conv_b", (KO,))
+
+
+def _conv_restate(x, w, b, pads, strides):
+    """float64 convolution of x [1,C,H,W] (or [1,C,L]: Conv1D over [1,C,L,1]) with w [O,I,kh,kw], the pads re-centred; and S, K of the contraction bound"""
+    if x.ndim == 3:
+        r = _conv_restate(x[..., None], w, b, (pads[0], 0, pads[1], 0), (strides[0], strides[0]))
+        return {k: (v[..., 0] if v.ndim == 4 else v) for k, v in r.items()}
+    O, I, kh, kw = w.shape
+    ph, pw = pads[0] + pads[2], pads[1] + pads[3]
+    pt, pl = ph // 2, pw // 2
+    xp = np.pad(x, ((0, 0), (0, 0), (pt, ph - pt), (pl, pw - pl)))
+    sh, sw = strides
+    Ho, Wo = (xp.shape[2] - kh) // sh + 1, (xp.shape[3] - kw) // sw + 1
+    out, S = np.zeros((1, O, Ho, Wo)), np.zeros((1, O, Ho, Wo))
+    for dy in range(kh):
+        for dx in range(kw):
+            patch = xp[:, :, dy:dy + sh * (Ho - 1) + 1:sh, dx:dx + sw * (Wo - 1) + 1:sw]
+            out += np.einsum("nchw,oc->nohw", patch, w[:, :, dy, dx])
+            S += np.einsum("nchw,oc->nohw", np.abs(patch), np.abs(w[:, :, dy, dx]))
+    if b is not None:
+        out, S = out + b[None, :, None, None], S + np.abs(b)[None, :, None, None]
+    return {"out": out, "out@S": S, "out@K": np.asarray(I * kh * kw)}
+
+
+def _conv_case(name, k=(3, 3), pads=(1, 1, 1, 1), strides=(1, 1), attrs="all", bias="given", nhwc=True, sx=KX, wshape=None, bshape=None, reject=None, more=None, neg=False, **kw):
+    """attrs: "all" (dilations, group, kernel_shape, pads, strides), "none" (dilations and group only: the defaults apply, the kernel size comes from the weights)
+    or a dict as it stands; bias: "given", "absent" (two inputs) or "empty" (three inputs, the third an empty name); more: further attributes; neg: `out` is Neg of the
+    convolution (exact on the device: the bound is the convolution's) -- the reference cannot hand a Conv1D's 3-D channels-last result out as a graph output"""
+    one_d = len(sx) == 3
+    wshape = wshape or ((KO, sx[1]) + tuple(k) + ((1,) if one_d else ()))
+    wgt = wt("/conv_w" + name, wshape) / 16
+    bvals = KB if bshape is None else wt("/conv_b" + name, bshape)
+    join = lambda v: ",".join(map(str, v))       # noqa: E731
+    if attrs == "all":
+        a = {"dilations": "1" if one_d else "1,1", "group": "1", "kernel_shape": join(k), "pads": join(pads), "strides": join(strides)}
+    elif attrs == "none":
+        a = {"dilations": "1" if one_d else "1,1", "group": "1"}
+    else:
+        a = dict(attrs)
+    a.update(more or {})
+    p4 = tuple(pads) if not one_d else (pads[0], 0, pads[1], 0)
+    s2 = tuple(strides) if not one_d else (strides[0], strides[0])
+    k2 = tuple(k) if not one_d else (k[0], 1)
+    ext = lambda n, p, kk, s: max((n + p - kk) // max(s, 1) + 1, 1)       # noqa: E731  (a refusal's graph still names an output shape)
+    so = (1, wshape[0], ext(sx[2], p4[0] + p4[2], k2[0], s2[0])) + (() if one_d else (ext(sx[3], p4[1] + p4[3], k2[1], s2[1]),))
+
+    def build(g):
+        x = nhwc_in(g, "x", sx) if nhwc and not one_d else g.input("x", sx)
+        ins = [x, g.weight("/conv.weight", wgt, conv=True, allow_quant=False)]
+        if bias == "given":
+            ins.append(g.weight("/conv.bias", bvals, allow_quant=False))
+        elif bias == "empty":
+            ins.append(None)
+        y = g.op("/conv", "Conv", ins, so, a or None, out_names=None if neg else ["out"])
+        if neg:
+            g.op("/neg", "Neg", [y], so, out_names=["out"])
+    inputs = {"x": _pl(sx) if nhwc and not one_d else sx}
+    if reject:
+        add("conv/" + name, "reject", build, inputs, None, reject=reject, **kw)
+        return
+    src = (lambda i: cf(i["x"])) if nhwc and not one_d else (lambda i: i["x"])
+
+    def ref(i):
+        r = _conv_restate(src(i), wgt.astype(f64), KB.astype(f64) if bias == "given" else None, pads, strides)
+        if neg:
+            r["out"] = -r["out"]
+        return r
+    add("conv/" + name, "reduce", build, inputs, ref, bound="contraction", stub_values=False, **kw)
+
+
+_conv_case("k3_pad1")
+_conv_case("plain_input", nhwc=False)
+_conv_case("k1", k=(1, 1), pads=(0, 0, 0, 0))
+_conv_case("pads_0011", pads=(0, 0, 1, 1))
+_conv_case("pads_1100", pads=(1, 1, 0, 0))
+_conv_case("pads_2000", pads=(2, 0, 0, 0))
+_conv_case("pads_1021", pads=(1, 0, 2, 1))
+_conv_case("stride2_pads_0011", pads=(0, 0, 1, 1), strides=(2, 2))
+_conv_case("stride_2_1", strides=(2, 1))
+_conv_case("k1x3", k=(1, 3), pads=(0, 1, 0, 1))
+_conv_case("k3x1", k=(3, 1), pads=(1, 0, 1, 0))
+_conv_case("k3x5", k=(3, 5), pads=(1, 2, 1, 2))
+_conv_case("k5x7_pads_2323", k=(5, 7), pads=(2, 3, 2, 3))
+_conv_case("no_pads_strides_kernel_shape", pads=(0, 0, 0, 0), attrs="none")
+_conv_case("no_attributes", pads=(0, 0, 0, 0), attrs={})
+_conv_case("no_bias", bias="absent")
+_conv_case("bias_empty_name", bias="empty")
+KL = (1, KC, 11)
+_conv_case("conv1d_k3_stride2_pads_11", k=(3,), pads=(1, 1), strides=(2,), sx=KL, neg=True)
+_conv_case("conv1d_pads_20", k=(3,), pads=(2, 0), strides=(1,), sx=KL, neg=True)
+_conv_case("conv1d_no_attributes", k=(3,), pads=(0, 0), strides=(1,), sx=KL, attrs={})
+_conv_case("group2", reject="group != 1 not supported", more={"group": "2"})
+_conv_case("dilations2", reject="dilations != 1 not supported", more={"dilations": "2,2"})
+_conv_case("two_pads_rank4", reject="invalid pads/strides", more={"pads": "1,1"})
+_conv_case("kernel_shape_contradicts_weights", reject="kernel_shape does not match the weights", more={"kernel_shape": "3,5"})
+_conv_case("auto_pad", reject="unrecognized attribute: auto_pad", more={"auto_pad": "SAME_UPPER"})
+_conv_case("dilations_length_contradicts_rank", reject="invalid dilations attribute value", more={"dilations": "1"})
+_conv_case("wrong_cin", reject="invalid shape of weights", wshape=(KO, KC // 2, 3, 3))
+_conv_case("bias_of_another_length", reject="invalid shape of bias", bshape=(KO - 1,))
+_conv_case("batch2", reject="batch size must be 1", sx=(2, KC, KH_, KW_), nhwc=False)
+_conv_case("stride0", reject="invalid pads/strides", more={"strides": "0,1"})
+# 7 + 2 < 10: (7 + 2 - 10) / 2 truncates to 0 in C, which would plan one output row of a kernel that fits nowhere
+_conv_case("kernel_larger_than_padded_input_stride2", k=(10, 3), strides=(2, 1), reject="kernel larger than the padded input")
+
+
+# ======================================================================================================================================
 # An operand without elements against an extent of 1 (support_dynamic_shapes: the declared 0 is a wildcard, so the computed shape is not checked against
 # it): the output is empty and nothing is launched.  Stub only.
 # ======================================================================================================================================
@@ -748,12 +860,22 @@ REF_REFUSES = {
     "expand/target1_input4": "input dimension > output dimension",
     "flatten/axis3": "invalid axis attribute",
     "maxpool/no_dilations_attribute": "invalid dilations attribute value",
+    # Conv: the reference wants strides[0] == strides[1] and every attribute present; lower_conv takes a stride per axis, applies the ONNX defaults and reads the
+    # kernel size from the weights, and skips a bias whose name is empty
+    "conv/stride_2_1": "XnnPack::convolution_nhwc_fp32: one or more arguments are invalid",
+    "conv/no_pads_strides_kernel_shape": "invalid shape of W or invalid kernel_shape",
+    "conv/no_attributes": "invalid dilations attribute value",
+    "conv/bias_empty_name": "input tensor not found",
+    "conv/conv1d_no_attributes": "invalid dilations attribute value",
 }
 # case -> note: the reference's form differs from the first restatement in kind; resolved in favour of the reference
 REF_DIFFERS = {
     "maxpool/pads0110": "pads that differ between the two sides of a direction: the first restatement (and the lowering) padded as ONNX names them (top, left, "
                         "bottom, right); the reference re-centres them as it does for Conv, top = (top + bottom) / 2 with the odd cell at the bottom, and the same "
                         "from left to right.  The restatement and the lowering follow the reference (also maxpool/pads1001, maxpool/pads2000).",
+    "conv/pads_1100": "pads (1,1,0,0): ONNX pads the top and the left; the reference re-centres, top = (1 + 0) / 2 = 0 with the odd cell at the bottom, left = 0 with the "
+                      "odd cell at the right -- the same convolution as conv/pads_0011 (the two cases hold different weights, so their outputs differ).  The restatement "
+                      "and lower_conv follow the reference (also conv/pads_2000: one cell at the top, one at the bottom; conv/pads_1021; conv/conv1d_pads_20).",
     "slice/two_axes_no_axes": "two starts / ends without an `axes` input: the first restatement (and the lowering) took the last two axes, ONNX would take axes 0 and "
                               "1; the reference slices the LAST axis twice, the second time on the result of the first (its `last_but_one` is only ever set from "
                               "`axes`).  The restatement and the lowering follow the reference.",
