@@ -341,6 +341,31 @@ int osg_sdpa(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, const 
  * input_ids / position_ids: the int64 staging buffers of the pass; tokens: device int64 [max_tokens]. */
 int osg_decode_pick(osg_ctx* ctx, const float* logits, long T, long V, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
                     int64_t* tokens, long max_tokens);
+/* osg_decode_pick with a sampling rule in the argmax's place: one token is drawn from the LAST row l[0..V) of logits [T][V] fp32, V <= 2^20, in one
+ * launch of one workgroup, without a device-wide sort and without a float sum: everything after the weights is integer arithmetic, so the token does
+ * not depend on the order of any reduction and the rule can be restated exactly (tests/sample_rule.py does, in numpy and Python integers).
+ * Arguments: temperature > 0 with a finite fp32 1 / temperature; top_k >= 0 (0 = off); top_p in (0, 1] (1 = off); seed; draw_base.  The draw index is
+ * n = draw_base + n_tokens (state[2] at the time of the launch, modulo 2^64).
+ *   1. Order.  NaN logits are left out.  The tokens are ordered by (value descending, index descending) -- among equals the LARGER index comes first,
+ *      the tie rule of osg_decode_pick; -0.0 and +0.0 are equal.  m = the first token's value.  No token left, or m = +-inf: stop = 2, nothing else
+ *      is written.  (The pick's "start from -1.0f" belongs to the app's argmax and is NOT part of this rule: a row of logits below -1 is sampled.)
+ *   2. top-k.  The first top_k tokens of that order are kept (all of them when top_k = 0 or top_k >= their number).
+ *   3. Weights, for kept tokens: x_i = (l_i - m) * inv_t in fp32, two roundings, inv_t = 1.0f / temperature computed once on the host in fp32 (a
+ *      MULTIPLY by the reciprocal, not a division by the temperature); w_i = exp(x_i) in fp32 (the device's expf: not correctly rounded, within 1 ulp);
+ *      q_i = floor(min(w_i, 1) * 2^32), an unsigned 64-bit integer in [0, 2^32].  Tokens with q_i = 0 drop out.  The first token has q = 2^32.
+ *   4. top-p, when top_p < 1.  Qtot = sum of q_i over the tokens kept so far.  threshold = max(1, floor(p * Qtot)), p = top_p's fp32 value taken
+ *      exactly (p = pm * 2^-ps with an integer pm < 2^24: the threshold is (pm * Qtot) >> ps in 128-bit integers, no rounding anywhere).  Kept: the
+ *      SHORTEST prefix of the order of step 1 whose q sum to at least the threshold (at least one token: that is what the max(1, ...) says).
+ *   5. Draw.  Philox4x32-10 (multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85) with key = (seed low, seed high) and
+ *      counter = (n low, n high, 0, 0); r = output word 0 | word 1 << 32; Q = sum of q_i over the final kept set; t = (r * Q) >> 64.  The token is the
+ *      first kept token IN ASCENDING INDEX ORDER whose running sum of q exceeds t (index order, not the order of step 1: any fixed order is a valid
+ *      draw from the same distribution, and this one needs no sort).
+ *   6. State.  As osg_decode_pick: stop != 0 or n_tokens >= max_tokens: nothing is read or written;   tok == eos_id (eos_id >= 0): stop = 1;
+ *      otherwise tokens[n_tokens++] = tok; input_ids[0] = tok; position_ids[0] = len; row = len; len = len + 1.
+ * Two launches with equal arguments over equal memory write equal bits. */
+int osg_decode_sample(osg_ctx* ctx, const float* logits, long T, long V, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
+                      int64_t* tokens, long max_tokens, float temperature, long top_k, float top_p, unsigned long long seed,
+                      unsigned long long draw_base);
 /* cache[h][*row][0..d) = src[h][0..d) for h < kv_heads: the new key or value row of every head, f16 [kv_heads][d], into a capacity buffer
  * [kv_heads][cap][d] at the row a device int names (state + 0).  A row outside [0, cap) writes nothing. */
 int osg_kv_append_at(osg_ctx* ctx, const void* src, void* cache, const int* row, int kv_heads, long cap, int d);

@@ -342,17 +342,28 @@ class Model:
         return ms.value
 
     def generate(self, max_new: int, n_caches: int, eos_id: int = -1, sync_every: int = 0, trace: bool = False, ids: str = "input_ids",
-                 pos: str = "position_ids", mask: str = "attention_mask", logits: str = "logits", cache_in: str = "pkv", cache_out: str = "opkv"):
+                 pos: str = "position_ids", mask: str = "attention_mask", logits: str = "logits", cache_in: str = "pkv", cache_out: str = "opkv",
+                 temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, draw_base: int = 0):
         """The LLM app's greedy token loop on the device (model_hip_generate): after a run() over the prompt has left `logits` (fp32) and the caches
         `cache_out`<i> (fp16, i < n_caches) in the Model, up to max_new tokens are picked (the app's argmax) and run through the resident T = 1 plan
         without a host round trip per token; the caches and the last logits are left as the host loop would leave them.  Returns
         (tokens int64 [n_tokens], stop, trace float32 [n_tokens, V] or None, device ms); stop: 0 budget spent, 1 eos_id picked, 2 invalid argmax.
-        sync_every > 0: the stop code is read after every sync_every passes and the call ends early."""
+        sync_every > 0: the stop code is read after every sync_every passes and the call ends early.
+        temperature > 0 samples instead (model_hip_generate_sampled; the rule is stated in include/osgpu.h at osg_decode_sample): logits / temperature,
+        the top_k largest (0 = off), the shortest prefix holding top_p of the mass (1 = off), a Philox draw keyed by the 64-bit `seed` at draw index
+        draw_base + n_tokens; stop 2 then means a row without a finite maximum.  temperature == 0 is the greedy call, whatever the other four say."""
         import numpy as np
-        f = self._lib.model_hip_generate
         cp, ip = ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)
-        f.argtypes = [ctypes.c_void_p, cp, cp, cp, cp, cp, cp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), ip, ip,
-                      ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)]
+        argtypes = [ctypes.c_void_p, cp, cp, cp, cp, cp, cp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), ip, ip,
+                    ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)]
+        rule = ()
+        if temperature == 0:
+            f = self._lib.model_hip_generate
+        else:
+            f = self._lib.model_hip_generate_sampled
+            argtypes += [ctypes.c_float, ctypes.c_longlong, ctypes.c_float, ctypes.c_ulonglong, ctypes.c_ulonglong]
+            rule = (float(temperature), int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(draw_base) & (2 ** 64 - 1))
+        f.argtypes = argtypes
         f.restype = ctypes.c_void_p
         toks = np.zeros(max(int(max_new), 1), np.int64)
         tr = None
@@ -364,7 +375,7 @@ class Model:
         n, stop, ms = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0)
         self._err(f(self._h, self._name(ids), self._name(pos), self._name(mask), self._name(logits), self._name(cache_in), self._name(cache_out), int(n_caches),
                     int(max_new), int(eos_id), int(sync_every), toks.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), ctypes.byref(n), ctypes.byref(stop),
-                    tr.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if tr is not None else None, ctypes.byref(ms)))
+                    tr.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if tr is not None else None, ctypes.byref(ms), *rule))
         return toks[:n.value].copy(), stop.value, (tr[:n.value].copy() if tr is not None else None), ms.value
 
     def get_tensor_f16(self, name: str):

@@ -477,7 +477,30 @@ char* model_hip_generate(Handle* h, const char* ids_name, const char* pos_name, 
         spec.ids = ids_name; spec.pos = pos_name; spec.mask = mask_name; spec.logits = logits_name;
         spec.cache_in = cache_in_prefix; spec.cache_out = cache_out_prefix; spec.n_caches = n_caches;
         static_assert(sizeof(long long) == sizeof(int64_t), "tokens are int64");
-        const double v = Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace);
+        const double v = Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, Plan::SampleRule());
+        if (ms) *ms = v;
+        return nullptr;
+    } catch (const std::exception& e) {
+        return dup_cstr(e.what());
+    }
+}
+// model_hip_generate with a sampling rule in the argmax's place (osg_decode_sample, include/osgpu.h states the rule in full): temperature > 0 divides the
+// logits, top_k > 0 keeps the k largest, top_p < 1 the shortest prefix that holds that share of the mass, and the token is drawn with Philox4x32-10 keyed by
+// `seed` at draw index draw_base + n_tokens -- so a call of N tokens equals calls of a and N - a tokens, the second with draw_base = a.  temperature = 0
+// is model_hip_generate itself (the other four arguments are still checked).  Refused, each with "Model::hip_generate: ": a temperature that is negative, NaN,
+// infinite or so small that 1 / temperature is not finite in fp32; top_k < 0; top_p NaN, <= 0 or > 1.  The decode plan is the one model_hip_generate builds
+// and keeps: a sampled and a greedy call share it.
+char* model_hip_generate_sampled(Handle* h, const char* ids_name, const char* pos_name, const char* mask_name, const char* logits_name, const char* cache_in_prefix,
+                                 const char* cache_out_prefix, int n_caches, int max_new, long long eos_id, int sync_every, long long* tokens, int* n_tokens,
+                                 int* stop, float* logits_trace, double* ms, float temperature, long long top_k, float top_p, unsigned long long seed,
+                                 unsigned long long draw_base) {
+    try {
+        Plan::DecodeSpec spec;
+        spec.ids = ids_name; spec.pos = pos_name; spec.mask = mask_name; spec.logits = logits_name;
+        spec.cache_in = cache_in_prefix; spec.cache_out = cache_out_prefix; spec.n_caches = n_caches;
+        Plan::SampleRule rule;
+        rule.temperature = temperature; rule.top_k = (long)top_k; rule.top_p = top_p; rule.seed = seed; rule.draw_base = draw_base;
+        const double v = Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, rule);
         if (ms) *ms = v;
         return nullptr;
     } catch (const std::exception& e) {

@@ -349,8 +349,11 @@ struct Plan {
     int cache_index(const std::string& name, const std::string& prefix) const;   // i of "<prefix><i>", i < n_caches; -1 otherwise
     // the reference app's token loop (src/llm.cpp:472-496) on the device: see model_hip_generate (exports.cpp) for the contract.  A static member of Plan
     // for the reason given at run_sampler_loop_multistep; the decode plan itself is kept in the Model's ConstPool.
+    // how a token is taken from the logits: default-constructed = greedy, the app's argmax (osg_decode_pick); temperature > 0 = the sampling rule of
+    // include/osgpu.h (osg_decode_sample).  Sampling is outside the decode plan: the plan, its capacity, its capture and its text are the same either way.
+    struct SampleRule { float temperature = 0.0f; long top_k = 0; float top_p = 1.0f; unsigned long long seed = 0, draw_base = 0; };
     static double generate(Model& m, const DecodeSpec& names, int max_new, long long eos_id, int sync_every, int64_t* tokens, int* n_tokens, int* stop,
-                           float* logits_trace);
+                           float* logits_trace, const SampleRule& rule);
     static std::string decode_info(Model& m);
     // a copy of a device-resident tensor's bytes (Tensor::m_hip_resident) for the host; the tensor stays where it is (model_hip_get_tensor_f16)
     static void read_resident(Model& m, const Tensor& t, void* dst);

@@ -825,13 +825,18 @@ std::string Plan::decode_info(Model& m) {
 }
 
 // The reference app's token loop (src/llm.cpp:472-496) with the argmax, the cache append and the cache length on the device: max_new x (osg_decode_pick + the
-// T = 1 pass of the Model's resident decode plan) enqueued back to back.  model_hip_generate (exports.cpp) states the contract.
+// T = 1 pass of the Model's resident decode plan) enqueued back to back.  model_hip_generate (exports.cpp) states the contract.  With a sampling rule
+// (model_hip_generate_sampled) osg_decode_sample stands where the pick stands; nothing else differs.
 double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long eos_id, int sync_every, int64_t* tokens, int* n_tokens, int* stop,
-                      float* logits_trace) {
+                      float* logits_trace, const SampleRule& rule) {
     static const std::string fn = "Model::hip_generate: ";
     if (n_tokens) *n_tokens = 0;
     if (stop) *stop = 0;
     if (max_new < 0) throw std::invalid_argument(fn + "max_new must be >= 0.");
+    if (!(rule.temperature >= 0.0f) || std::isinf(rule.temperature)) throw std::invalid_argument(fn + "temperature must be finite and >= 0 (0 = greedy).");
+    if (rule.temperature > 0.0f && std::isinf(1.0f / rule.temperature)) throw std::invalid_argument(fn + "temperature is too small: 1 / temperature is not finite.");
+    if (rule.top_k < 0) throw std::invalid_argument(fn + "top_k must be >= 0 (0 = off).");
+    if (!(rule.top_p > 0.0f) || !(rule.top_p <= 1.0f)) throw std::invalid_argument(fn + "top_p must be in (0, 1] (1 = off).");
     if (names.n_caches <= 0) throw std::invalid_argument(fn + "needs at least one key/value cache.");
     if (!m.m_plan || !m.m_backend || !m.m_pool || m.m_plan->runs < 1)
         throw std::runtime_error(fn + "run() once first (the prompt's logits and key/value caches must be in the Model).");
@@ -1001,7 +1006,12 @@ double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long 
     int passes = 0;
     be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");
     for (int n = 0; n < max_new; n++) {
-        be.check(be.api.osg_decode_pick(be.ctx, lg_dev, 1, V, eos_id, dp->dec_state, ids_dev, pos_dev, (int64_t*)dp->dec_tokens, max_new), "osg_decode_pick");
+        if (rule.temperature > 0.0f)
+            be.check(be.api.osg_decode_sample(be.ctx, lg_dev, 1, V, eos_id, dp->dec_state, ids_dev, pos_dev, (int64_t*)dp->dec_tokens, max_new, rule.temperature,
+                                              rule.top_k, rule.top_p, rule.seed, rule.draw_base),
+                     "osg_decode_sample");
+        else
+            be.check(be.api.osg_decode_pick(be.ctx, lg_dev, 1, V, eos_id, dp->dec_state, ids_dev, pos_dev, (int64_t*)dp->dec_tokens, max_new), "osg_decode_pick");
         if (dp->graph && m.m_hip_use_graph) be.check(be.api.osg_graph_launch(be.ctx, dp->graph), "osg_graph_launch");
         else if (dp->runs >= 1 && m.m_hip_use_graph) {
             be.check(be.api.osg_graph_begin(be.ctx), "osg_graph_begin");

@@ -3,8 +3,12 @@
 //   osg_decode_pick  <- the app's argmax over the last row of the logits (src/llm.cpp:355-370) and the loop's state advance: the token goes into the
 //                       pass's input_ids staging, the cache length into position_ids, tokens[n_tokens++] = tok; end-of-sequence and the invalid
 //                       argmax set the stop code, after which every further launch is a predicated no-op
+//   osg_decode_sample <- in the pick's place when the caller samples: temperature, top-k, top-p and a seeded draw over the same row by the integer rule
+//                       of include/osgpu.h, then the same state advance
 //   osg_kv_append_at <- the cache Concat (pkv ++ new row, axis 2) in place: the new row of every head into a capacity buffer at the device-side row
 // (osg_sdpa_len, the attention over such buffers, lives next to osg_sdpa in osg_attention.hip.)
+#include <cmath>
+#include <cstring>
 #include "osg_common.h"
 
 namespace {
@@ -52,6 +56,343 @@ __global__ __launch_bounds__(kPickThreads) void decode_pick_kernel(const float* 
     state[2] = n + 1;
 }
 
+// ---- osg_decode_sample: the rule of include/osgpu.h.  One workgroup; every pass re-reads the row (coalesced, out of L1 / L2), nothing is sorted. ----
+// Every token is one 52-bit composite c = (key << 20) | index, key an order-preserving image of its logit: descending c IS the order of step 1
+// (value descending, index descending), and all composites differ.  top-k and top-p are both prefixes of that order, so each is one composite `cut`
+// (kept: c >= cut), found by a radix descent over c from the top -- on counts for top-k, on the integer masses q for top-p.  The histograms are
+// integer LDS atomics: their sums do not depend on the order the waves arrive in.
+typedef unsigned long long u64;
+constexpr int kSampleThreads = 1024, kSampleWaves = kSampleThreads / 64;
+constexpr int kHistCopies = 8;   // the top byte of a float key takes few values: eight copies of each bin (lane & 7) spread the adds of one wave
+
+struct SampleShared {
+    u64 hist[256 * kHistCopies];   // [bin][copy]: the copies of one bin lie in neighbouring banks
+    u64 bins[256];
+    u64 wsum[kSampleWaves];
+    u64 bc[4];
+    u64 headq[4];
+    uint32_t wkey[kSampleWaves];
+    int wcnt[kSampleWaves];
+};
+
+__device__ __forceinline__ uint32_t sample_key(float v) {
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float sample_key_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
+// q of step 3: floor(min(exp((v - m) * inv_t), 1) * 2^32); the product by 2^32 is exact, the conversion truncates
+__device__ __forceinline__ u64 sample_q(float v, float m, float inv_t) {
+    const float w = fminf(expf((v - m) * inv_t), 1.0f);
+    return (u64)(w * 4294967296.0f);
+}
+// the composite of element i with value v; false for a NaN.  -0.0 and +0.0 are one value: both take the key of +0.0
+__device__ __forceinline__ bool sample_comp(long i, float& v, u64& c) {
+    if (v != v) return false;
+    if (v == 0.0f) v = 0.0f;
+    c = ((u64)sample_key(v) << 20) | (u64)i;
+    return true;
+}
+// How a pass reads the row: 16-byte loads from the first aligned element on (`head` = the 0-3 elements before it), up to four per thread in flight.
+// f(i, v) is called once for every element by exactly one thread, in no particular order.
+__device__ __forceinline__ int sample_head(const float* row, long V) {
+    const long a = (long)(((16 - ((uintptr_t)row & 15)) & 15) >> 2);
+    return (int)(a < V ? a : V);
+}
+template <class F>
+__device__ __forceinline__ void sample_for_each(const float* __restrict__ row, long V, int head, F f) {
+    const int tid = threadIdx.x;
+    if (tid < head) f((long)tid, row[tid]);
+    const long nvec = (V - head) / 4;
+    const float4* __restrict__ p = (const float4*)(row + head);
+    long j = tid;
+    for (; j + 3 * kSampleThreads < nvec; j += 4 * kSampleThreads) {
+        float4 x[4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) x[u] = p[j + u * kSampleThreads];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const long i = head + 4 * (j + u * kSampleThreads);
+            f(i, x[u].x); f(i + 1, x[u].y); f(i + 2, x[u].z); f(i + 3, x[u].w);
+        }
+    }
+    for (; j + kSampleThreads < nvec; j += 2 * kSampleThreads) {
+        const float4 x = p[j], y = p[j + kSampleThreads];
+        const long i = head + 4 * j, k = i + 4 * kSampleThreads;
+        f(i, x.x); f(i + 1, x.y); f(i + 2, x.z); f(i + 3, x.w);
+        f(k, y.x); f(k + 1, y.y); f(k + 2, y.z); f(k + 3, y.w);
+    }
+    if (j < nvec) {
+        const float4 x = p[j];
+        const long i = head + 4 * j;
+        f(i, x.x); f(i + 1, x.y); f(i + 2, x.z); f(i + 3, x.w);
+    }
+    const long t = head + 4 * nvec + tid;
+    if (t < V) f(t, row[t]);
+}
+// four consecutive elements from i on, row + i 16-byte aligned; past the end of the row a NaN stands (no token)
+__device__ __forceinline__ void sample_load4(const float* __restrict__ row, long V, long i, float (&v)[4]) {
+    if (i + 3 < V) {
+        const float4 x = *(const float4*)(row + i);
+        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; k++) v[k] = i + k < V ? row[i + k] : __uint_as_float(0x7fc00000u);
+    }
+}
+// max(1, floor(pm * qtot / 2^ps)) in 128-bit integer arithmetic; pm < 2^24, ps >= 23, so the result fits 64 bits
+__device__ __forceinline__ u64 sample_threshold(u64 qtot, uint32_t pm, int ps) {
+    const u64 lo = (u64)pm * qtot, hi = __umul64hi((u64)pm, qtot);
+    const u64 t = ps >= 128 ? 0 : ps >= 64 ? hi >> (ps - 64) : (hi << (64 - ps)) | (lo >> ps);
+    return t ? t : 1;
+}
+__device__ __forceinline__ u64 wave_sum(u64 s) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    return s;
+}
+__device__ __forceinline__ u64 wave_scan(u64 s, int lane) {   // inclusive, lane order
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const u64 o = __shfl_up(s, off);
+        if (lane >= off) s += o;
+    }
+    return s;
+}
+
+// The largest composite `cut` for which the weights of {c >= cut} sum to at least the target; weight = 1 per token and target given (MASS false:
+// 1 <= target <= number of tokens), or weight = q over the tokens with c >= floor_c and target = the top-p threshold of their total (MASS true).
+// Seven digits from the top: the four bytes of the key, then the index as 8 + 8 + 4 bits.  It ends early once a whole bin is kept, which is the
+// usual case after the key's four bytes (one token holds that key, or all its equals are kept): the lower bits of the cut are 0 then.
+template <bool MASS>
+__device__ u64 sample_select(const float* __restrict__ row, long V, int head, float m, float inv_t, u64 floor_c, u64 target, uint32_t pm, int ps,
+                             SampleShared& sh) {
+    const int tid = threadIdx.x, lane = tid & 63;
+    u64 prefix = 0, above = 0;
+    for (int d = 0; d < 7; d++) {
+        const int shift = d < 4 ? 44 - 8 * d : d == 4 ? 12 : d == 5 ? 4 : 0;
+        const int bits = d == 6 ? 4 : 8;
+        for (int j = tid; j < 256 * kHistCopies; j += kSampleThreads) sh.hist[j] = 0;
+        __syncthreads();
+        sample_for_each(row, V, head, [&](long i, float v) {
+            u64 c;
+            if (!sample_comp(i, v, c)) return;
+            if (((c ^ prefix) >> (shift + bits)) != 0) return;
+            u64 w = 1;
+            if (MASS) {
+                if (c < floor_c) return;
+                w = sample_q(v, m, inv_t);
+                if (w == 0) return;
+            }
+            atomicAdd(&sh.hist[((c >> shift) & (u64)((1 << bits) - 1)) * kHistCopies + (lane & (kHistCopies - 1))], w);
+        });
+        __syncthreads();
+        if (tid < 256) {
+            u64 s = 0;
+#pragma unroll
+            for (int k = 0; k < kHistCopies; k++) s += sh.hist[tid * kHistCopies + k];
+            sh.bins[tid] = s;
+        }
+        __syncthreads();
+        if (tid < 64) {   // wave 0 walks the bins from the top: lane L owns bins 255 - 4L ... 252 - 4L
+            u64 b[4], s = 0;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                b[k] = sh.bins[255 - 4 * lane - k];
+                s += b[k];
+            }
+            const u64 incl = wave_scan(s, lane);
+            if (MASS && d == 0) target = sample_threshold(__shfl(incl, 63), pm, ps);
+            const u64 hit = __ballot(above + incl >= target);   // (never 0: the target is at most the total)
+            if (hit != 0 && lane == __ffsll((long long)hit) - 1) {
+                u64 acc = above + incl - s;
+                int k = 0;
+                for (; k < 3; k++) {
+                    if (acc + b[k] >= target) break;
+                    acc += b[k];
+                }
+                sh.bc[0] = (u64)(255 - 4 * lane - k);
+                sh.bc[1] = acc;
+                sh.bc[2] = b[k];
+                sh.bc[3] = target;
+            }
+        }
+        __syncthreads();
+        const u64 binw = sh.bc[2];
+        prefix |= sh.bc[0] << shift;
+        above = sh.bc[1];
+        target = sh.bc[3];
+        if (above + binw == target) return prefix;
+        if (MASS && d == 3) {   // one key, one q: the bin holds binw / q equal tokens, of which the ceil((target - above) / q) largest indices are kept
+            const u64 q = sample_q(sample_key_value((uint32_t)(prefix >> 20)), m, inv_t);
+            if ((target - above + q - 1) / q * q == binw) return prefix;
+        }
+    }
+    return prefix;
+}
+
+// Philox4x32-10, word 0 | word 1 << 32 of the output for key = (seed lo, seed hi), counter = (n lo, n hi, 0, 0)
+__device__ __forceinline__ u64 sample_philox(u64 seed, u64 n) {
+    uint32_t c0 = (uint32_t)n, c1 = (uint32_t)(n >> 32), c2 = 0, c3 = 0, k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        const u64 p0 = (u64)0xD2511F53u * c0, p1 = (u64)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1;
+        c3 = (uint32_t)p0;
+        c0 = n0;
+        c2 = n2;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return (u64)c0 | ((u64)c1 << 32);
+}
+
+__global__ __launch_bounds__(kSampleThreads) void decode_sample_kernel(const float* __restrict__ row, long V, long long eos_id, int* __restrict__ state,
+                                                                       int64_t* __restrict__ input_ids, int64_t* __restrict__ position_ids,
+                                                                       int64_t* __restrict__ tokens, long max_tokens, float inv_t, long top_k, uint32_t pm,
+                                                                       int ps, u64 seed, u64 draw_base) {
+    const int n_tok = state[2];
+    if (state[3] != 0 || (long)n_tok >= max_tokens) return;   // as osg_decode_pick: uniform, nothing is read or written any more
+    __shared__ SampleShared sh;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // ---- step 1: the largest value and the number of tokens that are no NaN (key 0 belongs to a NaN: no token has it) ----
+    const int head = sample_head(row, V);
+    uint32_t kmax = 0;
+    int cnt = 0;
+    sample_for_each(row, V, head, [&](long i, float v) {
+        u64 c;
+        if (!sample_comp(i, v, c)) return;
+        kmax = max(kmax, (uint32_t)(c >> 20));
+        cnt++;
+    });
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, off));
+        cnt += __shfl_xor(cnt, off);
+    }
+    if (lane == 0) { sh.wkey[wave] = kmax; sh.wcnt[wave] = cnt; }
+    __syncthreads();
+    kmax = 0;
+    cnt = 0;
+    for (int w = 0; w < kSampleWaves; w++) { kmax = max(kmax, sh.wkey[w]); cnt += sh.wcnt[w]; }
+    const float m = sample_key_value(kmax);
+    if (cnt == 0 || (__float_as_uint(m) & 0x7fffffffu) == 0x7f800000u) {   // nothing to order, or +-inf on top: the invalid argmax
+        if (tid == 0) state[3] = 2;
+        return;
+    }
+    // ---- steps 2 and 4: the cut ----
+    u64 cut = 0;
+    if (top_k > 0 && top_k < (long)cnt) cut = sample_select<false>(row, V, head, m, inv_t, 0, (u64)top_k, 0, 0, sh);
+    if (pm != 0) {
+        const u64 p_cut = sample_select<true>(row, V, head, m, inv_t, cut, 0, pm, ps, sh);
+        cut = p_cut > cut ? p_cut : cut;
+    }
+    // ---- step 5: the draw, in ascending index order, in two levels: wave w sums the indices [head + w * cw, head + (w + 1) * cw), every thread finds the
+    // range in which the running sum passes t, the sixteen waves split THAT range again, and one wave walks a sixteenth of a sixteenth.  A lane holds four
+    // consecutive tokens of a block of 256.  The 0-3 tokens of the head come first of all; they go through LDS. ----
+    auto kept_q = [&](long i, float v) -> u64 {
+        u64 c;
+        if (!sample_comp(i, v, c) || c < cut) return 0;
+        return sample_q(v, m, inv_t);
+    };
+    auto block_q = [&](long i, long hi, const float (&v)[4], u64 (&q)[4]) -> u64 {   // (tokens at and past `hi` belong to the next range, or to nobody)
+        u64 sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            q[k] = i + k < hi ? kept_q(i + k, v[k]) : 0;
+            sum += q[k];
+        }
+        return sum;
+    };
+    auto range_sum = [&](long lo, long hi) -> u64 {
+        u64 s = 0;
+        for (long i = lo + 4 * lane; i < hi; i += 512) {
+            float v0[4], v1[4];
+            u64 q[4];
+            sample_load4(row, V, i, v0);
+            sample_load4(row, V, i + 256, v1);
+            s += block_q(i, hi, v0, q);
+            s += block_q(i + 256, hi, v1, q);
+        }
+        return wave_sum(s);
+    };
+    // which of the sixteen ranges holds t, given their sums in sh.wsum; base = the running sum before it (t lies in one of them)
+    auto find_range = [&](u64 t, u64& base) -> int {
+        int w = 0;
+        for (; w < kSampleWaves - 1; w++) {
+            const u64 s = sh.wsum[w];
+            if (t < base + s) break;
+            base += s;
+        }
+        return w;
+    };
+    const long cw = ((V - head + kSampleWaves - 1) / kSampleWaves + 255) / 256 * 256;
+    {
+        const long lo = head + (long)wave * cw;
+        const u64 s = range_sum(lo, lo + cw < V ? lo + cw : V);
+        if (lane == 0) sh.wsum[wave] = s;
+        if (tid < 4) sh.headq[tid] = tid < head ? kept_q(tid, row[tid]) : 0;
+    }
+    __syncthreads();
+    u64 Q = sh.headq[0] + sh.headq[1] + sh.headq[2];
+    for (int w = 0; w < kSampleWaves; w++) Q += sh.wsum[w];
+    const u64 t = __umul64hi(sample_philox(seed, draw_base + (u64)n_tok), Q);   // t < Q; Q >= 2^32: the first token of the order is always kept
+    long tok = -1;
+    u64 base = 0;
+    for (int k = 0; k < 3 && tok < 0; k++) {
+        base += sh.headq[k];
+        if (t < base) tok = k;
+    }
+    if (tok >= 0) {
+        if (tid != 0) return;
+    } else {
+        const int w1 = find_range(t, base);
+        const long lo1 = head + (long)w1 * cw, hi1 = lo1 + cw < V ? lo1 + cw : V;
+        const long cs = cw / kSampleWaves;   // (a multiple of 16: 16-byte loads stay aligned)
+        __syncthreads();
+        {
+            const long lo = lo1 + (long)wave * cs;
+            const u64 s = range_sum(lo, lo + cs < hi1 ? lo + cs : hi1);
+            if (lane == 0) sh.wsum[wave] = s;
+        }
+        __syncthreads();
+        const int w2 = find_range(t, base);
+        if (wave != w2) return;
+        const long lo = lo1 + (long)w2 * cs, hi = lo + cs < hi1 ? lo + cs : hi1;
+        for (long i0 = lo; i0 < hi; i0 += 256) {
+            float v[4];
+            u64 q[4];
+            const long i = i0 + 4 * lane;
+            sample_load4(row, V, i, v);
+            const u64 mine = block_q(i, hi, v, q);
+            const u64 incl = wave_scan(mine, lane);
+            const u64 hit = __ballot(base + incl > t);
+            const u64 total = __shfl(incl, 63);   // (while every lane of the wave is still here)
+            if (hit != 0) {
+                if (lane != __ffsll((long long)hit) - 1) return;
+                u64 acc = base + incl - mine;
+                int k = 0;
+                for (; k < 3; k++) {
+                    acc += q[k];
+                    if (acc > t) break;
+                }
+                tok = i + k;
+                break;
+            }
+            base += total;
+        }
+    }
+    if (tok < 0) return;   // (not reached: this wave's range holds t)
+    if (eos_id >= 0 && tok == (long)eos_id) { state[3] = 1; return; }
+    const int len = state[1];
+    tokens[n_tok] = tok;
+    input_ids[0] = tok;
+    position_ids[0] = len;
+    state[0] = len;
+    state[1] = len + 1;
+    state[2] = n_tok + 1;
+}
+
 __global__ __launch_bounds__(256) void kv_append_at_kernel(const uint16_t* __restrict__ src, uint16_t* __restrict__ cache, const int* __restrict__ row_p,
                                                            int kv_heads, long cap, int d) {
     const long row = *row_p;
@@ -73,6 +414,33 @@ int osg_decode_pick(osg_ctx* ctx, const float* logits, long T, long V, long long
     if (max_tokens < 0 || max_tokens > 0x7fffffffL) OSG_FAIL(ctx, "osg_decode_pick: invalid token budget");
     hipLaunchKernelGGL(decode_pick_kernel, dim3(1), dim3(kPickThreads), 0, ctx->compute, logits + (T - 1) * V, V, eos_id, state, input_ids, position_ids,
                        tokens, max_tokens);
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int osg_decode_sample(osg_ctx* ctx, const float* logits, long T, long V, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
+                      int64_t* tokens, long max_tokens, float temperature, long top_k, float top_p, unsigned long long seed, unsigned long long draw_base) {
+    if (T <= 0 || V <= 0) OSG_FAIL(ctx, "osg_decode_sample: invalid shape of the logits");
+    if (V > (1L << 20)) OSG_FAIL(ctx, "osg_decode_sample: more than 2^20 logits per row");
+    if (!logits || !state || !input_ids || !position_ids || !tokens) OSG_FAIL(ctx, "osg_decode_sample: null operand");
+    if (max_tokens < 0 || max_tokens > 0x7fffffffL) OSG_FAIL(ctx, "osg_decode_sample: invalid token budget");
+    const float inv_t = 1.0f / temperature;
+    if (!(temperature > 0.0f) || !(inv_t > 0.0f) || std::isinf(temperature) || std::isinf(inv_t))
+        OSG_FAIL(ctx, "osg_decode_sample: temperature and 1 / temperature must be positive and finite");
+    if (top_k < 0) OSG_FAIL(ctx, "osg_decode_sample: top_k must be >= 0");
+    if (!(top_p > 0.0f) || !(top_p <= 1.0f)) OSG_FAIL(ctx, "osg_decode_sample: top_p must be in (0, 1]");
+    // top_p = pm * 2^-ps exactly, pm < 2^24 (the fp32 significand as an integer); pm = 0 says top-p is off
+    uint32_t pm = 0;
+    int ps = 0;
+    if (top_p < 1.0f) {
+        uint32_t u;
+        std::memcpy(&u, &top_p, 4);
+        const int e = (int)(u >> 23);
+        pm = e ? ((u & 0x7fffffu) | 0x800000u) : (u & 0x7fffffu);
+        ps = e ? 150 - e : 149;
+    }
+    hipLaunchKernelGGL(decode_sample_kernel, dim3(1), dim3(kSampleThreads), 0, ctx->compute, logits + (T - 1) * V, V, eos_id, state, input_ids, position_ids,
+                       tokens, max_tokens, inv_t, top_k, pm, ps, seed, draw_base);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }

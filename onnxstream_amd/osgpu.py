@@ -29,7 +29,7 @@ EXPORTS = [
     "osg_unary", "osg_binary", "osg_geglu", "osg_transpose", "osg_copy_2d", "osg_concat2", "osg_resize_nearest", "osg_gather_rows",
     "osg_maxpool_nhwc", "osg_convert", "osg_sampler_prepare", "osg_sampler_cfg_euler_a", "osg_sampler_cfg_multistep", "osg_sampler_prepare_rescale",
     "osg_sampler_prepare_single", "osg_sampler_euler_a_single", "osg_sampler_multistep_single", "osg_sampler_cfg_stochastic", "osg_sampler_stochastic_single",
-    "osg_decode_gather", "osg_decode_blend", "osg_decode_pick", "osg_kv_append_at", "osg_sdpa_len",
+    "osg_decode_gather", "osg_decode_blend", "osg_decode_pick", "osg_decode_sample", "osg_kv_append_at", "osg_sdpa_len",
     "osg_range_push", "osg_range_pop", "osg_marker_record", "osg_copy_wait_marker", "osg_timer_mark", "osg_timer_between", "osg_set_stat_sinks", "osg_group_norm_stats_nhwc", "osg_qu8_conv2d_nhwc", "osg_qu8_conv2d_nhwc_t", "osg_qu8_conv_tap_sums", "osg_qu8_gemm", "osg_qu8_lut", "osg_qu8_binary", "osg_qu8_instance_norm", "osg_qu8_instance_norm_nhwc", "osg_qu8_affine_act", "osg_qu8_norm_affine_act_nhwc", "osg_qu8_softmax_last", "osg_kdbg_read",
     "osg_tblock_tail_supported", "osg_tblock_tail", "osg_tblock_kv_pack_elems", "osg_tblock_kv_pack_jobs", "osg_tblock_pack_weight", 
 ]
@@ -132,6 +132,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.osg_decode_pick.argtypes = [vp, vp, cl, cl, ctypes.c_longlong, vp, vp, vp, vp, cl]
         lib.osg_kv_append_at.argtypes = [vp, vp, vp, vp, ci, cl, ci]
         lib.osg_sdpa_len.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, cl, cl, cl, ci, ci, ci, ci, cf]
+    if hasattr(lib, "osg_decode_sample"):
+        lib.osg_decode_sample.argtypes = [vp, vp, cl, cl, ctypes.c_longlong, vp, vp, vp, vp, cl, cf, cl, cf, ctypes.c_ulonglong, ctypes.c_ulonglong]
     lib.osg_set_stat_sinks.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, ci]
     lib.osg_group_norm_stats_nhwc.argtypes = [vp, vp, vp, vp, vp, ci, ctypes.c_long, ci, ci, cf, ci, vp]
     lib.osg_qu8_conv2d_nhwc.argtypes = [vp, vp, cf, ci, vp, cf, ci, vp, cf, ci, vp] + [ci] * 13
@@ -514,6 +516,15 @@ class Gpu:
         t, vv = logits.shape
         assert logits.dtype == np.float32 and state.dtype == np.int32 and state.size >= 4 and ids.dtype == pos.dtype == tokens.dtype == np.int64
         self._ck(self.lib.osg_decode_pick(self.ctx, logits.ptr, t, vv, int(eos_id), state.ptr, ids.ptr, pos.ptr, tokens.ptr, tokens.size))
+
+    def decode_sample(self, logits: DevBuf, eos_id: int, state: DevBuf, ids: DevBuf, pos: DevBuf, tokens: DevBuf, temperature: float, top_k: int = 0,
+                      top_p: float = 1.0, seed: int = 0, draw_base: int = 0):
+        """osg_decode_sample: decode_pick's operands, then the sampling rule of include/osgpu.h (temperature > 0, top_k 0 = off, top_p 1 = off, a 64-bit seed;
+        the draw index is draw_base + state[2])"""
+        t, vv = logits.shape
+        assert logits.dtype == np.float32 and state.dtype == np.int32 and state.size >= 4 and ids.dtype == pos.dtype == tokens.dtype == np.int64
+        self._ck(self.lib.osg_decode_sample(self.ctx, logits.ptr, t, vv, int(eos_id), state.ptr, ids.ptr, pos.ptr, tokens.ptr, tokens.size, float(temperature),
+                                            int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(draw_base) & (2 ** 64 - 1)))
 
     def instance_norm(self, x: DevBuf, scale: Optional[DevBuf], bias: Optional[DevBuf], eps: float, out: Optional[DevBuf] = None):
         rows, L = int(np.prod(x.shape[:-1])), x.shape[-1]

@@ -211,12 +211,15 @@ def forward_resident(m, cfg: LlamaConfig, input_ids, first: bool, P: int, fp16: 
     return logits
 
 
-def generate(m, cfg: LlamaConfig, max_new: int, eos_id: int = -1, sync_every: int = 0, trace: bool = False):
+def generate(m, cfg: LlamaConfig, max_new: int, eos_id: int = -1, sync_every: int = 0, trace: bool = False, temperature: float = 0.0, top_k: int = 0,
+             top_p: float = 1.0, seed: int = 0, draw_base: int = 0):
     """The app's token loop (src/llm.cpp:472-496) on the device, after a forward_resident(..., keep_logits=True) over the prompt: greedy tokens picked and
     run through the Model's resident T = 1 plan without a host round trip per token (bindings.Model.generate).  Leaves the caches opkv* and the logits of
-    the last pass in the Model, as the host loop would.  Returns (tokens, stop, logits trace [n_tokens, V] or None, device ms)."""
+    the last pass in the Model, as the host loop would.  Returns (tokens, stop, logits trace [n_tokens, V] or None, device ms).
+    temperature > 0: sampled tokens instead (temperature, top_k, top_p, seed, draw_base: bindings.Model.generate)."""
     m.set_use_fp16_arithmetic(True)
-    return m.generate(max_new, 2 * cfg.layers, eos_id=eos_id, sync_every=sync_every, trace=trace)
+    return m.generate(max_new, 2 * cfg.layers, eos_id=eos_id, sync_every=sync_every, trace=trace, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
+                      draw_base=draw_base)
 
 
 def configure(m, cfg: LlamaConfig, model_dir: str, sdpa: bool = False, ops_cache: bool = True, upcast: bool = False):

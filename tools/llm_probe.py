@@ -1,6 +1,9 @@
 """Dev tool (GPU box): the LLM flow (synth/llama.py, src/llm.cpp's loop shape) at TinyLlama-1.1B size -- 22 layers, hidden 2048, 32 query / 4 key-value
 heads of 64, MLP 5632, vocabulary 32000, random weights -- prefill of 32 tokens, then greedy decode; wall ms per call, caches resident in the Model (fp16, renamed).
---generate: instead, the host-driven resident loop against the device loop (Model.generate) in one process, 64 tokens each (profiles/llm_generate_probe.txt)."""
+--generate: instead, the host-driven resident loop against the device loop (Model.generate) in one process, 64 tokens each (profiles/llm_generate_probe.txt).
+--generate --temperature T [--top-k K] [--top-p P] [--seed S]: the device loop greedy (twice: their difference is the noise) against the same loop sampling
+by that rule, then osg_decode_sample alone at V = 32000 and 128256; each option takes a comma-separated list, one entry per rule
+(profiles/llm_generate_sampled_probe.txt: --temperature 0.8,1 --top-k 40,0 --top-p 0.9,0.95)."""
 import os, sys, time, tempfile
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -66,8 +69,78 @@ def generate_leg(n_new=64):
     m.close()
 
 
+def _option(name, default, conv):
+    if name not in sys.argv:
+        return None if default is None else [default]
+    return [conv(x) for x in sys.argv[sys.argv.index(name) + 1].split(",")]
+
+
+def sampled_leg(rules, seed, n_new=64):
+    """--generate --temperature ...: warm device-loop calls of n_new tokens after the 32-token prefill in one process -- greedy, greedy again, then one per
+    sampling rule -- and the sampling kernel by itself: the mean of 100 back-to-back launches between two events, over a row of N(0, 3^2) logits."""
+    rng = np.random.default_rng(0)
+    prompt = [int(t) for t in rng.integers(0, cfg.vocab, 32)]
+    m = Model(b.LIB_HOST, 0, "ram+nocache")
+    m._set_option("hip_autotune", 0)
+    m._set_option("hip_resident_outputs", 1)
+    m.add_outputs_convert("logits")
+    llama.configure(m, cfg, d, sdpa=True, upcast=True)
+
+    def leg(name, **kw):
+        m.clear_tensors()
+        llama.forward_resident(m, cfg, prompt, True, 0, keep_logits=True)
+        built = m.hip_plans_built()
+        t0 = time.perf_counter()
+        toks, stop, _, ms = llama.generate(m, cfg, n_new, **kw)
+        wall = (time.perf_counter() - t0) * 1e3
+        print(f"device loop {name}: wall {wall / n_new:.3f} ms/token ({wall:.1f} ms the call), device {ms / n_new:.3f} ms/token, {len(toks)} tokens "
+              f"({len(set(int(t) for t in toks))} distinct), stop {stop}, plans built by the call {m.hip_plans_built() - built}", flush=True)
+
+    leg("greedy, cold (builds and captures the plan)")
+    leg("greedy, warm, first")
+    leg("greedy, warm, second")
+    for t, k, p in rules:
+        leg(f"sampled T {t:g} top_k {k} top_p {p:g} seed {seed}, warm", temperature=t, top_k=k, top_p=p, seed=seed)
+    leg("greedy, warm, third")
+    print(m.hip_decode_plan_info().splitlines()[0], flush=True)
+    m.close()
+
+    from onnxstream_amd import osgpu
+    g = osgpu.Gpu(0)
+    reps = 100
+    for V in (32000, 128256):
+        row = g.to_dev((np.random.default_rng(V).standard_normal((1, V)) * 3).astype(np.float32))
+        ids, pos, toks = g.to_dev(np.zeros(1, np.int64)), g.to_dev(np.zeros(1, np.int64)), g.to_dev(np.zeros(reps + 8, np.int64))
+        for t, k, p in rules:
+            state = g.to_dev(np.array([0, 1, 0, 0], np.int32))
+            for _ in range(8):
+                g.decode_sample(row, -1, state, ids, pos, toks, t, k, p, seed)
+            g.sync()
+            g.timer_start()
+            for _ in range(reps):
+                g.decode_sample(row, -1, state, ids, pos, toks, t, k, p, seed)
+            us = g.timer_stop() * 1e3 / reps
+            print(f"osg_decode_sample alone, V {V}, T {t:g} top_k {k} top_p {p:g}: {us:.1f} us per launch (mean of {reps} back to back), "
+                  f"{int(state.numpy()[2])} tokens taken", flush=True)
+        state = g.to_dev(np.array([0, 1, 0, 0], np.int32))
+        for _ in range(8):
+            g.decode_pick(row, -1, state, ids, pos, toks)
+        g.sync()
+        g.timer_start()
+        for _ in range(reps):
+            g.decode_pick(row, -1, state, ids, pos, toks)
+        print(f"osg_decode_pick alone, V {V}: {g.timer_stop() * 1e3 / reps:.1f} us per launch (mean of {reps} back to back)", flush=True)
+    g.close()
+
+
 if "--generate" in sys.argv:
-    generate_leg()
+    temps = _option("--temperature", None, float)
+    if temps is None:
+        generate_leg()
+    else:
+        ks, ps, seed = _option("--top-k", 0, int), _option("--top-p", 1.0, float), _option("--seed", 0, int)[0]
+        ks, ps = (ks * len(temps))[:len(temps)] if len(ks) == 1 else ks, (ps * len(temps))[:len(temps)] if len(ps) == 1 else ps
+        sampled_leg(list(zip(temps, ks, ps)), seed)
     sys.exit(0)
 
 for sdpa in (True, False):
