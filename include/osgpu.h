@@ -376,6 +376,28 @@ int osg_kv_append_at(osg_ctx* ctx, const void* src, void* cache, const int* row,
 int osg_sdpa_len(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, const void* v, const void* mask, void* o, const int* tkv,
                  long kv_head_stride, long kv_batch_stride, long cap, int batch, int q_heads, int kv_heads, int D, float scale);
 
+/* ---- the same loop for n_seq sequences side by side (model_hip_generate_batch): n_seq states of four int32 each, state + 4 * s that of sequence s;
+ * a sequence that has stopped stays stopped while the others go on, so rows, lengths and positions differ per sequence and are all device values. */
+/* osg_decode_sample for n_seq sequences in ONE launch of n_seq workgroups.  Workgroup s runs the rule of osg_decode_sample, to the letter (the same
+ * device code), over row s of logits [n_seq][V] fp32 with state + 4 * s, input_ids[s], position_ids[s], tokens + s * max_tokens and seed seeds[s]
+ * (seeds: DEVICE uint64 [n_seq]); eos_id, max_tokens, the rule's three parameters and draw_base are shared, the draw index of sequence s is
+ * draw_base + its own n_tokens.  No workgroup reads or writes what belongs to another: sequence s with seed x gets the token osg_decode_sample gives
+ * for that row, that state and seed x, wherever it stands in the batch.  n_seq <= 65535. */
+int osg_decode_sample_batch(osg_ctx* ctx, const float* logits, long V, int n_seq, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
+                            int64_t* tokens, long max_tokens, float temperature, long top_k, float top_p, const unsigned long long* seeds,
+                            unsigned long long draw_base);
+/* osg_kv_append_at per batch: cache[b][h][row_b][0..d) = src[b][h][0..d), src f16 [batch][kv_heads][d], cache [batch][kv_heads][cap][d] (dense),
+ * row_b = state[4 * b].  A row outside [0, cap) writes nothing for that b only.  batch <= 65535. */
+int osg_kv_append_at_batch(osg_ctx* ctx, const void* src, void* cache, const int* state, int batch, int kv_heads, long cap, int d);
+/* osg_sdpa_len with a key count per batch: that of batch b is tkv[b * tkv_stride] (tkv = state + 1, tkv_stride = 4 over the states above), clamped
+ * into [1, cap], one scalar load at the entry of each workgroup.  The arithmetic per (batch, head) is that of osg_sdpa_len: the output of batch b has
+ * the bits of osg_sdpa on dense copies of its first tkv_b rows.  Rows at and past a batch's own length are never read.  batch * q_heads <= 65535. */
+int osg_sdpa_len_batch(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, const void* v, const void* mask, void* o, const int* tkv,
+                       long tkv_stride, long kv_head_stride, long kv_batch_stride, long cap, int batch, int q_heads, int kv_heads, int D, float scale);
+/* osg_rope with a table row per (batch, token): x, y [batch][heads][T][d], cos_t / sin_t [batch][T][d] -- in the batched token loop every sequence
+ * stands at a position of its own.  The arithmetic and the roundings per element are those of osg_rope. */
+int osg_rope_batch(osg_ctx* ctx, osg_dtype dtype, const void* x, const void* cos_t, const void* sin_t, void* y, long batch, long heads, long T, int d);
+
 /* ---- normalisation / reductions ---------------------------------------------------------------------------- */
 /* InstanceNormalization on [rows, L] (reference input [1,G,L], onnxstream.cpp:4788-5055): per row mean/var in f32,
  * y = scale[row % n_scale]*(x-mean)/sqrt(var+eps)+bias[row % n_scale]; scale/bias are f32 (forced f32 at :4802). */

@@ -378,6 +378,41 @@ class Model:
                     tr.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if tr is not None else None, ctypes.byref(ms), *rule))
         return toks[:n.value].copy(), stop.value, (tr[:n.value].copy() if tr is not None else None), ms.value
 
+    def generate_batch(self, n_seq: int, max_new: int, n_caches: int, seeds, temperature: float, top_k: int = 0, top_p: float = 1.0, draw_base: int = 0,
+                       eos_id: int = -1, sync_every: int = 0, trace: bool = False, ids: str = "input_ids", pos: str = "position_ids",
+                       mask: str = "attention_mask", logits: str = "logits", cache_in: str = "pkv", cache_out: str = "opkv"):
+        """n_seq sampled continuations of the one prompt in one call (model_hip_generate_batch): sequence s is `generate` with seed = seeds[s], on caches and
+        a state of its own, and all of them share every pass of a decode plan of batch n_seq.  A sequence that stops, stops alone.  The Model's tensors are
+        left as they were.  seeds: n_seq 64-bit integers (None: the call is refused).  Returns (tokens: list of n_seq int64 arrays [n_tokens[s]],
+        stop int32 [n_seq], traces: list of n_seq float32 arrays [n_tokens[s], V] or None, device ms)."""
+        import numpy as np
+        cp, ip = ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)
+        f = self._lib.model_hip_generate_batch
+        f.argtypes = [ctypes.c_void_p, cp, cp, cp, cp, cp, cp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int,
+                      ctypes.POINTER(ctypes.c_longlong), ip, ip, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), ctypes.c_float,
+                      ctypes.c_longlong, ctypes.c_float, ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_ulonglong]
+        f.restype = ctypes.c_void_p
+        ns, mn = max(int(n_seq), 1), max(int(max_new), 1)
+        sd = None
+        if seeds is not None:
+            sd = np.array([int(x) & (2 ** 64 - 1) for x in seeds], np.uint64)
+            if int(n_seq) >= 1 and sd.size != ns:
+                raise OnnxStreamError("Model::hip_generate_batch: one seed per sequence is needed.")
+        toks = np.zeros((ns, mn), np.int64)
+        tr = None
+        if trace:
+            got = self.get_tensor(logits)
+            if got is None:
+                raise OnnxStreamError("Model::hip_generate_batch: tensor not found: " + logits)
+            tr = np.zeros((ns, mn, got[1][-1]), np.float32)
+        n, stop, ms = np.zeros(ns, np.int32), np.zeros(ns, np.int32), ctypes.c_double(0)
+        self._err(f(self._h, self._name(ids), self._name(pos), self._name(mask), self._name(logits), self._name(cache_in), self._name(cache_out), int(n_caches),
+                    int(n_seq), int(max_new), int(eos_id), int(sync_every), toks.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), n.ctypes.data_as(ip),
+                    stop.ctypes.data_as(ip), tr.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if tr is not None else None, ctypes.byref(ms),
+                    float(temperature), int(top_k), float(top_p), sd.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)) if sd is not None else None,
+                    int(draw_base) & (2 ** 64 - 1)))
+        return ([toks[s, :n[s]].copy() for s in range(ns)], stop, [tr[s, :n[s]].copy() for s in range(ns)] if tr is not None else None, ms.value)
+
     def get_tensor_f16(self, name: str):
         """The bits of a float16 tensor of Model::m_data (an output kept out of m_outputs_convert_set, e.g. a key/value cache of the LLM flow) as a
         numpy float16 array; a device-resident tensor is copied from where it lies and stays there (model_hip_get_tensor_f16)."""

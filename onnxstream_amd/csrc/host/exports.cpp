@@ -507,7 +507,34 @@ char* model_hip_generate_sampled(Handle* h, const char* ids_name, const char* po
         return dup_cstr(e.what());
     }
 }
-// steps of the decode plan model_hip_generate built, as model_hip_plan_info gives them, after a first line "decode capacity <CAP>"; "ERROR: ..." on error
+// n_seq sampled continuations of ONE prompt in one call: after the same batch-1 run() over the prompt, sequence s is exactly the loop of
+// model_hip_generate_sampled with seed = seeds[s] (draw index draw_base + n_tokens[s]), on copies of the prompt's caches of its own and with a state of its
+// own.  The n_seq sequences share every pass: a decode plan of batch n_seq (n_seq is part of its key; a call with another n_seq rebuilds it), whose weights
+// are read once per pass for all of them.  A sequence that stops (eos_id, an invalid row, the budget) stops alone: its picks become no-ops and its slot of
+// the pass recomputes its last token's pass, as the single loop does after a stop; nothing on the device waits.  tokens: [n_seq][max_new] int64; n_tokens,
+// stop: [n_seq]; logits_trace (may be NULL): [n_seq][max_new][V] fp32, rows [s][0 .. n_tokens[s]) are written.  sync_every > 0 ends the call early only once
+// EVERY sequence has stopped.  m_data is left untouched -- the prompt's logits and caches are as before the call, and the caller carries on through run() with
+// the continuation it picks.  Refused, each with "Model::hip_generate_batch: ": what model_hip_generate_sampled refuses, n_seq < 1, seeds == NULL, and
+// temperature == 0 (n_seq greedy sequences are one sequence n_seq times: model_hip_generate gives it).
+char* model_hip_generate_batch(Handle* h, const char* ids_name, const char* pos_name, const char* mask_name, const char* logits_name, const char* cache_in_prefix,
+                               const char* cache_out_prefix, int n_caches, int n_seq, int max_new, long long eos_id, int sync_every, long long* tokens,
+                               int* n_tokens, int* stop, float* logits_trace, double* ms, float temperature, long long top_k, float top_p,
+                               const unsigned long long* seeds, unsigned long long draw_base) {
+    try {
+        Plan::DecodeSpec spec;
+        spec.ids = ids_name; spec.pos = pos_name; spec.mask = mask_name; spec.logits = logits_name;
+        spec.cache_in = cache_in_prefix; spec.cache_out = cache_out_prefix; spec.n_caches = n_caches;
+        Plan::SampleRule rule;
+        rule.temperature = temperature; rule.top_k = (long)top_k; rule.top_p = top_p; rule.draw_base = draw_base;
+        const double v = Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, rule, n_seq, seeds, true);
+        if (ms) *ms = v;
+        return nullptr;
+    } catch (const std::exception& e) {
+        return dup_cstr(e.what());
+    }
+}
+// steps of the decode plan model_hip_generate built, as model_hip_plan_info gives them, after a first line "decode capacity <CAP>" (a plan of n_seq > 1
+// sequences: "decode capacity <CAP> sequences <n_seq>"); "ERROR: ..." on error
 char* model_hip_decode_plan_info(Handle* h) {
     try {
         return dup_cstr(Plan::decode_info(h->model));

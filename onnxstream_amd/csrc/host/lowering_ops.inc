@@ -665,13 +665,23 @@
         const Shape s = V(x).shape;
         need(op, s.size() >= 2, "invalid shape of input.");
         const long d = s.back(), T = s[s.size() - 2];
-        need(op, d % 2 == 0 && V(cs).numel() == T * d && V(sn).numel() == T * d && !V(cs).batched && !V(sn).batched, "cos / sin must be [.., T, d] tables shared by every head.");
+        // (tables of their own per sample: the positions of a decode plan of N sequences -- osg_rope_batch)
+        const bool per_sample = V(cs).batched && V(sn).batched && V(x).batched && N > 1;
+        need(op, d % 2 == 0 && V(cs).numel() == T * d && V(sn).numel() == T * d && (per_sample || (!V(cs).batched && !V(sn).batched)),
+             "cos / sin must be [.., T, d] tables shared by every head.");
         {   // (leading dims of the tables must be 1: one table row per token)
             const Shape cshape = V(cs).shape;
             need(op, cshape.size() >= 2 && cshape.back() == d && cshape[cshape.size() - 2] == T, "invalid shape of the cos / sin tables.");
         }
         const int y = out_val(op, s, Lay::plain, V(x).batched);
         const long bh = P.total_elems(x) / (T * d);
+        if (per_sample) {
+            const long nb = N, heads = bh / nb;
+            P.add_step("RoPE(batch) " + op.m_name, {x, cs, sn}, {y}, [=, this] {
+                be.check(be.api.osg_rope_batch(be.ctx, OSG_F16, P.ptr(x), P.ptr(cs), P.ptr(sn), P.ptr(y), nb, heads, T, (int)d), "RoPE");
+            });
+            return;
+        }
         P.add_step("RoPE " + op.m_name, {x, cs, sn}, {y}, [=, this] { be.check(be.api.osg_rope(be.ctx, OSG_F16, P.ptr(x), P.ptr(cs), P.ptr(sn), P.ptr(y), bh, T, (int)d), "RoPE"); });
     }
 
@@ -1176,8 +1186,16 @@
         const bool k_cap = V(P.root_of(k)).kv_cap, v_cap = V(P.root_of(v)).kv_cap;
         if (k_cap || v_cap) {
             // decode plans: key and value are capacity buffers [Hkv][CAP][D] (S == CAP here), the number of keys is the device-side cache length
-            if (!(k_cap && v_cap && T == 1 && nb == 1 && S == P.dspec.cap && V(k).view_off == 0 && V(v).view_off == 0)) refuse_kv_cap(op);
+            if (!(k_cap && v_cap && T == 1 && Bq == 1 && nb == N && !V(mk).batched && S == P.dspec.cap && V(k).view_off == 0 && V(v).view_off == 0)) refuse_kv_cap(op);
             const long cap = S;
+            if (N > 1) {   // N sequences: the capacity buffers of sequence b follow those of b - 1, its length is state[4 * b + 1]; the mask is shared
+                P.add_step("ScaledDotProductAttention(len, batch) " + op.m_name, {q, k, mk, v}, {y}, [=, this] {
+                    be.check(be.api.osg_sdpa_len_batch(be.ctx, OSG_F16, P.ptr(q), P.ptr(k), P.ptr(v), P.ptr(mk), P.ptr(y), P.dec_state + 1, 4, cap * D, cap * D * Hkv, cap,
+                                                       (int)nb, (int)Hq, (int)Hkv, (int)D, scale),
+                             "ScaledDotProductAttention");
+                });
+                return;
+            }
             P.add_step("ScaledDotProductAttention(len) " + op.m_name, {q, k, mk, v}, {y}, [=, this] {
                 be.check(be.api.osg_sdpa_len(be.ctx, OSG_F16, P.ptr(q), P.ptr(k), P.ptr(v), P.ptr(mk), P.ptr(y), P.dec_state + 1, cap * D, cap * D * Hkv, cap, 1, (int)Hq,
                                              (int)Hkv, (int)D, scale),
@@ -1438,6 +1456,14 @@
                 check_out(op, os);
                 const int y = P.alias(c, os, Lay::plain, op.m_output[0].m_name);
                 const long Hkv = cs[1], d = cs[3], cap = P.dspec.cap;
+                if (N > 1) {   // N sequences: each appends at the row of its own state
+                    need(op, V(r).batched && V(c).batched, "in the device token loop of several sequences every sequence has a cache and a new row of its own.");
+                    const long nb = N;
+                    P.add_step("KVAppend(batch) " + op.m_name, {r, c}, {y}, [=, this] {
+                        be.check(be.api.osg_kv_append_at_batch(be.ctx, P.ptr(r), P.ptr(y), P.dec_state, (int)nb, (int)Hkv, cap, (int)d), "osg_kv_append_at_batch");
+                    });
+                    return;
+                }
                 P.add_step("KVAppend " + op.m_name, {r, c}, {y}, [=, this] {
                     be.check(be.api.osg_kv_append_at(be.ctx, P.ptr(r), P.ptr(y), P.dec_state, (int)Hkv, cap, (int)d), "osg_kv_append_at");
                 });

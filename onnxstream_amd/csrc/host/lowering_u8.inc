@@ -488,9 +488,12 @@
             V(idev).dptr = P.const_alloc(tag, std::max<size_t>(idx.size() * 8, 8), &fresh);
             be.check(be.api.osg_upload_sync(be.ctx, V(idev).dptr, idx.data(), idx.size() * 8), "osg_upload_sync");
         }
-        int y = out_val(op, os, Lay::plain, V(x).batched, V(x).dtype);
+        // a decode plan of N sequences: the device indices are one set per sequence, stacked -- one launch gathers all of them from the shared table
+        const bool idx_batched = dev_idx >= 0 && V(dev_idx).batched;
+        need(op, !(idx_batched && V(x).batched), "per-sample indices into per-sample data are not implemented.");
+        int y = out_val(op, os, Lay::plain, V(x).batched || idx_batched, V(x).dtype);
         const int es = (int)esize(V(x).dtype);
-        const long nb = B(x), n_idx = dev_idx >= 0 ? V(dev_idx).numel() : (long)idx.size(), per_in = V(x).numel(), per_out = n_idx * els;
+        const long nb = B(x), n_idx = dev_idx >= 0 ? P.total_elems(dev_idx) : (long)idx.size(), per_in = V(x).numel(), per_out = n_idx * els;
         P.add_step("Gather " + op.m_name, {x, idev}, {y}, [=, this] {
             for (long b = 0; b < nb; b++)
                 be.check(be.api.osg_gather_rows(be.ctx, es, (const char*)P.ptr(x) + b * per_in * es, (const int64_t*)P.ptr(idev), (char*)P.ptr(y) + b * per_out * es, n_idx,

@@ -414,6 +414,7 @@ Plan::~Plan() {
     if (dec_state) be.api.osg_free(be.ctx, dec_state);
     if (dec_tokens) be.api.osg_free(be.ctx, dec_tokens);
     if (dec_trace) be.api.osg_free(be.ctx, dec_trace);
+    if (dec_seeds) be.api.osg_free(be.ctx, dec_seeds);
     if (ring) be.free(ring);
     for (void* p : owned) be.free(p);
     if (arena && !arena_pooled) be.free(arena);
@@ -503,10 +504,11 @@ void Plan::build() {
             inp.shape = src->m_shape;
             if (src->m_type == TensorDataType::int64) {
                 // token ids / positions / masks of the LLM graphs: values known now, consumed by plan-time evaluation (Lowering::try_host_eval)
-                if (u8 || N != 1) throw std::invalid_argument("Model::run: int64 graph inputs need one sample per pass and floating-point arithmetic (" + iname + ").");
+                // (a decode plan of N sequences: one token and one position per sequence, the mask -- a plan-time value -- shared by all of them)
+                if (u8 || (N != 1 && !decode)) throw std::invalid_argument("Model::run: int64 graph inputs need one sample per pass and floating-point arithmetic (" + iname + ").");
                 if (decode && (iname == dspec.ids || iname == dspec.pos)) {
                     // the token and its position change per pass and are written on the device (osg_decode_pick): a staging buffer, no plan-time value
-                    inp.staging = inp.val = new_val(iname, shape, OSG_I64, Lay::plain, false);
+                    inp.staging = inp.val = new_val(iname, shape, OSG_I64, Lay::plain, N > 1);
                     vals[inp.val].dptr = small_alloc(std::max<size_t>(val_bytes(inp.val), 8));
                     vals[inp.val].pinned = true;
                     vals[inp.val].dev_int = true;
@@ -536,13 +538,15 @@ void Plan::build() {
             if (src->m_type == TensorDataType::float16 && prod(shape) != 0) {
                 // an output the caller kept in fp16 (m_outputs_convert_set excludes it) and feeds back under another name: the LLM app's
                 // opkv* -> pkv* renaming (src/llm.cpp:403-407).  Uploaded as it is, no rounding step.
-                if (N != 1) throw std::invalid_argument("Model::run: float16 graph inputs need one sample per pass (" + iname + ").");
+                const bool dec_cache = decode && cache_index(iname, dspec.cache_in) >= 0;
+                if (N != 1 && !dec_cache) throw std::invalid_argument("Model::run: float16 graph inputs need one sample per pass (" + iname + ").");
                 inp.staging = inp.val = new_val(iname, shape, OSG_F16, Lay::plain, true);
-                if (decode && cache_index(iname, dspec.cache_in) >= 0) {
-                    // a cache of the decode plan: [1, Hkv, CAP - 1, d] by its shape, in a buffer of CAP rows per head -- the Concat appends in place (lower_concat)
+                if (dec_cache) {
+                    // a cache of the decode plan: [1, Hkv, CAP - 1, d] by its shape, in a buffer of CAP rows per head -- the Concat appends in place (lower_concat);
+                    // N sequences: N such buffers behind each other
                     if (shape.size() != 4 || shape[0] != 1 || shape[2] != dspec.cap - 1)
                         throw std::invalid_argument("Model::hip_generate: cache '" + iname + "' must be a [1, Hkv, P, d] tensor.");
-                    vals[inp.val].dptr = small_alloc((size_t)shape[1] * dspec.cap * shape[3] * 2);
+                    vals[inp.val].dptr = small_alloc((size_t)N * shape[1] * dspec.cap * shape[3] * 2);
                     vals[inp.val].kv_cap = true;
                 } else
                     vals[inp.val].dptr = small_alloc(val_bytes(inp.val));

@@ -341,19 +341,22 @@ struct Plan {
     bool decode = false;
     DecodeSpec dspec;
     std::vector<Tensor>* build_inputs = nullptr;
-    int* dec_state = nullptr;                 // device int32[4]: row, len, n_tokens, stop (include/osgpu.h, osg_decode_pick)
+    int* dec_state = nullptr;                 // device int32[4] per sequence (N of them): row, len, n_tokens, stop (include/osgpu.h, osg_decode_pick)
     long dec_pos_limit = 1L << 62, dec_tok_limit = 1L << 62;   // rows of the smallest table a Gather indexes with position_ids / input_ids
-    void* dec_tokens = nullptr;               // device int64 [max_new]
-    void* dec_trace = nullptr;                // device fp32 [max_new, V]
-    size_t dec_tokens_bytes = 0, dec_trace_bytes = 0;
+    void* dec_tokens = nullptr;               // device int64 [N][max_new]
+    void* dec_trace = nullptr;                // device fp32 [N][max_new, V]
+    void* dec_seeds = nullptr;                // device uint64 [N]: the seeds of a generate_batch call
+    size_t dec_tokens_bytes = 0, dec_trace_bytes = 0, dec_seeds_bytes = 0;
     int cache_index(const std::string& name, const std::string& prefix) const;   // i of "<prefix><i>", i < n_caches; -1 otherwise
     // the reference app's token loop (src/llm.cpp:472-496) on the device: see model_hip_generate (exports.cpp) for the contract.  A static member of Plan
     // for the reason given at run_sampler_loop_multistep; the decode plan itself is kept in the Model's ConstPool.
     // how a token is taken from the logits: default-constructed = greedy, the app's argmax (osg_decode_pick); temperature > 0 = the sampling rule of
     // include/osgpu.h (osg_decode_sample).  Sampling is outside the decode plan: the plan, its capacity, its capture and its text are the same either way.
     struct SampleRule { float temperature = 0.0f; long top_k = 0; float top_p = 1.0f; unsigned long long seed = 0, draw_base = 0; };
+    // batch (model_hip_generate_batch): n_seq sampled sequences from the one prompt in a decode plan of batch n_seq, sequence s with seeds[s] and its own
+    // state, caches and stop; the outputs are arrays over the sequences and m_data is left untouched.  n_seq is part of the decode plan's key.
     static double generate(Model& m, const DecodeSpec& names, int max_new, long long eos_id, int sync_every, int64_t* tokens, int* n_tokens, int* stop,
-                           float* logits_trace, const SampleRule& rule);
+                           float* logits_trace, const SampleRule& rule, int n_seq = 1, const unsigned long long* seeds = nullptr, bool batch = false);
     static std::string decode_info(Model& m);
     // a copy of a device-resident tensor's bytes (Tensor::m_hip_resident) for the host; the tensor stays where it is (model_hip_get_tensor_f16)
     static void read_resident(Model& m, const Tensor& t, void* dst);

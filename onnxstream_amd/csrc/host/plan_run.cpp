@@ -827,11 +827,19 @@ std::string Plan::decode_info(Model& m) {
 // The reference app's token loop (src/llm.cpp:472-496) with the argmax, the cache append and the cache length on the device: max_new x (osg_decode_pick + the
 // T = 1 pass of the Model's resident decode plan) enqueued back to back.  model_hip_generate (exports.cpp) states the contract.  With a sampling rule
 // (model_hip_generate_sampled) osg_decode_sample stands where the pick stands; nothing else differs.
+// n_seq / seeds (model_hip_generate_batch, `batch` set): n_seq sequences from the one prompt, side by side in a decode plan of batch n_seq -- tokens
+// [n_seq][max_new], n_tokens / stop [n_seq], logits_trace [n_seq][max_new][V], sequence s sampled with seeds[s]; m_data is left as it was.
 double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long eos_id, int sync_every, int64_t* tokens, int* n_tokens, int* stop,
-                      float* logits_trace, const SampleRule& rule) {
-    static const std::string fn = "Model::hip_generate: ";
-    if (n_tokens) *n_tokens = 0;
-    if (stop) *stop = 0;
+                      float* logits_trace, const SampleRule& rule, int n_seq, const unsigned long long* seeds, bool batch) {
+    const std::string fn = batch ? "Model::hip_generate_batch: " : "Model::hip_generate: ";
+    if (batch && n_seq < 1) throw std::invalid_argument(fn + "n_seq must be >= 1.");
+    for (int s = 0; s < n_seq; s++) {
+        if (n_tokens) n_tokens[s] = 0;
+        if (stop) stop[s] = 0;
+    }
+    if (batch && !seeds) throw std::invalid_argument(fn + "no seeds (one per sequence).");
+    if (batch && rule.temperature == 0.0f)
+        throw std::invalid_argument(fn + "temperature must be > 0: greedy sequences from one prompt are all the same sequence (model_hip_generate gives it).");
     if (max_new < 0) throw std::invalid_argument(fn + "max_new must be >= 0.");
     if (!(rule.temperature >= 0.0f) || std::isinf(rule.temperature)) throw std::invalid_argument(fn + "temperature must be finite and >= 0 (0 = greedy).");
     if (rule.temperature > 0.0f && std::isinf(1.0f / rule.temperature)) throw std::invalid_argument(fn + "temperature is too small: 1 / temperature is not finite.");
@@ -890,7 +898,7 @@ double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long 
     for (auto& e : m.m_extra_outputs) key += e + ",";
     key += "|";
     for (auto& e : m.m_outputs_convert_set) key += e + ",";
-    key += "|";
+    key += "|" + std::to_string(n_seq) + "|";
     if (m.m_requires_upcast)
         for (auto& op : m.m_ops) key += m.m_requires_upcast(op.m_type, op.m_name) ? '1' : '0';
     Plan* dp = pool.decode_plan;
@@ -918,19 +926,19 @@ double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long 
             t.set_vector(tensor_vector<uint16_t>());
             fake.push_back(std::move(t));
         }
-        dp = new Plan(m, be, pool, 1);
+        dp = new Plan(m, be, pool, (size_t)n_seq);
         dp->decode = true;
         dp->dspec = names;
         dp->dspec.cap = cap;
         dp->build_inputs = &fake;
         m.m_plans_built++;
         try {
-            dp->dec_state = (int*)be.malloc(16);
+            dp->dec_state = (int*)be.malloc(16 * (size_t)n_seq);
             dp->build();
             dp->build_inputs = nullptr;
             // the plan must really be the loop's: one in-place append per cache, the token and position inputs, the logits as an fp32 output
             size_t appends = 0;
-            for (auto& s : dp->steps) appends += s.what.rfind("KVAppend ", 0) == 0;
+            for (auto& s : dp->steps) appends += s.what.rfind("KVAppend ", 0) == 0 || s.what.rfind("KVAppend(batch) ", 0) == 0;
             if (appends != (size_t)names.n_caches)
                 throw std::invalid_argument(fn + "the graph appends to " + std::to_string(appends) + " caches named '" + names.cache_in + "<i>' -> '" + names.cache_out +
                                             "<i>', the call names " + std::to_string(names.n_caches) + ".");
@@ -971,8 +979,9 @@ double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long 
     const long cap = dp->dspec.cap;
     FlightGuard flight(dp->in_flight);
     // ---- entry: state, the caches into their capacity buffers (strided copies), the last row of the prompt's logits into the pass's logits buffer ----
-    dp->sampler_grow(dp->dec_tokens, dp->dec_tokens_bytes, (size_t)max_new * 8);
-    if (logits_trace) dp->sampler_grow(dp->dec_trace, dp->dec_trace_bytes, (size_t)max_new * V * sizeof(float));
+    dp->sampler_grow(dp->dec_tokens, dp->dec_tokens_bytes, (size_t)n_seq * max_new * 8);
+    if (logits_trace) dp->sampler_grow(dp->dec_trace, dp->dec_trace_bytes, (size_t)n_seq * max_new * V * sizeof(float));
+    if (batch) dp->sampler_grow(dp->dec_seeds, dp->dec_seeds_bytes, (size_t)n_seq * 8);
     std::vector<size_t> slot((size_t)names.n_caches + 1, 0);      // scratch for host-side caches, on the way in (P rows) and out (up to P + max_new rows)
     for (int i = 0; i < names.n_caches; i++) slot[(size_t)i + 1] = slot[(size_t)i] + (((size_t)geo[i][0] * (P + max_new) * geo[i][1] * 2 + 255) & ~(size_t)255);
     struct Scratch {
@@ -981,11 +990,13 @@ double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long 
     } scratch{be};
     std::vector<char> was_resident((size_t)names.n_caches, 0);
     // (a loop that stops at its first pick still runs its passes: they append nowhere -- row -1 -- and gather row 0 of the tables)
-    const int st0[4] = {-1, (int)P, 0, 0};
-    be.check(be.api.osg_upload(be.ctx, dp->dec_state, st0, sizeof st0), "osg_upload");
-    const int64_t zero = 0;
-    be.check(be.api.osg_upload(be.ctx, dp->ptr(in_ids->staging), &zero, 8), "osg_upload");
-    be.check(be.api.osg_upload(be.ctx, dp->ptr(in_pos->staging), &zero, 8), "osg_upload");
+    std::vector<int> st((size_t)n_seq * 4, 0);
+    for (int s = 0; s < n_seq; s++) { st[4 * (size_t)s] = -1; st[4 * (size_t)s + 1] = (int)P; }
+    be.check(be.api.osg_upload(be.ctx, dp->dec_state, st.data(), st.size() * sizeof(int)), "osg_upload");
+    if (batch) be.check(be.api.osg_upload(be.ctx, dp->dec_seeds, seeds, (size_t)n_seq * 8), "osg_upload");
+    const std::vector<int64_t> zeros((size_t)n_seq, 0);
+    be.check(be.api.osg_upload(be.ctx, dp->ptr(in_ids->staging), zeros.data(), zeros.size() * 8), "osg_upload");
+    be.check(be.api.osg_upload(be.ctx, dp->ptr(in_pos->staging), zeros.data(), zeros.size() * 8), "osg_upload");
     for (int i = 0; i < names.n_caches; i++) {
         Tensor& c = find(names.cache_out + std::to_string(i));
         const long Hkv = geo[i][0], d = geo[i][1];
@@ -996,17 +1007,29 @@ double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long 
             be.check(be.api.osg_upload(be.ctx, (char*)scratch.p + slot[(size_t)i], c.get_vector<uint16_t>().data(), (size_t)Hkv * P * d * 2), "osg_upload");
             src = (char*)scratch.p + slot[(size_t)i];
         }
-        be.check(be.api.osg_copy_2d(be.ctx, 2, src, P * d, 0, dp->ptr(in_cache[(size_t)i]->val), cap * d, 0, Hkv, P * d), "osg_copy_2d");
+        for (int s = 0; s < n_seq; s++)      // (every sequence starts from a copy of the prompt's cache in capacity buffers of its own)
+            be.check(be.api.osg_copy_2d(be.ctx, 2, src, P * d, 0, (char*)dp->ptr(in_cache[(size_t)i]->val) + (size_t)s * Hkv * cap * d * 2, cap * d, 0, Hkv, P * d),
+                     "osg_copy_2d");
     }
-    float* lg_dev = (float*)dp->ptr(out_lg->f32val);
-    be.check(be.api.osg_upload(be.ctx, lg_dev, lg.get_vector<float>().data() + (size_t)(T0 - 1) * V, (size_t)V * sizeof(float)), "osg_upload");
+    float* lg_dev = (float*)dp->ptr(out_lg->f32val);      // [n_seq][V]
+    for (int s = 0; s < n_seq; s++)
+        be.check(be.api.osg_upload(be.ctx, lg_dev + (size_t)s * V, lg.get_vector<float>().data() + (size_t)(T0 - 1) * V, (size_t)V * sizeof(float)), "osg_upload");
     int64_t *ids_dev = (int64_t*)dp->ptr(in_ids->staging), *pos_dev = (int64_t*)dp->ptr(in_pos->staging);
     // ---- the loop: nothing on the device waits -- once the stop code is set, a pick is a no-op and a pass recomputes the last token's pass (same inputs, same row) ----
-    int st[4] = {0, 0, 0, 0};
+    auto all_stopped = [&] {
+        for (int s = 0; s < n_seq; s++)
+            if (!st[4 * (size_t)s + 3]) return false;
+        return true;
+    };
+    std::fill(st.begin(), st.end(), 0);
     int passes = 0;
     be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");
     for (int n = 0; n < max_new; n++) {
-        if (rule.temperature > 0.0f)
+        if (batch)
+            be.check(be.api.osg_decode_sample_batch(be.ctx, lg_dev, V, n_seq, eos_id, dp->dec_state, ids_dev, pos_dev, (int64_t*)dp->dec_tokens, max_new,
+                                                    rule.temperature, rule.top_k, rule.top_p, (const unsigned long long*)dp->dec_seeds, rule.draw_base),
+                     "osg_decode_sample_batch");
+        else if (rule.temperature > 0.0f)
             be.check(be.api.osg_decode_sample(be.ctx, lg_dev, 1, V, eos_id, dp->dec_state, ids_dev, pos_dev, (int64_t*)dp->dec_tokens, max_new, rule.temperature,
                                               rule.top_k, rule.top_p, rule.seed, rule.draw_base),
                      "osg_decode_sample");
@@ -1032,25 +1055,44 @@ double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long 
             dp->run_steps();
         dp->runs++;
         passes++;
-        if (logits_trace) be.check(be.api.osg_copy(be.ctx, (char*)dp->dec_trace + (size_t)n * V * sizeof(float), lg_dev, (size_t)V * sizeof(float)), "osg_copy");
+        if (logits_trace && n_seq == 1)
+            be.check(be.api.osg_copy(be.ctx, (char*)dp->dec_trace + (size_t)n * V * sizeof(float), lg_dev, (size_t)V * sizeof(float)), "osg_copy");
+        else if (logits_trace)      // row n of every sequence's trace [max_new][V] in one strided copy
+            be.check(be.api.osg_copy_2d(be.ctx, 4, lg_dev, V, 0, dp->dec_trace, (long)max_new * V, (long)n * V, n_seq, V), "osg_copy_2d");
         if (sync_every > 0 && (n + 1) % sync_every == 0 && n + 1 < max_new) {
-            be.check(be.api.osg_download(be.ctx, st, dp->dec_state, sizeof st), "osg_download");
-            if (st[3]) break;
+            be.check(be.api.osg_download(be.ctx, st.data(), dp->dec_state, st.size() * sizeof(int)), "osg_download");
+            if (all_stopped()) break;
         }
     }
     float ms = 0;
     be.check(be.api.osg_timer_stop(be.ctx, &ms), "osg_timer_stop");
     // ---- exit: the state, the tokens, the trace; then m_data as the host loop would have left it ----
-    be.check(be.api.osg_download(be.ctx, st, dp->dec_state, sizeof st), "osg_download");
+    be.check(be.api.osg_download(be.ctx, st.data(), dp->dec_state, st.size() * sizeof(int)), "osg_download");
+    for (int s = 0; s < n_seq; s++) {
+        const int* q = &st[4 * (size_t)s];
+        if (q[2] < 0 || q[2] > max_new || q[1] != P + q[2]) throw std::runtime_error(fn + "the device-side loop state is inconsistent.");
+    }
+    dp->m_last_ms = passes ? ms / passes : 0;
+    m.m_last_ms = dp->m_last_ms;
+    m.m_last_kernels = dp->kernel_count();
+    if (batch) {
+        // every sequence's tokens and trace rows up to its own count; m_data stays as it was -- the caller carries on from the continuation it picks
+        for (int s = 0; s < n_seq; s++) {
+            const size_t nt = (size_t)st[4 * (size_t)s + 2], at = (size_t)s * max_new;
+            if (nt) be.check(be.api.osg_download(be.ctx, tokens + at, (char*)dp->dec_tokens + at * 8, nt * 8), "osg_download");
+            if (nt && logits_trace)
+                be.check(be.api.osg_download(be.ctx, logits_trace + at * V, (char*)dp->dec_trace + at * V * sizeof(float), nt * V * sizeof(float)), "osg_download");
+            if (n_tokens) n_tokens[s] = (int)nt;
+            if (stop) stop[s] = st[4 * (size_t)s + 3];
+        }
+        be.check(be.api.osg_sync(be.ctx), "osg_sync");
+        return ms;
+    }
     const int nt = st[2];
-    if (nt < 0 || nt > max_new || st[1] != P + nt) throw std::runtime_error(fn + "the device-side loop state is inconsistent.");
     if (nt) be.check(be.api.osg_download(be.ctx, tokens, dp->dec_tokens, (size_t)nt * 8), "osg_download");
     if (nt && logits_trace) be.check(be.api.osg_download(be.ctx, logits_trace, dp->dec_trace, (size_t)nt * V * sizeof(float)), "osg_download");
     if (n_tokens) *n_tokens = nt;
     if (stop) *stop = st[3];
-    dp->m_last_ms = passes ? ms / passes : 0;
-    m.m_last_ms = dp->m_last_ms;
-    m.m_last_kernels = dp->kernel_count();
     if (nt == 0) return ms;          // no pass of the host loop ran: logits and caches stay as they are
     const long Pf = P + nt;
     auto replace = [&](Tensor&& t) {
@@ -1103,7 +1145,7 @@ double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long 
 std::string Plan::info() const {
     std::string out;
     char buf[128];
-    if (decode) out += "decode capacity " + std::to_string(dspec.cap) + "\n";
+    if (decode) out += "decode capacity " + std::to_string(dspec.cap) + (N > 1 ? " sequences " + std::to_string(N) : "") + "\n";
     for (size_t i = 0; i < steps.size(); i++) {
         const Step& s = steps[i];
         snprintf(buf, sizeof buf, "step %zu reads=", i);

@@ -299,6 +299,15 @@ __global__ __launch_bounds__(256) void attn_len_kernel(AttnParams p, const int* 
     attn_body<DP, DT, 1, 64>(p);
 }
 
+// osg_sdpa_len_batch: the same, every batch with a key count of its own -- tkv[b * tkv_stride], b = blockIdx.y / heads.  The index is uniform over
+// the workgroup, so the count is one scalar load at entry, as above.
+template <int DP, int DT>
+__global__ __launch_bounds__(256) void attn_len_batch_kernel(AttnParams p, const int* __restrict__ tkv, long tkv_stride, int cap) {
+    const int b = blockIdx.y / p.heads;
+    p.Tkv = min(max(tkv[b * tkv_stride], 1), cap);
+    attn_body<DP, DT, 1, 64>(p);
+}
+
 // =====================================================================================================================================
 // v2 (round 5) -- the UNet's attention shapes (no mask, head dim 40 / 64 / 80 / 160).  Same mapping and the same online softmax as attn_kernel,
 // but the per-tile instruction count of a wave is roughly halved (the kernel is issue-bound: ~380 instructions per 64-key tile and wave around 28 MFMAs):
@@ -710,6 +719,27 @@ int dispatch_attn_len(osg_ctx* ctx, const AttnParams& p, int batch, const int* t
     OSG_FAIL(ctx, "osg_sdpa_len: head dim > 160 not implemented");
 }
 
+template <int DP, int DT>
+int launch_attn_len_batch(osg_ctx* ctx, const AttnParams& p, int batch, const int* tkv, long tkv_stride, int cap) {
+    dim3 grid(1, batch * p.heads);
+    osg_set_kernel(ctx, 0, 1, DP, DT, 1, 64, (int)grid.y);
+    hipLaunchKernelGGL((attn_len_batch_kernel<DP, DT>), grid, dim3(256), 0, ctx->compute, p, tkv, tkv_stride, cap);
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int dispatch_attn_len_batch(osg_ctx* ctx, const AttnParams& p, int batch, const int* tkv, long tkv_stride, int cap) {
+    const int D = p.D;
+    if (D <= 32) return launch_attn_len_batch<32, 2>(ctx, p, batch, tkv, tkv_stride, cap);
+    if (D <= 48) return launch_attn_len_batch<64, 3>(ctx, p, batch, tkv, tkv_stride, cap);
+    if (D <= 64) return launch_attn_len_batch<64, 4>(ctx, p, batch, tkv, tkv_stride, cap);
+    if (D <= 80) return launch_attn_len_batch<96, 5>(ctx, p, batch, tkv, tkv_stride, cap);
+    if (D <= 96) return launch_attn_len_batch<96, 6>(ctx, p, batch, tkv, tkv_stride, cap);
+    if (D <= 128) return launch_attn_len_batch<128, 8>(ctx, p, batch, tkv, tkv_stride, cap);
+    if (D <= 160) return launch_attn_len_batch<160, 10>(ctx, p, batch, tkv, tkv_stride, cap);
+    OSG_FAIL(ctx, "osg_sdpa_len_batch: head dim > 160 not implemented");
+}
+
 int dispatch_attn(osg_ctx* ctx, const AttnParams& p, int batch) {
     const int D = p.D;
     // the UNet's shapes: v2 (OSG_ATTN_V1=1: the round-2 kernel, for A/B).  K / V rows must be 16-byte aligned (checked by the callers); the DMA offsets are 32-bit
@@ -778,6 +808,25 @@ int osg_sdpa_len(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, co
     AttnParams p{(const f16*)q, (const f16*)k, (const f16*)v, (f16*)o, D, qh, qh * q_heads, D, kv_head_stride, kv_batch_stride, D, kv_head_stride,
                  kv_batch_stride, D, qh, qh * q_heads, q_heads, 1, 1, D, scale * 1.4426950408889634f, (const f16*)mask, 1.0f / scale, q_heads / kv_heads};
     return dispatch_attn_len(ctx, p, batch, tkv, (int)cap);
+}
+
+int osg_sdpa_len_batch(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, const void* v, const void* mask, void* o, const int* tkv,
+                       long tkv_stride, long kv_head_stride, long kv_batch_stride, long cap, int batch, int q_heads, int kv_heads, int D, float scale) {
+    if (dtype != OSG_F16) OSG_FAIL(ctx, "osg_sdpa_len_batch: only f16 arithmetic is implemented on the device");
+    if (batch <= 0 || q_heads <= 0 || kv_heads <= 0 || D <= 0 || cap <= 0 || cap > 0x7fffffffL || (long)batch * q_heads > 65535)
+        OSG_FAIL(ctx, "osg_sdpa_len_batch: invalid shape of query, key or value.");
+    if (q_heads % kv_heads) OSG_FAIL(ctx, "osg_sdpa_len_batch: query heads must be a multiple of key/value heads.");
+    if (!q || !k || !v || !o || !tkv) OSG_FAIL(ctx, "osg_sdpa_len_batch: null operand");
+    if (tkv_stride < 0) OSG_FAIL(ctx, "osg_sdpa_len_batch: the stride of the key counts must be >= 0");
+    if (!mask) OSG_FAIL(ctx, "osg_sdpa_len_batch: a mask [cap] is required (the mask-less route of osg_sdpa is another kernel)");
+    if (!(scale > 0.f)) OSG_FAIL(ctx, "osg_sdpa_len_batch: the fused kernel tracks the row maximum of the raw scores and needs scale > 0");
+    if (D % 8) OSG_FAIL(ctx, "osg_sdpa_len_batch: head dim must be a multiple of 8");
+    if (kv_head_stride < cap * D || (kv_head_stride | kv_batch_stride) % 8 || (batch > 1 && kv_batch_stride < kv_head_stride * kv_heads))
+        OSG_FAIL(ctx, "osg_sdpa_len_batch: the head stride must hold cap rows, strides must keep 16-byte alignment");
+    const long qh = D;
+    AttnParams p{(const f16*)q, (const f16*)k, (const f16*)v, (f16*)o, D, qh, qh * q_heads, D, kv_head_stride, kv_batch_stride, D, kv_head_stride,
+                 kv_batch_stride, D, qh, qh * q_heads, q_heads, 1, 1, D, scale * 1.4426950408889634f, (const f16*)mask, 1.0f / scale, q_heads / kv_heads};
+    return dispatch_attn_len_batch(ctx, p, batch, tkv, tkv_stride, (int)cap);
 }
 
 int osg_attention(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, const void* v, void* o, int heads, int Tq, int Tkv, int D,

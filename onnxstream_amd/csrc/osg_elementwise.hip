@@ -246,6 +246,22 @@ __global__ __launch_bounds__(256) void rope_kernel(const f16* __restrict__ x, co
     y[i] = (f16)((float)a + (float)b);
 }
 
+// rope_kernel with a table row per (batch, token): x [B][H][T][d], cos / sin [B][T][d] -- the token loop's batch, every sequence at a position of its own
+__global__ __launch_bounds__(256) void rope_batch_kernel(const f16* __restrict__ x, const f16* __restrict__ cs, const f16* __restrict__ sn, f16* __restrict__ y, long n,
+                                                         long heads, long T, int d) {
+#pragma clang fp contract(off)
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int j = (int)(i % d), half = d >> 1;
+    const long r = i / d, t = r % T, b = r / (T * heads);
+    const float xv = (float)x[i];
+    const float rot = j < half ? -(float)x[i + half] : (float)x[i - half];
+    const long c = (b * T + t) * d + j;
+    const f16 a = (f16)(xv * (float)cs[c]);
+    const f16 bb = (f16)(rot * (float)sn[c]);
+    y[i] = (f16)((float)a + (float)bb);
+}
+
 }  // namespace
 
 extern "C" {
@@ -258,6 +274,17 @@ int osg_rope(osg_ctx* ctx, osg_dtype dtype, const void* x, const void* cos_t, co
     if (d % 2) OSG_FAIL(ctx, "osg_rope: the head dim must be even");
     const long n = bh * T * d;
     hipLaunchKernelGGL(rope_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->compute, (const f16*)x, (const f16*)cos_t, (const f16*)sin_t, (f16*)y, n, T, d);
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int osg_rope_batch(osg_ctx* ctx, osg_dtype dtype, const void* x, const void* cos_t, const void* sin_t, void* y, long batch, long heads, long T, int d) {
+    if (batch <= 0 || heads <= 0 || T <= 0 || d <= 0) return 0;
+    if (dtype != OSG_F16) OSG_FAIL(ctx, "osg_rope_batch: only f16 arithmetic is implemented on the device");
+    if (d % 2) OSG_FAIL(ctx, "osg_rope_batch: the head dim must be even");
+    const long n = batch * heads * T * d;
+    hipLaunchKernelGGL(rope_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->compute, (const f16*)x, (const f16*)cos_t, (const f16*)sin_t, (f16*)y, n,
+                       heads, T, d);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }

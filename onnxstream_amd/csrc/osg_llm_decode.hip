@@ -6,6 +6,7 @@
 //   osg_decode_sample <- in the pick's place when the caller samples: temperature, top-k, top-p and a seeded draw over the same row by the integer rule
 //                       of include/osgpu.h, then the same state advance
 //   osg_kv_append_at <- the cache Concat (pkv ++ new row, axis 2) in place: the new row of every head into a capacity buffer at the device-side row
+//   osg_decode_sample_batch, osg_kv_append_at_batch <- the same two for n_seq sequences side by side, each with its own state (model_hip_generate_batch)
 // (osg_sdpa_len, the attention over such buffers, lives next to osg_sdpa in osg_attention.hip.)
 #include <cmath>
 #include <cstring>
@@ -247,10 +248,11 @@ __device__ __forceinline__ u64 sample_philox(u64 seed, u64 n) {
     return (u64)c0 | ((u64)c1 << 32);
 }
 
-__global__ __launch_bounds__(kSampleThreads) void decode_sample_kernel(const float* __restrict__ row, long V, long long eos_id, int* __restrict__ state,
-                                                                       int64_t* __restrict__ input_ids, int64_t* __restrict__ position_ids,
-                                                                       int64_t* __restrict__ tokens, long max_tokens, float inv_t, long top_k, uint32_t pm,
-                                                                       int ps, u64 seed, u64 draw_base) {
+// the rule, for the workgroup that runs it: osg_decode_sample launches one over the one sequence, osg_decode_sample_batch one per sequence over its own
+// row, state, staging slots, token list and seed -- ONE body, so the two cannot drift apart
+__device__ __forceinline__ void decode_sample_body(const float* __restrict__ row, long V, long long eos_id, int* __restrict__ state,
+                                                   int64_t* __restrict__ input_ids, int64_t* __restrict__ position_ids, int64_t* __restrict__ tokens,
+                                                   long max_tokens, float inv_t, long top_k, uint32_t pm, int ps, u64 seed, u64 draw_base) {
     const int n_tok = state[2];
     if (state[3] != 0 || (long)n_tok >= max_tokens) return;   // as osg_decode_pick: uniform, nothing is read or written any more
     __shared__ SampleShared sh;
@@ -393,6 +395,34 @@ __global__ __launch_bounds__(kSampleThreads) void decode_sample_kernel(const flo
     state[2] = n_tok + 1;
 }
 
+__global__ __launch_bounds__(kSampleThreads) void decode_sample_kernel(const float* __restrict__ row, long V, long long eos_id, int* __restrict__ state,
+                                                                       int64_t* __restrict__ input_ids, int64_t* __restrict__ position_ids,
+                                                                       int64_t* __restrict__ tokens, long max_tokens, float inv_t, long top_k, uint32_t pm,
+                                                                       int ps, u64 seed, u64 draw_base) {
+    decode_sample_body(row, V, eos_id, state, input_ids, position_ids, tokens, max_tokens, inv_t, top_k, pm, ps, seed, draw_base);
+}
+
+// workgroup s = sequence s: everything it touches is indexed by blockIdx.x alone (uniform: the seed is one scalar load)
+__global__ __launch_bounds__(kSampleThreads) void decode_sample_batch_kernel(const float* __restrict__ logits, long V, long long eos_id, int* __restrict__ state,
+                                                                             int64_t* __restrict__ input_ids, int64_t* __restrict__ position_ids,
+                                                                             int64_t* __restrict__ tokens, long max_tokens, float inv_t, long top_k,
+                                                                             uint32_t pm, int ps, const u64* __restrict__ seeds, u64 draw_base) {
+    const long s = blockIdx.x;
+    decode_sample_body(logits + s * V, V, eos_id, state + 4 * s, input_ids + s, position_ids + s, tokens + s * max_tokens, max_tokens, inv_t, top_k, pm, ps,
+                       seeds[s], draw_base);
+}
+
+__global__ __launch_bounds__(256) void kv_append_at_batch_kernel(const uint16_t* __restrict__ src, uint16_t* __restrict__ cache, const int* __restrict__ state,
+                                                                 int kv_heads, long cap, int d) {
+    const long b = blockIdx.y;
+    const long row = state[4 * b];
+    if (row < 0 || row >= cap) return;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)kv_heads * d) return;
+    const long h = i / d, e = i - h * d;
+    cache[((b * kv_heads + h) * cap + row) * d + e] = src[b * kv_heads * d + i];
+}
+
 __global__ __launch_bounds__(256) void kv_append_at_kernel(const uint16_t* __restrict__ src, uint16_t* __restrict__ cache, const int* __restrict__ row_p,
                                                            int kv_heads, long cap, int d) {
     const long row = *row_p;
@@ -401,6 +431,19 @@ __global__ __launch_bounds__(256) void kv_append_at_kernel(const uint16_t* __res
     if (i >= (long)kv_heads * d) return;
     const long h = i / d, e = i - h * d;
     cache[(h * cap + row) * d + e] = src[i];
+}
+
+// top_p = pm * 2^-ps exactly, pm < 2^24 (the fp32 significand as an integer); pm = 0 says top-p is off
+void split_top_p(float top_p, uint32_t& pm, int& ps) {
+    pm = 0;
+    ps = 0;
+    if (top_p < 1.0f) {
+        uint32_t u;
+        std::memcpy(&u, &top_p, 4);
+        const int e = (int)(u >> 23);
+        pm = e ? ((u & 0x7fffffu) | 0x800000u) : (u & 0x7fffffu);
+        ps = e ? 150 - e : 149;
+    }
 }
 
 }  // namespace
@@ -429,18 +472,42 @@ int osg_decode_sample(osg_ctx* ctx, const float* logits, long T, long V, long lo
         OSG_FAIL(ctx, "osg_decode_sample: temperature and 1 / temperature must be positive and finite");
     if (top_k < 0) OSG_FAIL(ctx, "osg_decode_sample: top_k must be >= 0");
     if (!(top_p > 0.0f) || !(top_p <= 1.0f)) OSG_FAIL(ctx, "osg_decode_sample: top_p must be in (0, 1]");
-    // top_p = pm * 2^-ps exactly, pm < 2^24 (the fp32 significand as an integer); pm = 0 says top-p is off
-    uint32_t pm = 0;
-    int ps = 0;
-    if (top_p < 1.0f) {
-        uint32_t u;
-        std::memcpy(&u, &top_p, 4);
-        const int e = (int)(u >> 23);
-        pm = e ? ((u & 0x7fffffu) | 0x800000u) : (u & 0x7fffffu);
-        ps = e ? 150 - e : 149;
-    }
+    uint32_t pm;
+    int ps;
+    split_top_p(top_p, pm, ps);
     hipLaunchKernelGGL(decode_sample_kernel, dim3(1), dim3(kSampleThreads), 0, ctx->compute, logits + (T - 1) * V, V, eos_id, state, input_ids, position_ids,
                        tokens, max_tokens, inv_t, top_k, pm, ps, seed, draw_base);
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int osg_decode_sample_batch(osg_ctx* ctx, const float* logits, long V, int n_seq, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
+                            int64_t* tokens, long max_tokens, float temperature, long top_k, float top_p, const unsigned long long* seeds,
+                            unsigned long long draw_base) {
+    if (V <= 0 || n_seq <= 0 || n_seq > 65535) OSG_FAIL(ctx, "osg_decode_sample_batch: invalid shape of the logits");
+    if (V > (1L << 20)) OSG_FAIL(ctx, "osg_decode_sample_batch: more than 2^20 logits per row");
+    if (!logits || !state || !input_ids || !position_ids || !tokens || !seeds) OSG_FAIL(ctx, "osg_decode_sample_batch: null operand");
+    if (max_tokens < 0 || max_tokens > 0x7fffffffL) OSG_FAIL(ctx, "osg_decode_sample_batch: invalid token budget");
+    const float inv_t = 1.0f / temperature;
+    if (!(temperature > 0.0f) || !(inv_t > 0.0f) || std::isinf(temperature) || std::isinf(inv_t))
+        OSG_FAIL(ctx, "osg_decode_sample_batch: temperature and 1 / temperature must be positive and finite");
+    if (top_k < 0) OSG_FAIL(ctx, "osg_decode_sample_batch: top_k must be >= 0");
+    if (!(top_p > 0.0f) || !(top_p <= 1.0f)) OSG_FAIL(ctx, "osg_decode_sample_batch: top_p must be in (0, 1]");
+    uint32_t pm;
+    int ps;
+    split_top_p(top_p, pm, ps);
+    hipLaunchKernelGGL(decode_sample_batch_kernel, dim3((unsigned)n_seq), dim3(kSampleThreads), 0, ctx->compute, logits, V, eos_id, state, input_ids, position_ids,
+                       tokens, max_tokens, inv_t, top_k, pm, ps, (const u64*)seeds, draw_base);
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int osg_kv_append_at_batch(osg_ctx* ctx, const void* src, void* cache, const int* state, int batch, int kv_heads, long cap, int d) {
+    if (batch <= 0 || batch > 65535 || kv_heads <= 0 || cap <= 0 || d <= 0) OSG_FAIL(ctx, "osg_kv_append_at_batch: invalid shape of the cache");
+    if (!src || !cache || !state) OSG_FAIL(ctx, "osg_kv_append_at_batch: null operand");
+    const long n = (long)kv_heads * d;
+    hipLaunchKernelGGL(kv_append_at_batch_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, ctx->compute, (const uint16_t*)src,
+                       (uint16_t*)cache, state, kv_heads, cap, d);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }

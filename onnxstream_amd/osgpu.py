@@ -30,6 +30,7 @@ EXPORTS = [
     "osg_maxpool_nhwc", "osg_convert", "osg_sampler_prepare", "osg_sampler_cfg_euler_a", "osg_sampler_cfg_multistep", "osg_sampler_prepare_rescale",
     "osg_sampler_prepare_single", "osg_sampler_euler_a_single", "osg_sampler_multistep_single", "osg_sampler_cfg_stochastic", "osg_sampler_stochastic_single",
     "osg_decode_gather", "osg_decode_blend", "osg_decode_pick", "osg_decode_sample", "osg_kv_append_at", "osg_sdpa_len",
+    "osg_decode_sample_batch", "osg_kv_append_at_batch", "osg_sdpa_len_batch", "osg_rope_batch",
     "osg_range_push", "osg_range_pop", "osg_marker_record", "osg_copy_wait_marker", "osg_timer_mark", "osg_timer_between", "osg_set_stat_sinks", "osg_group_norm_stats_nhwc", "osg_qu8_conv2d_nhwc", "osg_qu8_conv2d_nhwc_t", "osg_qu8_conv_tap_sums", "osg_qu8_gemm", "osg_qu8_lut", "osg_qu8_binary", "osg_qu8_instance_norm", "osg_qu8_instance_norm_nhwc", "osg_qu8_affine_act", "osg_qu8_norm_affine_act_nhwc", "osg_qu8_softmax_last", "osg_kdbg_read",
     "osg_tblock_tail_supported", "osg_tblock_tail", "osg_tblock_kv_pack_elems", "osg_tblock_kv_pack_jobs", "osg_tblock_pack_weight", 
 ]
@@ -134,6 +135,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.osg_sdpa_len.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, cl, cl, cl, ci, ci, ci, ci, cf]
     if hasattr(lib, "osg_decode_sample"):
         lib.osg_decode_sample.argtypes = [vp, vp, cl, cl, ctypes.c_longlong, vp, vp, vp, vp, cl, cf, cl, cf, ctypes.c_ulonglong, ctypes.c_ulonglong]
+    if hasattr(lib, "osg_decode_sample_batch"):
+        lib.osg_decode_sample_batch.argtypes = [vp, vp, cl, ci, ctypes.c_longlong, vp, vp, vp, vp, cl, cf, cl, cf, vp, ctypes.c_ulonglong]
+        lib.osg_kv_append_at_batch.argtypes = [vp, vp, vp, vp, ci, ci, cl, ci]
+        lib.osg_sdpa_len_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, cl, cl, cl, cl, ci, ci, ci, ci, cf]
+        lib.osg_rope_batch.argtypes = [vp, ci, vp, vp, vp, vp, cl, cl, cl, ci]
     lib.osg_set_stat_sinks.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, ci]
     lib.osg_group_norm_stats_nhwc.argtypes = [vp, vp, vp, vp, vp, ci, ctypes.c_long, ci, ci, cf, ci, vp]
     lib.osg_qu8_conv2d_nhwc.argtypes = [vp, vp, cf, ci, vp, cf, ci, vp, cf, ci, vp] + [ci] * 13
@@ -525,6 +531,39 @@ class Gpu:
         assert logits.dtype == np.float32 and state.dtype == np.int32 and state.size >= 4 and ids.dtype == pos.dtype == tokens.dtype == np.int64
         self._ck(self.lib.osg_decode_sample(self.ctx, logits.ptr, t, vv, int(eos_id), state.ptr, ids.ptr, pos.ptr, tokens.ptr, tokens.size, float(temperature),
                                             int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(draw_base) & (2 ** 64 - 1)))
+
+    def decode_sample_batch(self, logits: DevBuf, eos_id: int, state: DevBuf, ids: DevBuf, pos: DevBuf, tokens: DevBuf, seeds: DevBuf, temperature: float,
+                            top_k: int = 0, top_p: float = 1.0, draw_base: int = 0):
+        """osg_decode_sample_batch: logits fp32 [n_seq, V], state int32 [n_seq, 4], ids / pos int64 [n_seq], tokens int64 [n_seq, max_tokens], seeds uint64
+        [n_seq] on the device; sequence s is decode_sample over row s with seeds[s]"""
+        ns, vv = logits.shape
+        assert logits.dtype == np.float32 and state.dtype == np.int32 and state.size >= 4 * ns and ids.dtype == pos.dtype == tokens.dtype == np.int64
+        assert ids.size >= ns and pos.size >= ns and tokens.shape[0] == ns and seeds.dtype == np.uint64 and seeds.size >= ns
+        self._ck(self.lib.osg_decode_sample_batch(self.ctx, logits.ptr, vv, ns, int(eos_id), state.ptr, ids.ptr, pos.ptr, tokens.ptr, tokens.shape[1],
+                                                  float(temperature), int(top_k), float(top_p), seeds.ptr, int(draw_base) & (2 ** 64 - 1)))
+
+    def kv_append_at_batch(self, src: DevBuf, cache: DevBuf, state: DevBuf):
+        """osg_kv_append_at_batch: src f16 [B, Hkv, d] into cache [B, Hkv, CAP, d], batch b at row state[b, 0] (device int32 [B, 4]), in place"""
+        bsz, hkv, cap, d = cache.shape
+        assert src.size == bsz * hkv * d and state.dtype == np.int32 and state.size >= 4 * bsz
+        self._ck(self.lib.osg_kv_append_at_batch(self.ctx, src.ptr, cache.ptr, state.ptr, bsz, hkv, cap, d))
+
+    def sdpa_len_batch(self, q: DevBuf, k: DevBuf, v: DevBuf, mask: DevBuf, state: DevBuf, scale: float, out: Optional[DevBuf] = None):
+        """osg_sdpa_len_batch: q:[B,Hq,1,D], k,v: capacity buffers [B,Hkv,CAP,D], mask:[CAP]; batch b reads state[b, 1] keys (device int32 [B, 4])"""
+        bsz, hq, tq, d = q.shape
+        hkv, cap = k.shape[1], k.shape[2]
+        assert tq == 1 and state.dtype == np.int32 and state.size >= 4 * bsz
+        o = self._out(out, q.shape, q.dtype)
+        self._ck(self.lib.osg_sdpa_len_batch(self.ctx, _NP2DT[q.dtype], q.ptr, k.ptr, v.ptr, self._p(mask), o.ptr, state.ptr + 4, 4, cap * d, cap * d * hkv, cap,
+                                             bsz, hq, hkv, d, scale))
+        return o
+
+    def rope_batch(self, x: DevBuf, cos: DevBuf, sin: DevBuf):
+        """osg_rope_batch: x [B, H, T, d], cos / sin [B, T, d]"""
+        bsz, h, t, d = x.shape
+        y = self.empty(x.shape, x.dtype)
+        self._ck(self.lib.osg_rope_batch(self.ctx, _NP2DT[x.dtype], x.ptr, cos.ptr, sin.ptr, y.ptr, bsz, h, t, d))
+        return y
 
     def instance_norm(self, x: DevBuf, scale: Optional[DevBuf], bias: Optional[DevBuf], eps: float, out: Optional[DevBuf] = None):
         rows, L = int(np.prod(x.shape[:-1])), x.shape[-1]

@@ -222,6 +222,19 @@ def generate(m, cfg: LlamaConfig, max_new: int, eos_id: int = -1, sync_every: in
                       draw_base=draw_base)
 
 
+def generate_batch(m, cfg: LlamaConfig, n_seq: int, max_new: int, eos_id: int = -1, sync_every: int = 0, trace: bool = False, temperature: float = 1.0,
+                   top_k: int = 0, top_p: float = 1.0, seeds=None, seed: int = 0, draw_base: int = 0):
+    """n_seq sampled continuations of the prompt in one call (bindings.Model.generate_batch), after a forward_resident(..., keep_logits=True) over it.  The
+    sequences share every pass of one decode plan of batch n_seq; each has its seed, its caches and its stop.  seeds: one 64-bit integer per sequence; when
+    None, `seed` expands to seed + s modulo 2^64.  Leaves the Model's tensors as they were.  Returns (list of token arrays, stop [n_seq], list of logits
+    traces or None, device ms)."""
+    if seeds is None:
+        seeds = [(int(seed) + s) % 2 ** 64 for s in range(max(int(n_seq), 0))]
+    m.set_use_fp16_arithmetic(True)
+    return m.generate_batch(n_seq, max_new, 2 * cfg.layers, seeds, temperature, top_k=top_k, top_p=top_p, draw_base=draw_base, eos_id=eos_id,
+                            sync_every=sync_every, trace=trace)
+
+
 def configure(m, cfg: LlamaConfig, model_dir: str, sdpa: bool = False, ops_cache: bool = True, upcast: bool = False):
     """Model options of src/llm.cpp:361-377 that the C API can express (m_requires_upcast is a std::function: not settable from here).
     ops_cache=False for fp32-arithmetic runs of the reference: its ops cache does not survive a second call over fp16-stored weights."""

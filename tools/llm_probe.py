@@ -3,7 +3,10 @@ heads of 64, MLP 5632, vocabulary 32000, random weights -- prefill of 32 tokens,
 --generate: instead, the host-driven resident loop against the device loop (Model.generate) in one process, 64 tokens each (profiles/llm_generate_probe.txt).
 --generate --temperature T [--top-k K] [--top-p P] [--seed S]: the device loop greedy (twice: their difference is the noise) against the same loop sampling
 by that rule, then osg_decode_sample alone at V = 32000 and 128256; each option takes a comma-separated list, one entry per rule
-(profiles/llm_generate_sampled_probe.txt: --temperature 0.8,1 --top-k 40,0 --top-p 0.9,0.95)."""
+(profiles/llm_generate_sampled_probe.txt: --temperature 0.8,1 --top-k 40,0 --top-p 0.9,0.95).
+--generate --sequences N[,N...] [--temperature T] [--top-k K] [--top-p P] [--seed S]: the single sampled loop (Model.generate) as the baseline, then
+Model.generate_batch with each N, 64 tokens per sequence after the 32-token prefill, all in one process: ms per pass and tokens per second
+(profiles/llm_generate_batch_probe.txt: --sequences 1,2,4,8,16 --temperature 0.8 --top-k 40 --top-p 0.9)."""
 import os, sys, time, tempfile
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -133,9 +136,66 @@ def sampled_leg(rules, seed, n_new=64):
     g.close()
 
 
+def batch_leg(n_list, rule, seed, n_new=64):
+    """--generate --sequences ...: per N a cold call (the decode plan of batch N is built and captured) and two warm ones; before, between and after them the
+    single-sequence sampled loop, whose calls among themselves show the run-to-run spread.  No sequence can stop (eos -1): every call is n_new passes."""
+    rng = np.random.default_rng(0)
+    prompt = [int(t) for t in rng.integers(0, cfg.vocab, 32)]
+    t, k, p = rule
+    m = Model(b.LIB_HOST, 0, "ram+nocache")
+    m._set_option("hip_autotune", 0)
+    m._set_option("hip_resident_outputs", 1)
+    m.add_outputs_convert("logits")
+    llama.configure(m, cfg, d, sdpa=True, upcast=True)
+
+    def prefill():
+        m.clear_tensors()
+        llama.forward_resident(m, cfg, prompt, True, 0, keep_logits=True)
+        return m.hip_plans_built()
+
+    def single(name):
+        built = prefill()
+        t0 = time.perf_counter()
+        toks, stop, _, ms = llama.generate(m, cfg, n_new, temperature=t, top_k=k, top_p=p, seed=seed)
+        wall = (time.perf_counter() - t0) * 1e3
+        print(f"single sampled loop, {name}: device {ms / n_new:.3f} ms/pass, {n_new / ms * 1e3:.0f} tokens/s, wall {wall:.1f} ms the call, {len(toks)} tokens, "
+              f"plans built by the call {m.hip_plans_built() - built}", flush=True)
+        return [int(x) for x in toks]
+
+    def batch(n, name):
+        built = prefill()
+        t0 = time.perf_counter()
+        toks, stop, _, ms = llama.generate_batch(m, cfg, n, n_new, temperature=t, top_k=k, top_p=p, seed=seed)
+        wall = (time.perf_counter() - t0) * 1e3
+        total = sum(len(x) for x in toks)
+        print(f"batch loop --sequences {n}, {name}: device {ms / n_new:.3f} ms/pass, {total / ms * 1e3:.0f} tokens/s, wall {wall:.1f} ms the call, {total} tokens "
+              f"({len(set(tuple(int(v) for v in x) for x in toks))} distinct sequences), plans built by the call {m.hip_plans_built() - built}, "
+              f"{m.hip_last_kernel_count()} kernels per pass", flush=True)
+        return [[int(v) for v in x] for x in toks]
+
+    print(f"rule: T {t:g} top_k {k} top_p {p:g}, seeds {seed} + s; {n_new} passes per call after a {len(prompt)}-token prefill", flush=True)
+    single("cold (builds and captures the plan)")
+    base = single("warm, first")
+    single("warm, second")
+    for n in n_list:
+        batch(n, "cold (builds and captures the plan)")
+        got = batch(n, "warm, first")
+        batch(n, "warm, second")
+        print(f"    sequence 0 of the batch equals the single loop with its seed: {got[0] == base}", flush=True)
+        print("    " + m.hip_decode_plan_info().splitlines()[0], flush=True)
+    single("cold again (the plan of one sequence is rebuilt)")
+    single("warm, third")
+    single("warm, fourth")
+    m.close()
+
+
 if "--generate" in sys.argv:
     temps = _option("--temperature", None, float)
-    if temps is None:
+    seqs = _option("--sequences", None, int)
+    if seqs is not None:
+        rule = ((temps or [0.8])[0], _option("--top-k", 40, int)[0], _option("--top-p", 0.9, float)[0])
+        batch_leg(seqs, rule, _option("--seed", 0, int)[0])
+    elif temps is None:
         generate_leg()
     else:
         ks, ps, seed = _option("--top-k", 0, int), _option("--top-p", 1.0, float), _option("--seed", 0, int)[0]
