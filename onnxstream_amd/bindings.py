@@ -180,65 +180,13 @@ class Model:
         a = np.ascontiguousarray(data, np.float32)
         self._err(f(self._h, self._name(name), index, a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), a.size))
 
-    def hip_sampler_loop(self, sample: str, timestep: str, out: str, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, guidance: float = 7.0, clip=None) -> float:
-        """The denoising loop (CFG combine + Euler-Ancestral update) enqueued on the device, one host sync at the end.
-        x: float32 [prompts, ...] (updated IN PLACE); noise: float32 [steps, prompts, ...] or None; the per-step scalar arrays have
-        `steps` float32 entries.  The plan must have been built by a run() with 2*prompts pushes.  Returns the loop's device ms."""
+    # the three device sampler loops: one marshalling helper per family; guidance None = the *_single export, which has no such argument
+    def _sampler_loop(self, fname: str, sample: str, timestep: str, out: str, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, guidance, clip):
         import numpy as np
-        f = self._lib.model_hip_sampler_loop
+        f = getattr(self._lib, "model_" + fname)
         fp = ctypes.POINTER(ctypes.c_float)
-        f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, fp, fp, fp,
-                      ctypes.c_float, fp, ctypes.POINTER(ctypes.c_double)]
-        f.restype = ctypes.c_void_p
-        assert x.dtype == np.float32 and x.flags.c_contiguous
-        arrs = [np.ascontiguousarray(a, np.float32) for a in (c_in, c_out, t, sigma, d_sigma, sigma_up)]
-        steps = len(arrs[0])
-        if noise is not None:
-            noise = np.ascontiguousarray(noise, np.float32)
-            assert noise.size == steps * x.size
-        if clip is not None:
-            clip = np.ascontiguousarray(clip, np.float32)
-            assert clip.size == steps
-        ms = ctypes.c_double(0)
-        self._err(f(self._h, self._name(sample), self._name(timestep), self._name(out), steps, x.shape[0], x.ctypes.data_as(fp),
-                    noise.ctypes.data_as(fp) if noise is not None else None, *[a.ctypes.data_as(fp) for a in arrs], guidance,
-                    clip.ctypes.data_as(fp) if clip is not None else None, ctypes.byref(ms)))
-        return ms.value
-
-    def hip_sampler_loop_multistep(self, sample: str, timestep: str, out: str, x, sampler: int, c_in, c_out, t, sigma, order, coef, dcoef,
-                                   guidance: float = 7.0) -> float:
-        """The denoising loop with a one-evaluation multistep sampler (DPM++ 2M / 2M v2, iPNDM, iPNDM_v, iPNDM_vo, Taylor3, DDIM) on the device,
-        one host sync at the end.  sampler: the loop form of model_hip_sampler_loop_multistep (pipeline.Txt2Img.multistep_table makes it and the
-        tables); c_in, c_out, t, sigma: `steps` float32 entries; order: `steps` ints; coef: float32 [steps, 6]; dcoef: float64 [steps, 2].
-        x: float32 [prompts, ...], updated IN PLACE.  Returns the loop's device ms."""
-        import numpy as np
-        f = self._lib.model_hip_sampler_loop_multistep
-        fp, dp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
-        f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, ip,
-                      fp, ctypes.c_ulonglong, dp, ctypes.c_ulonglong, ctypes.c_float, ctypes.POINTER(ctypes.c_double)]
-        f.restype = ctypes.c_void_p
-        assert x.dtype == np.float32 and x.flags.c_contiguous
-        arrs = [np.ascontiguousarray(a, np.float32) for a in (c_in, c_out, t, sigma)]
-        steps = len(arrs[0])
-        if any(len(a) != steps for a in arrs) or len(order) != steps:
-            raise OnnxStreamError("hip_sampler_loop_multistep: c_in, c_out, t, sigma and order need one entry per step")
-        order = np.ascontiguousarray(order, np.int32)
-        coef = np.ascontiguousarray(coef, np.float32)
-        dcoef = np.ascontiguousarray(dcoef, np.float64)
-        ms = ctypes.c_double(0)
-        self._err(f(self._h, self._name(sample), self._name(timestep), self._name(out), steps, x.shape[0], int(sampler), x.ctypes.data_as(fp),
-                    *[a.ctypes.data_as(fp) for a in arrs], order.ctypes.data_as(ip), coef.ctypes.data_as(fp), coef.size, dcoef.ctypes.data_as(dp),
-                    dcoef.size, guidance, ctypes.byref(ms)))
-        return ms.value
-
-    def hip_sampler_loop_single(self, sample: str, timestep: str, out: str, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, clip=None) -> float:
-        """hip_sampler_loop for a plan built by a run() with `prompts` pushes, ONE UNet sample per prompt (SDXL Turbo, src/sd.cpp:1537-1541):
-        den = eps*c_out + x, no guidance pair.  The arguments of hip_sampler_loop without `guidance`."""
-        import numpy as np
-        f = self._lib.model_hip_sampler_loop_single
-        fp = ctypes.POINTER(ctypes.c_float)
-        f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, fp, fp, fp, fp,
-                      ctypes.POINTER(ctypes.c_double)]
+        f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, fp, fp, fp] + \
+                     ([ctypes.c_float] if guidance is not None else []) + [fp, ctypes.POINTER(ctypes.c_double)]
         f.restype = ctypes.c_void_p
         assert x.dtype == np.float32 and x.flags.c_contiguous
         arrs = [np.ascontiguousarray(a, np.float32) for a in (c_in, c_out, t, sigma, d_sigma, sigma_up)]
@@ -252,30 +200,54 @@ class Model:
         ms = ctypes.c_double(0)
         self._err(f(self._h, self._name(sample), self._name(timestep), self._name(out), steps, x.shape[0], x.ctypes.data_as(fp),
                     noise.ctypes.data_as(fp) if noise is not None else None, *[a.ctypes.data_as(fp) for a in arrs],
-                    clip.ctypes.data_as(fp) if clip is not None else None, ctypes.byref(ms)))
+                    *([guidance] if guidance is not None else []), clip.ctypes.data_as(fp) if clip is not None else None, ctypes.byref(ms)))
         return ms.value
 
-    def hip_sampler_loop_multistep_single(self, sample: str, timestep: str, out: str, x, sampler: int, c_in, c_out, t, sigma, order, coef, dcoef) -> float:
-        """hip_sampler_loop_multistep for a plan with ONE UNet sample per prompt (see hip_sampler_loop_single): the same arguments without `guidance`."""
+    def hip_sampler_loop(self, sample: str, timestep: str, out: str, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, guidance: float = 7.0, clip=None) -> float:
+        """The denoising loop (CFG combine + Euler-Ancestral update) enqueued on the device, one host sync at the end.
+        x: float32 [prompts, ...] (updated IN PLACE); noise: float32 [steps, prompts, ...] or None; the per-step scalar arrays have
+        `steps` float32 entries.  The plan must have been built by a run() with 2*prompts pushes.  Returns the loop's device ms."""
+        return self._sampler_loop("hip_sampler_loop", sample, timestep, out, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, guidance, clip)
+
+    def hip_sampler_loop_single(self, sample: str, timestep: str, out: str, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, clip=None) -> float:
+        """hip_sampler_loop for a plan built by a run() with `prompts` pushes, ONE UNet sample per prompt (SDXL Turbo, src/sd.cpp:1537-1541):
+        den = eps*c_out + x, no guidance pair.  The arguments of hip_sampler_loop without `guidance`."""
+        return self._sampler_loop("hip_sampler_loop_single", sample, timestep, out, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, None, clip)
+
+    def _sampler_loop_multistep(self, fname: str, sample: str, timestep: str, out: str, x, sampler, c_in, c_out, t, sigma, order, coef, dcoef, guidance):
         import numpy as np
-        f = self._lib.model_hip_sampler_loop_multistep_single
+        f = getattr(self._lib, "model_" + fname)
         fp, dp, ip = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
         f.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, fp, fp, fp, fp, fp, ip,
-                      fp, ctypes.c_ulonglong, dp, ctypes.c_ulonglong, ctypes.POINTER(ctypes.c_double)]
+                      fp, ctypes.c_ulonglong, dp, ctypes.c_ulonglong] + ([ctypes.c_float] if guidance is not None else []) + [ctypes.POINTER(ctypes.c_double)]
         f.restype = ctypes.c_void_p
         assert x.dtype == np.float32 and x.flags.c_contiguous
         arrs = [np.ascontiguousarray(a, np.float32) for a in (c_in, c_out, t, sigma)]
         steps = len(arrs[0])
         if any(len(a) != steps for a in arrs) or len(order) != steps:
-            raise OnnxStreamError("hip_sampler_loop_multistep_single: c_in, c_out, t, sigma and order need one entry per step")
+            raise OnnxStreamError(f"{fname}: c_in, c_out, t, sigma and order need one entry per step")
         order = np.ascontiguousarray(order, np.int32)
         coef = np.ascontiguousarray(coef, np.float32)
         dcoef = np.ascontiguousarray(dcoef, np.float64)
         ms = ctypes.c_double(0)
         self._err(f(self._h, self._name(sample), self._name(timestep), self._name(out), steps, x.shape[0], int(sampler), x.ctypes.data_as(fp),
                     *[a.ctypes.data_as(fp) for a in arrs], order.ctypes.data_as(ip), coef.ctypes.data_as(fp), coef.size, dcoef.ctypes.data_as(dp),
-                    dcoef.size, ctypes.byref(ms)))
+                    dcoef.size, *([guidance] if guidance is not None else []), ctypes.byref(ms)))
         return ms.value
+
+    def hip_sampler_loop_multistep(self, sample: str, timestep: str, out: str, x, sampler: int, c_in, c_out, t, sigma, order, coef, dcoef,
+                                   guidance: float = 7.0) -> float:
+        """The denoising loop with a one-evaluation multistep sampler (DPM++ 2M / 2M v2, iPNDM, iPNDM_v, iPNDM_vo, Taylor3, DDIM) on the device,
+        one host sync at the end.  sampler: the loop form of model_hip_sampler_loop_multistep (pipeline.Txt2Img.multistep_table makes it and the
+        tables); c_in, c_out, t, sigma: `steps` float32 entries; order: `steps` ints; coef: float32 [steps, 6]; dcoef: float64 [steps, 2].
+        x: float32 [prompts, ...], updated IN PLACE.  Returns the loop's device ms."""
+        return self._sampler_loop_multistep("hip_sampler_loop_multistep", sample, timestep, out, x, sampler, c_in, c_out, t, sigma, order, coef, dcoef,
+                                            guidance)
+
+    def hip_sampler_loop_multistep_single(self, sample: str, timestep: str, out: str, x, sampler: int, c_in, c_out, t, sigma, order, coef, dcoef) -> float:
+        """hip_sampler_loop_multistep for a plan with ONE UNet sample per prompt (see hip_sampler_loop_single): the same arguments without `guidance`."""
+        return self._sampler_loop_multistep("hip_sampler_loop_multistep_single", sample, timestep, out, x, sampler, c_in, c_out, t, sigma, order, coef,
+                                            dcoef, None)
 
     def _sampler_loop_stochastic(self, fname: str, sample: str, timestep: str, out: str, x, c_in, c_out, t, sigma, form, draws, coef, noise, guidance):
         import numpy as np

@@ -38,6 +38,56 @@ const char* dtype_name(TensorDataType t) {
     }
 }
 
+// the error convention of the char*-returning exports: run `f`; NULL on success, the exception's text (malloc'd) otherwise.  With `ms`, f returns the
+// device time that *ms (may be NULL) receives.
+template <class F>
+char* guarded(F&& f) {
+    try {
+        f();
+        return nullptr;
+    } catch (const std::exception& e) {
+        return dup_cstr(e.what());
+    }
+}
+template <class F>
+char* guarded(double* ms, F&& f) {
+    return guarded([&] {
+        const double v = f();
+        if (ms) *ms = v;
+    });
+}
+
+// the three sampler loops on the Model's plan; each pair of exports (model_hip_sampler_loop*, *_single) differs in `branches` and `guidance` alone
+char* euler_a_loop(Handle* h, int branches, float guidance, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, float* x,
+                   const float* noise, const float* c_in, const float* c_out, const float* t, const float* sigma, const float* d_sigma, const float* sigma_up,
+                   const float* clip, double* ms) {
+    return guarded(ms, [&] {
+        return Plan::on_plan_of(h->model, branches == 2 ? "Model::hip_sampler_loop" : "Model::hip_sampler_loop_single", [&](Plan& p) {
+            return p.sampler_loop(sample_name, timestep_name, out_name, steps, prompts, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, guidance, clip, branches);
+        });
+    });
+}
+char* multistep_loop(Handle* h, int branches, float guidance, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, int sampler,
+                     float* x, const float* c_in, const float* c_out, const float* t, const float* sigma, const int* order, const float* coef,
+                     unsigned long long n_coef, const double* dcoef, unsigned long long n_dcoef, double* ms) {
+    return guarded(ms, [&] {
+        return Plan::on_plan_of(h->model, branches == 2 ? "Model::hip_sampler_loop_multistep" : "Model::hip_sampler_loop_multistep_single", [&](Plan& p) {
+            return p.sampler_loop_multistep(sample_name, timestep_name, out_name, steps, prompts, sampler, x, c_in, c_out, t, sigma, order, coef, (size_t)n_coef,
+                                            dcoef, (size_t)n_dcoef, guidance, branches);
+        });
+    });
+}
+char* stochastic_loop(Handle* h, int branches, float guidance, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, float* x,
+                      const float* c_in, const float* c_out, const float* t, const float* sigma, const int* form, const int* draws, const float* coef,
+                      unsigned long long n_coef, const float* noise, double* ms) {
+    return guarded(ms, [&] {
+        return Plan::on_plan_of(h->model, branches == 2 ? "Model::hip_sampler_loop_stochastic" : "Model::hip_sampler_loop_stochastic_single", [&](Plan& p) {
+            return p.sampler_loop_stochastic(sample_name, timestep_name, out_name, steps, prompts, x, c_in, c_out, t, sigma, form, draws, coef, (size_t)n_coef,
+                                             noise, guidance, branches);
+        });
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -71,12 +121,7 @@ void model_read_string(Handle* h, char* str) {
 }
 
 char* model_read_file(Handle* h, char* fn) {
-    try {
-        h->model.read_file(fn);
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return guarded([&] { h->model.read_file(fn); });
 }
 
 char* model_get_weights_names(Handle* h) {
@@ -201,12 +246,7 @@ void model_run(Handle* h) {
 }
 
 char* model_run_2(Handle* h) {
-    try {
-        h->model.run();
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return guarded([&] { h->model.run(); });
 }
 
 void model_clear_tensors(Handle* h) { h->model.m_data.clear(); }
@@ -294,18 +334,13 @@ int model_hip_drop_tensor(Handle* h, char* name) {   // (llm.cpp's get_output mo
 }
 // bring a device-resident tensor (hip_resident_outputs) to the host; returns an error string or NULL
 char* model_hip_fetch_tensor(Handle* h, char* name) {
-    try {
-        h->model.hip_fetch_tensor(name);
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return guarded([&] { h->model.hip_fetch_tensor(name); });
 }
 // the bits of a float16 tensor of m_data (an output kept out of m_outputs_convert_set: the LLM flow's caches), which model_get_tensor cannot hand out.
 // shape: [8] (receives the dims), *rank their number; dst (may be NULL: shape only) receives dst_elems halves, which must be the tensor's element count.
 // A device-resident tensor is read where it lies and stays there.
 char* model_hip_get_tensor_f16(Handle* h, char* name, unsigned short* dst, unsigned long long dst_elems, unsigned long long* shape, int* rank) {
-    try {
+    return guarded([&] {
         for (auto& t : h->model.m_data)
             if (t.m_name == name) {
                 if (t.m_type != TensorDataType::float16) throw std::invalid_argument("Model::hip_get_tensor_f16: tensor is not float16: " + std::string(name));
@@ -313,7 +348,7 @@ char* model_hip_get_tensor_f16(Handle* h, char* name, unsigned short* dst, unsig
                 size_t n = 1;
                 for (size_t k = 0; k < t.m_shape.size(); k++) { shape[k] = t.m_shape[k]; n *= t.m_shape[k]; }
                 *rank = (int)t.m_shape.size();
-                if (!dst) return nullptr;
+                if (!dst) return;
                 if (dst_elems != n) throw std::invalid_argument("Model::get_tensor_data: mismatch between tensor shape and data size.");
                 if (t.m_hip_resident) {
                     if (t.m_hip_resident_bytes != n * 2) throw std::invalid_argument("Model::get_tensor_data: mismatch between tensor shape and data size.");
@@ -322,12 +357,10 @@ char* model_hip_get_tensor_f16(Handle* h, char* name, unsigned short* dst, unsig
                     if (t.get_vector<uint16_t>().size() != n) throw std::invalid_argument("Model::get_tensor_data: mismatch between tensor shape and data size.");
                     std::memcpy(dst, t.get_vector<uint16_t>().data(), n * 2);
                 }
-                return nullptr;
+                return;
             }
         throw std::invalid_argument("Model::hip_get_tensor_f16: tensor not found: " + std::string(name));
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    });
 }
 int model_hip_rename_tensor(Handle* h, char* from, char* to) {
     for (auto& t : h->model.m_data)
@@ -336,21 +369,11 @@ int model_hip_rename_tensor(Handle* h, char* from, char* to) {
 }
 // relaunch the captured pass n times on the resident inputs; ms_each (may be NULL) receives per-launch device times
 char* model_hip_replay(Handle* h, int n, float* ms_each) {
-    try {
-        h->model.hip_replay(n, ms_each);
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return guarded([&] { h->model.hip_replay(n, ms_each); });
 }
 // refresh sample `index` of a resident graph input (fp32, `count` elements) without running a pass
 char* model_hip_set_input(Handle* h, char* name, long long index, const float* data, unsigned long long count) {
-    try {
-        h->model.hip_set_input(name, (long)index, data, (size_t)count);
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return guarded([&] { h->model.hip_set_input(name, (long)index, data, (size_t)count); });
 }
 // the reference app's denoising loop (CFG combine + Euler-Ancestral, src/sd.cpp:1397-1559, src/samplers.h:1430-1472) enqueued on the device
 // without per-step host round trips.  x:[prompts,L] fp32 is updated in place; noise:[steps,prompts,L]; the five per-step scalar arrays
@@ -358,13 +381,7 @@ char* model_hip_set_input(Handle* h, char* name, long long index, const float* d
 char* model_hip_sampler_loop(Handle* h, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, float* x, const float* noise,
                              const float* c_in, const float* c_out, const float* t, const float* sigma, const float* d_sigma, const float* sigma_up, float guidance, const float* clip,
                              double* ms) {
-    try {
-        const double v = h->model.hip_sampler_loop(sample_name, timestep_name, out_name, steps, prompts, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, guidance, clip);
-        if (ms) *ms = v;
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return euler_a_loop(h, 2, guidance, sample_name, timestep_name, out_name, steps, prompts, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, clip, ms);
 }
 // the same loop with a one-evaluation multistep sampler of src/samplers.h.  sampler: 0 = dpm++2m / dpm++2mv2, 1 = ipndm, 2 = ipndm_v, 3 = ipndm_vo,
 // 4 = taylor3, 5 = ddim; order: [steps] int (0 = the sampler's first-step form; <= step index; sampler 0 also takes 2 = the plain Euler step of the
@@ -373,40 +390,19 @@ char* model_hip_sampler_loop(Handle* h, char* sample_name, char* timestep_name, 
 char* model_hip_sampler_loop_multistep(Handle* h, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, int sampler, float* x,
                                        const float* c_in, const float* c_out, const float* t, const float* sigma, const int* order, const float* coef,
                                        unsigned long long n_coef, const double* dcoef, unsigned long long n_dcoef, float guidance, double* ms) {
-    try {
-        const double v = Plan::run_sampler_loop_multistep(h->model, sample_name, timestep_name, out_name, steps, prompts, sampler, x, c_in, c_out, t,
-                                                           sigma, order, coef, (size_t)n_coef, dcoef, (size_t)n_dcoef, guidance);
-        if (ms) *ms = v;
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return multistep_loop(h, 2, guidance, sample_name, timestep_name, out_name, steps, prompts, sampler, x, c_in, c_out, t, sigma, order, coef, n_coef, dcoef, n_dcoef, ms);
 }
 // the two loops above for a plan that holds ONE sample per prompt (SDXL Turbo: CFGDenoiser_CompVisDenoiser returns the cond branch alone, src/sd.cpp:1537-1541):
 // den = eps*c_out + x, no guidance.  The arguments of their siblings without `guidance`; the plan's batch must be `prompts`.
 char* model_hip_sampler_loop_single(Handle* h, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, float* x, const float* noise,
                                     const float* c_in, const float* c_out, const float* t, const float* sigma, const float* d_sigma, const float* sigma_up,
                                     const float* clip, double* ms) {
-    try {
-        const double v = Plan::run_sampler_loop(h->model, sample_name, timestep_name, out_name, steps, prompts, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up,
-                                                clip, 1);
-        if (ms) *ms = v;
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return euler_a_loop(h, 1, 0.f, sample_name, timestep_name, out_name, steps, prompts, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, clip, ms);
 }
 char* model_hip_sampler_loop_multistep_single(Handle* h, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, int sampler, float* x,
                                               const float* c_in, const float* c_out, const float* t, const float* sigma, const int* order, const float* coef,
                                               unsigned long long n_coef, const double* dcoef, unsigned long long n_dcoef, double* ms) {
-    try {
-        const double v = Plan::run_sampler_loop_multistep(h->model, sample_name, timestep_name, out_name, steps, prompts, sampler, x, c_in, c_out, t, sigma,
-                                                           order, coef, (size_t)n_coef, dcoef, (size_t)n_dcoef, 0.f, 1);
-        if (ms) *ms = v;
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return multistep_loop(h, 1, 0.f, sample_name, timestep_name, out_name, steps, prompts, sampler, x, c_in, c_out, t, sigma, order, coef, n_coef, dcoef, n_dcoef, ms);
 }
 // the same loop with a one-evaluation sampler that adds fresh noise per step (ddpm, ddpm_a, ddim_a, tcd, tcd_a, lcm, dpm++3msde, dpm++3msde_a;
 // src/samplers.h:1039-1223, :1406-1428, :412-541).  form: [steps] int, the osg_stochastic_form (include/osgpu.h) of each step; draws: [steps] int,
@@ -415,26 +411,12 @@ char* model_hip_sampler_loop_multistep_single(Handle* h, char* sample_name, char
 char* model_hip_sampler_loop_stochastic(Handle* h, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, float* x,
                                         const float* c_in, const float* c_out, const float* t, const float* sigma, const int* form, const int* draws,
                                         const float* coef, unsigned long long n_coef, const float* noise, float guidance, double* ms) {
-    try {
-        const double v = Plan::run_sampler_loop_stochastic(h->model, sample_name, timestep_name, out_name, steps, prompts, x, c_in, c_out, t, sigma, form,
-                                                            draws, coef, (size_t)n_coef, noise, guidance);
-        if (ms) *ms = v;
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return stochastic_loop(h, 2, guidance, sample_name, timestep_name, out_name, steps, prompts, x, c_in, c_out, t, sigma, form, draws, coef, n_coef, noise, ms);
 }
 char* model_hip_sampler_loop_stochastic_single(Handle* h, char* sample_name, char* timestep_name, char* out_name, int steps, int prompts, float* x,
                                                const float* c_in, const float* c_out, const float* t, const float* sigma, const int* form,
                                                const int* draws, const float* coef, unsigned long long n_coef, const float* noise, double* ms) {
-    try {
-        const double v = Plan::run_sampler_loop_stochastic(h->model, sample_name, timestep_name, out_name, steps, prompts, x, c_in, c_out, t, sigma, form,
-                                                            draws, coef, (size_t)n_coef, noise, 0.f, 1);
-        if (ms) *ms = v;
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return stochastic_loop(h, 1, 0.f, sample_name, timestep_name, out_name, steps, prompts, x, c_in, c_out, t, sigma, form, draws, coef, n_coef, noise, ms);
 }
 // latents -> image on the device (decoder_solver / sd_tiled_decoder / sdxl_decoder around the VAE pass, src/sd.cpp:1174-1346, :2357-2516, and Mat::to_pixels
 // :340-364): latents [images, 4, h, w] fp32 host -> image [images, 3, u*h, u*w] fp32 and / or pixels [images, u*h, u*w, 3] uint8, either may be NULL (not
@@ -443,13 +425,11 @@ char* model_hip_sampler_loop_stochastic_single(Handle* h, char* sample_name, cha
 // another size than the decode writes is refused, since u is the plan's to know.  *ms (may be NULL) receives the device time from gather to blend.
 char* model_hip_decode(Handle* h, char* in_name, char* out_name, int images, int lat_h, int lat_w, float factor, const float* latents, float* image,
                        unsigned long long image_elems, unsigned char* pixels, unsigned long long pixels_elems, double* ms) {
-    try {
-        const double v = Plan::run_decode(h->model, in_name, out_name, images, lat_h, lat_w, factor, latents, image, (size_t)image_elems, pixels, (size_t)pixels_elems);
-        if (ms) *ms = v;
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return guarded(ms, [&] {
+        return Plan::on_plan_of(h->model, "Model::hip_decode", [&](Plan& p) {
+            return p.decode_tiles(in_name, out_name, images, lat_h, lat_w, factor, latents, image, (size_t)image_elems, pixels, (size_t)pixels_elems);
+        });
+    });
 }
 // the reference LLM app's greedy token loop (src/llm.cpp:472-496) on the device: one call, one plan, one synchronisation for up to max_new tokens.  The Model is
 // configured as the app configures it (dynamic shapes, fp16 arithmetic, m_use_scaled_dp_attn_op, `logits_name` the only converted output, the caches extra
@@ -472,17 +452,13 @@ char* model_hip_decode(Handle* h, char* in_name, char* out_name, int images, int
 char* model_hip_generate(Handle* h, const char* ids_name, const char* pos_name, const char* mask_name, const char* logits_name, const char* cache_in_prefix,
                          const char* cache_out_prefix, int n_caches, int max_new, long long eos_id, int sync_every, long long* tokens, int* n_tokens, int* stop,
                          float* logits_trace, double* ms) {
-    try {
+    return guarded(ms, [&] {
         Plan::DecodeSpec spec;
         spec.ids = ids_name; spec.pos = pos_name; spec.mask = mask_name; spec.logits = logits_name;
         spec.cache_in = cache_in_prefix; spec.cache_out = cache_out_prefix; spec.n_caches = n_caches;
         static_assert(sizeof(long long) == sizeof(int64_t), "tokens are int64");
-        const double v = Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, Plan::SampleRule());
-        if (ms) *ms = v;
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+        return Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, Plan::SampleRule());
+    });
 }
 // model_hip_generate with a sampling rule in the argmax's place (osg_decode_sample, include/osgpu.h states the rule in full): temperature > 0 divides the
 // logits, top_k > 0 keeps the k largest, top_p < 1 the shortest prefix that holds that share of the mass, and the token is drawn with Philox4x32-10 keyed by
@@ -494,18 +470,14 @@ char* model_hip_generate_sampled(Handle* h, const char* ids_name, const char* po
                                  const char* cache_out_prefix, int n_caches, int max_new, long long eos_id, int sync_every, long long* tokens, int* n_tokens,
                                  int* stop, float* logits_trace, double* ms, float temperature, long long top_k, float top_p, unsigned long long seed,
                                  unsigned long long draw_base) {
-    try {
+    return guarded(ms, [&] {
         Plan::DecodeSpec spec;
         spec.ids = ids_name; spec.pos = pos_name; spec.mask = mask_name; spec.logits = logits_name;
         spec.cache_in = cache_in_prefix; spec.cache_out = cache_out_prefix; spec.n_caches = n_caches;
         Plan::SampleRule rule;
         rule.temperature = temperature; rule.top_k = (long)top_k; rule.top_p = top_p; rule.seed = seed; rule.draw_base = draw_base;
-        const double v = Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, rule);
-        if (ms) *ms = v;
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+        return Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, rule);
+    });
 }
 // n_seq sampled continuations of ONE prompt in one call: after the same batch-1 run() over the prompt, sequence s is exactly the loop of
 // model_hip_generate_sampled with seed = seeds[s] (draw index draw_base + n_tokens[s]), on copies of the prompt's caches of its own and with a state of its
@@ -520,18 +492,14 @@ char* model_hip_generate_batch(Handle* h, const char* ids_name, const char* pos_
                                const char* cache_out_prefix, int n_caches, int n_seq, int max_new, long long eos_id, int sync_every, long long* tokens,
                                int* n_tokens, int* stop, float* logits_trace, double* ms, float temperature, long long top_k, float top_p,
                                const unsigned long long* seeds, unsigned long long draw_base) {
-    try {
+    return guarded(ms, [&] {
         Plan::DecodeSpec spec;
         spec.ids = ids_name; spec.pos = pos_name; spec.mask = mask_name; spec.logits = logits_name;
         spec.cache_in = cache_in_prefix; spec.cache_out = cache_out_prefix; spec.n_caches = n_caches;
         Plan::SampleRule rule;
         rule.temperature = temperature; rule.top_k = (long)top_k; rule.top_p = top_p; rule.draw_base = draw_base;
-        const double v = Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, rule, n_seq, seeds, true);
-        if (ms) *ms = v;
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+        return Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, rule, n_seq, seeds, true);
+    });
 }
 // steps of the decode plan model_hip_generate built, as model_hip_plan_info gives them, after a first line "decode capacity <CAP>" (a plan of n_seq > 1
 // sequences: "decode capacity <CAP> sequences <n_seq>"); "ERROR: ..." on error
@@ -562,20 +530,10 @@ char* model_hip_profile(Handle* h, int reps) {
 // range_data.txt (per-op output ranges of a calibration run; src/sd.cpp:1214 reads it before the uint8 VAE decode, :1241 writes it after
 // --decoder-calibrate): Model::read_range_data / write_range_data have no export in the reference's C API (the app links the class)
 char* model_hip_read_range_data(Handle* h, const char* filename) {
-    try {
-        h->model.read_range_data(filename);
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return guarded([&] { h->model.read_range_data(filename); });
 }
 char* model_hip_write_range_data(Handle* h, const char* filename) {
-    try {
-        h->model.write_range_data(filename);
-        return nullptr;
-    } catch (const std::exception& e) {
-        return dup_cstr(e.what());
-    }
+    return guarded([&] { h->model.write_range_data(filename); });
 }
 
 }  // extern "C"

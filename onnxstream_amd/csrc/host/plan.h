@@ -186,13 +186,19 @@ struct Plan {
     void execute(const std::function<void()>& while_device_runs = nullptr);
     // relaunch the captured pass `n` times on the inputs already resident in HBM; per-launch device ms (HIP events)
     void replay(int n, float* ms_each);
-    // the reference app's denoising loop with the CFG combine and the Euler-Ancestral update on the device: `steps`
-    // passes enqueued back to back, one host sync at the end.  The plan's batch must be 2*prompts (push 2p = cond, 2p+1 = uncond of
-    // prompt p) and every other input (context, ...) must already be resident from an earlier run().  Per-step scalars come from the
-    // caller (who owns the schedule): c_in, c_out, t, sigma = sigma_i, d_sigma = sigma_down - sigma_i, sigma_up, clip (NULL or per-step clamp of the new latents, 0 = none).  x: [prompts, L] fp32 host, updated
-    // in place; noise: [steps, prompts, L] fp32 host.  Returns the device time of the whole loop in ms.
     // overwrite sample `index` of a graph input in its device staging (what run() does for every pushed tensor) without running a pass
     void set_input(const std::string& name, long index, const float* data, size_t count);
+    // ---- the device sampler loops ----
+    // branches (all three loops): UNet samples per prompt in the plan's batch.  2 = the cond / uncond pair with the CFG combine: the plan's batch must be
+    // 2*prompts (push 2p = cond, 2p+1 = uncond of prompt p).  1 = one sample per prompt and den = eps*c_out + x, what CFGDenoiser_CompVisDenoiser returns
+    // in Turbo mode (src/sd.cpp:1537-1541): the plan's batch must be `prompts`, guidance is unused and the osg_sampler_*_single kernels run (the
+    // model_hip_sampler_loop*_single exports).
+    //
+    // the reference app's denoising loop with the CFG combine and the Euler-Ancestral update on the device: `steps` passes enqueued
+    // back to back, one host sync at the end.  Every other input (context, ...) must already be resident from an earlier run().  Per-step scalars come
+    // from the caller (who owns the schedule): c_in, c_out, t, sigma = sigma_i, d_sigma = sigma_down - sigma_i, sigma_up, clip (NULL or per-step clamp of
+    // the new latents, 0 = none).  x: [prompts, L] fp32 host, updated in place; noise: [steps, prompts, L] fp32 host.  Returns the device time of the
+    // whole loop in ms.
     double sampler_loop(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps, int prompts,
                         float* x, const float* noise, const float* c_in, const float* c_out, const float* t, const float* sigma, const float* d_sigma,
                         const float* sigma_up, float guidance, const float* clip, int branches = 2);
@@ -200,20 +206,11 @@ struct Plan {
     // per step a prepare launch (DDIM: with its in-place prescale of x), the pass, and one osg_sampler_cfg_multistep launch whose form follows
     // from `sampler` (OSG_LOOP_* of exports.cpp) and order[i].  coef: [steps, 6] float (k0..k4 of the form, then DDIM's prescale factor),
     // dcoef: [steps, 2] double (DDIM's da, db); n_coef / n_dcoef are their lengths.  The history ring [H, prompts, L] is allocated once and
-    // reused; order[i] <= i is required, so a call never reads an entry an earlier image left behind.
+    // reused; order[i] <= i is required, so a call never reads an entry an earlier image left behind.  Order 2 of sampler 0 is the Euler step of the
+    // reference's SDXL last-step rule (src/sd.cpp:1705-1719); it reads no history and is legal at any step.
     double sampler_loop_multistep(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps, int prompts,
                                   int sampler, float* x, const float* c_in, const float* c_out, const float* t, const float* sigma, const int* order,
                                   const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef, float guidance, int branches = 2);
-    // branches (both loops): UNet samples per prompt in the plan's batch.  2 = the cond / uncond pair with the CFG combine; 1 = one sample per prompt and
-    // den = eps*c_out + x, what CFGDenoiser_CompVisDenoiser returns in Turbo mode (src/sd.cpp:1537-1541): the plan's batch must be `prompts`, guidance is
-    // unused and the osg_sampler_*_single kernels run (model_hip_sampler_loop_single / model_hip_sampler_loop_multistep_single).  Order 2 of sampler 0 is
-    // the Euler step of the reference's SDXL last-step rule (src/sd.cpp:1705-1719); it reads no history and is legal at any step.
-    // the same on Model m's plan, recording its last-pass time (model_hip_sampler_loop_multistep).  A static member of Plan, Model's friend, so that
-    // onnxstream.h -- the header the reference application is compiled against for the drop-in link (oracle/Makefile) -- stays as it is.
-    static double run_sampler_loop_multistep(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name,
-                                             int n_steps, int prompts, int sampler, float* x, const float* c_in, const float* c_out, const float* t,
-                                             const float* sigma, const int* order, const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef,
-                                             float guidance, int branches = 2);
     // the same loop with one of the one-evaluation samplers that add fresh noise per step (DDPM(-a), DDIM-a, TCD(-a), LCM, DPM++ 3M SDE(-a);
     // src/samplers.h:1039-1223, :1406-1428, :412-541): per step a prepare launch (with the in-place prescale of x where coef[i][9] != 1, prescale_sample
     // :38-60), the pass, and one osg_sampler_cfg_stochastic / osg_sampler_stochastic_single launch of form[i] (osg_stochastic_form).  coef: [steps, 10]
@@ -223,13 +220,6 @@ struct Plan {
     double sampler_loop_stochastic(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps, int prompts,
                                    float* x, const float* c_in, const float* c_out, const float* t, const float* sigma, const int* form, const int* draws,
                                    const float* coef, size_t n_coef, const float* noise, float guidance, int branches = 2);
-    static double run_sampler_loop_stochastic(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name,
-                                              int n_steps, int prompts, float* x, const float* c_in, const float* c_out, const float* t, const float* sigma,
-                                              const int* form, const int* draws, const float* coef, size_t n_coef, const float* noise, float guidance,
-                                              int branches = 2);
-    static double run_sampler_loop(Model& m,const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
-                                   int prompts, float* x, const float* noise, const float* c_in, const float* c_out, const float* t, const float* sigma,
-                                   const float* d_sigma, const float* sigma_up, const float* clip, int branches);
     // latents -> image without leaving the device (the VAE decoder plan): upload the latents [images, 4, H, W], osg_decode_gather cuts and scales the
     // tiles into the input staging, the pass (captured, or eager while no graph exists), osg_decode_blend folds the tiles and makes the fp32 image
     // [images, 3, u*H, u*W] and / or the packed uint8 image [images, u*H, u*W, 3]; only the one(s) asked for (non-NULL) come back.  Tile size t and
@@ -237,9 +227,16 @@ struct Plan {
     // image_elems / pixels_elems: what the caller's buffers hold; a non-NULL buffer of another size than the decode writes is refused (the caller cannot know u).
     double decode_tiles(const std::string& in_name, const std::string& out_name, int images, int H, int W, float factor, const float* latents, float* image,
                         size_t image_elems, uint8_t* pixels, size_t pixels_elems);
-    // the same on Model m's plan (model_hip_decode); a static member for the reason given at run_sampler_loop_multistep
-    static double run_decode(Model& m, const std::string& in_name, const std::string& out_name, int images, int H, int W, float factor, const float* latents,
-                             float* image, size_t image_elems, uint8_t* pixels, size_t pixels_elems);
+    // run(plan) on Model m's plan, recording its last-pass time in the Model; `fn` is the "Model::hip_..." name for the text thrown when there is no plan.
+    // The one way from a Model to its plan for the exports (the sampler loops, model_hip_decode).  A static member of Plan, Model's friend, so that
+    // onnxstream.h -- the header the reference application is compiled against for the drop-in link (oracle/Makefile) -- stays as it is.
+    template <class Run>
+    static double on_plan_of(Model& m, const char* fn, Run&& run) {
+        if (!m.m_plan) throw std::runtime_error(std::string(fn) + ": no plan (call run() first).");
+        const double ms = run(*m.m_plan);
+        m.m_last_ms = m.m_plan->last_ms();
+        return ms;
+    }
     // eager pass with HIP events around every step, `reps` times; "ms<TAB>flops<TAB>bytes<TAB>what" per line (ms = mean)
     std::string profile(int reps);
     // plan introspection for the CPU tests of the host logic (tests/test_planner_cpu.py): one line per step
@@ -323,11 +320,17 @@ struct Plan {
     void* samp_noise = nullptr;
     void* samp_hist = nullptr;    // sampler_loop_multistep, sampler_loop_stochastic: history ring [H, prompts, L], device fp32
     size_t samp_x_bytes = 0, samp_noise_bytes = 0, samp_hist_bytes = 0;
-    // the prologue the sampler loops share (plan_run.cpp): state and batch checks, the tensors a loop reads and writes, growing a state buffer
+    // what the sampler loops share (plan_run.cpp): state and batch checks, the tensors a loop reads and writes, and the frame around the per-step launches
     struct SamplerIO { const In* in_s = nullptr; const In* in_t = nullptr; const Out* out = nullptr; long L = 0, TL = 0; };
+    struct SamplerPrescale { bool rescale; float x_scale; };
     void sampler_check_state(const std::string& fn, int prompts, int branches) const;
     SamplerIO sampler_io(const std::string& fn, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name) const;
-    void sampler_grow(void*& p, size_t& have, size_t need);
+    template <class Prescale, class Update>
+    double sampler_frame(const std::string& fn, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
+                         int prompts, int branches, float* x, const float* c_in, const float* t, int H, const float* noise, Prescale&& prescale,
+                         Update&& update);
+    // a grow-only device buffer: (p, have) is reallocated when it holds fewer than `need` bytes; the contents are not kept
+    void grow_buffer(void*& p, size_t& have, size_t need);
     void* dec_lat = nullptr;      // decode_tiles state: latents [images, 4, H, W] fp32, image [images, 3, uH, uW] fp32, pixels [images, uH, uW, 3] uint8
     void* dec_img = nullptr;
     void* dec_pix = nullptr;
@@ -349,7 +352,7 @@ struct Plan {
     size_t dec_tokens_bytes = 0, dec_trace_bytes = 0, dec_seeds_bytes = 0;
     int cache_index(const std::string& name, const std::string& prefix) const;   // i of "<prefix><i>", i < n_caches; -1 otherwise
     // the reference app's token loop (src/llm.cpp:472-496) on the device: see model_hip_generate (exports.cpp) for the contract.  A static member of Plan
-    // for the reason given at run_sampler_loop_multistep; the decode plan itself is kept in the Model's ConstPool.
+    // for the reason given at on_plan_of; the decode plan itself is kept in the Model's ConstPool.
     // how a token is taken from the logits: default-constructed = greedy, the app's argmax (osg_decode_pick); temperature > 0 = the sampling rule of
     // include/osgpu.h (osg_decode_sample).  Sampling is outside the decode plan: the plan, its capacity, its capture and its text are the same either way.
     struct SampleRule { float temperature = 0.0f; long top_k = 0; float top_p = 1.0f; unsigned long long seed = 0, draw_base = 0; };

@@ -474,8 +474,8 @@ void Plan::set_input(const std::string& name, long index, const float* data, siz
     throw std::invalid_argument("Model::get_tensor_data: input tensor not found: " + name);
 }
 
-// what both sampler loops check (sampler_check_state) and look up (sampler_io) before they enqueue anything; `fn` is the "Model::hip_sampler_loop...: " prefix of the caller's error texts.
-// branches: UNet samples per prompt in the plan's batch, 2 = the cond / uncond pair, 1 = Turbo's single sample (the *_single entry points).
+// what the sampler loops check (sampler_check_state) and look up (sampler_io) before they enqueue anything; `fn` is the "Model::hip_sampler_loop...: " prefix
+// of the caller's error texts.  branches: see plan.h.
 void Plan::sampler_check_state(const std::string& fn, int prompts, int branches) const {
     if (runs < 1) throw std::runtime_error(fn + "run() once first (the context inputs must be resident).");
     if (stream_weights) throw std::runtime_error(fn + "not available in streamed-weights mode.");
@@ -504,7 +504,7 @@ Plan::SamplerIO Plan::sampler_io(const std::string& fn, const std::string& sampl
     return io;
 }
 
-void Plan::sampler_grow(void*& p, size_t& have, size_t need) {
+void Plan::grow_buffer(void*& p, size_t& have, size_t need) {
     if (have >= need) return;
     if (p) be.check(be.api.osg_free(be.ctx, p), "osg_free");
     p = nullptr;
@@ -513,36 +513,43 @@ void Plan::sampler_grow(void*& p, size_t& have, size_t need) {
     have = need;
 }
 
-double Plan::sampler_loop(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps, int prompts,
-                          float* x, const float* noise, const float* c_in, const float* c_out, const float* t, const float* sigma, const float* d_sigma,
-                          const float* sigma_up, float guidance, const float* clip, int branches) {
-    const bool pair = branches == 2;
-    const std::string fn = pair ? "Model::hip_sampler_loop: " : "Model::hip_sampler_loop_single: ";
-    sampler_check_state(fn, prompts, branches);
+// The frame the three sampler loops share: everything between a loop's own table checks and its return.  H: depth of the history ring the loop needs
+// (0: none); noise: [steps, prompts, L] host, uploaded when non-NULL.  Per step one prepare launch, the pass, one update launch:
+//   prescale(i) -> {rescale, x_scale}: the pair launches osg_sampler_prepare_rescale with x_scale where `rescale` and osg_sampler_prepare otherwise; the
+//       single form hands x_scale to osg_sampler_prepare_single.
+//   update(i, x, eps, nz, L, slot): the loop's update launch.  nz: row i of the uploaded noise, NULL when none was uploaded.  slot(k): history entry k of
+//       step i (k = 0: written now, k >= 1: written k steps ago), which lives in ring slot (i - k) mod H -- the reference's shift of
+//       sampler_history_buffer (src/samplers.h:422, :695 and alike) becomes a rotation of the pointers; NULL without a ring.
+template <class Prescale, class Update>
+double Plan::sampler_frame(const std::string& fn, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name,
+                           int n_steps, int prompts, int branches, float* x, const float* c_in, const float* t, int H, const float* noise,
+                           Prescale&& prescale, Update&& update) {
     FlightGuard flight(in_flight);
     const SamplerIO io = sampler_io(fn, sample_name, timestep_name, out_name);
     const long L = io.L;
     float *sample = (float*)ptr(io.in_s->staging), *tstep = (float*)ptr(io.in_t->staging);
     const float* eps = (const float*)ptr(io.out->f32val);
-    const size_t xb = (size_t)prompts * L * sizeof(float), nb = (size_t)n_steps * xb;
-    sampler_grow(samp_x, samp_x_bytes, xb);
-    if (noise) sampler_grow(samp_noise, samp_noise_bytes, nb);
+    const size_t row = (size_t)prompts * L, xb = row * sizeof(float), nb = (size_t)n_steps * xb;
+    grow_buffer(samp_x, samp_x_bytes, xb);
+    if (noise) grow_buffer(samp_noise, samp_noise_bytes, nb);
+    if (H) grow_buffer(samp_hist, samp_hist_bytes, (size_t)H * xb);
     be.check(be.api.osg_upload(be.ctx, samp_x, x, xb), "osg_upload");
     if (noise) be.check(be.api.osg_upload(be.ctx, samp_noise, noise, nb), "osg_upload");
+    float* const sx = (float*)samp_x;
     be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");
     for (int i = 0; i < n_steps; i++) {
-        if (pair) be.check(be.api.osg_sampler_prepare(be.ctx, (const float*)samp_x, sample, tstep, prompts, L, c_in[i], t[i], io.TL), "osg_sampler_prepare");
-        else be.check(be.api.osg_sampler_prepare_single(be.ctx, (float*)samp_x, sample, tstep, prompts, L, 1.f, c_in[i], t[i], io.TL), "osg_sampler_prepare_single");
+        const SamplerPrescale ps = prescale(i);
+        if (branches != 2)
+            be.check(be.api.osg_sampler_prepare_single(be.ctx, sx, sample, tstep, prompts, L, ps.x_scale, c_in[i], t[i], io.TL), "osg_sampler_prepare_single");
+        else if (ps.rescale)
+            be.check(be.api.osg_sampler_prepare_rescale(be.ctx, sx, sample, tstep, prompts, L, ps.x_scale, c_in[i], t[i], io.TL), "osg_sampler_prepare_rescale");
+        else
+            be.check(be.api.osg_sampler_prepare(be.ctx, sx, sample, tstep, prompts, L, c_in[i], t[i], io.TL), "osg_sampler_prepare");
         if (graph) be.check(be.api.osg_graph_launch(be.ctx, graph), "osg_graph_launch");
         else run_steps();
-        const float* nz = noise ? (const float*)samp_noise + (size_t)i * prompts * L : nullptr;
-        const float cl = clip ? clip[i] : 0.f;
-        if (pair)
-            be.check(be.api.osg_sampler_cfg_euler_a(be.ctx, (float*)samp_x, eps, nz, prompts, L, c_out[i], guidance, sigma[i], d_sigma[i], sigma_up[i], cl),
-                     "osg_sampler_cfg_euler_a");
-        else
-            be.check(be.api.osg_sampler_euler_a_single(be.ctx, (float*)samp_x, eps, nz, prompts, L, c_out[i], sigma[i], d_sigma[i], sigma_up[i], cl),
-                     "osg_sampler_euler_a_single");
+        const float* nz = noise ? (const float*)samp_noise + (size_t)i * row : nullptr;
+        auto slot = [&](int k) -> float* { return H ? (float*)samp_hist + (size_t)(((i - k) % H + H) % H) * row : nullptr; };
+        update(i, sx, eps, nz, L, slot);
     }
     float ms = 0;
     be.check(be.api.osg_timer_stop(be.ctx, &ms), "osg_timer_stop");
@@ -550,6 +557,26 @@ double Plan::sampler_loop(const std::string& sample_name, const std::string& tim
     runs += n_steps;
     m_last_ms = n_steps > 0 ? ms / n_steps : 0;
     return ms;
+}
+
+double Plan::sampler_loop(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps, int prompts,
+                          float* x, const float* noise, const float* c_in, const float* c_out, const float* t, const float* sigma, const float* d_sigma,
+                          const float* sigma_up, float guidance, const float* clip, int branches) {
+    const bool pair = branches == 2;
+    const std::string fn = pair ? "Model::hip_sampler_loop: " : "Model::hip_sampler_loop_single: ";
+    sampler_check_state(fn, prompts, branches);
+    return sampler_frame(
+        fn, sample_name, timestep_name, out_name, n_steps, prompts, branches, x, c_in, t, 0, noise,
+        [](int) { return SamplerPrescale{false, 1.f}; },   // Euler-A never rescales x
+        [&](int i, float* sx, const float* eps, const float* nz, long L, auto&&) {
+            const float cl = clip ? clip[i] : 0.f;
+            if (pair)
+                be.check(be.api.osg_sampler_cfg_euler_a(be.ctx, sx, eps, nz, prompts, L, c_out[i], guidance, sigma[i], d_sigma[i], sigma_up[i], cl),
+                         "osg_sampler_cfg_euler_a");
+            else
+                be.check(be.api.osg_sampler_euler_a_single(be.ctx, sx, eps, nz, prompts, L, c_out[i], sigma[i], d_sigma[i], sigma_up[i], cl),
+                         "osg_sampler_euler_a_single");
+        });
 }
 
 double Plan::sampler_loop_multistep(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
@@ -579,50 +606,24 @@ double Plan::sampler_loop_multistep(const std::string& sample_name, const std::s
     for (int i = 0; i < n_steps; i++)
         if (order[i] < 0 || order[i] > 3 || forms[sampler][order[i]] < 0 || reads(order[i]) > i)
             throw std::invalid_argument(fn + "order " + std::to_string(order[i]) + " at step " + std::to_string(i) + " is not available.");
-    FlightGuard flight(in_flight);
-    const SamplerIO io = sampler_io(fn, sample_name, timestep_name, out_name);
-    const long L = io.L;
-    float *sample = (float*)ptr(io.in_s->staging), *tstep = (float*)ptr(io.in_t->staging);
-    const float* eps = (const float*)ptr(io.out->f32val);
-    const int H = depth[sampler];
-    const size_t xb = (size_t)prompts * L * sizeof(float), hb = (size_t)H * xb;
-    sampler_grow(samp_x, samp_x_bytes, xb);
-    if (H) sampler_grow(samp_hist, samp_hist_bytes, hb);
-    be.check(be.api.osg_upload(be.ctx, samp_x, x, xb), "osg_upload");
-    // history entry k of step i (k = 0: written now, k >= 1: written k steps ago) lives in ring slot (i - k) mod H: the reference's shift of
-    // sampler_history_buffer (src/samplers.h:695 and alike) becomes a rotation of the pointers
-    auto slot = [&](int i, int k) -> float* { return H ? (float*)samp_hist + (size_t)(((i - k) % H + H) % H) * prompts * L : nullptr; };
-    be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");
-    for (int i = 0; i < n_steps; i++) {
-        const float* k = coef + (size_t)i * 6;
-        if (!pair)
-            be.check(be.api.osg_sampler_prepare_single(be.ctx, (float*)samp_x, sample, tstep, prompts, L, sampler == 5 ? k[5] : 1.f, c_in[i], t[i], io.TL),
-                     "osg_sampler_prepare_single");
-        else if (sampler == 5)
-            be.check(be.api.osg_sampler_prepare_rescale(be.ctx, (float*)samp_x, sample, tstep, prompts, L, k[5], c_in[i], t[i], io.TL),
-                     "osg_sampler_prepare_rescale");
-        else
-            be.check(be.api.osg_sampler_prepare(be.ctx, (const float*)samp_x, sample, tstep, prompts, L, c_in[i], t[i], io.TL), "osg_sampler_prepare");
-        if (graph) be.check(be.api.osg_graph_launch(be.ctx, graph), "osg_graph_launch");
-        else run_steps();
-        const int form = forms[sampler][order[i]], r = reads(order[i]);
-        float* h0 = slot(i, 0);
-        const float *h1 = r >= 1 ? slot(i, 1) : nullptr, *h2 = r >= 2 ? slot(i, 2) : nullptr, *h3 = r >= 3 ? slot(i, 3) : nullptr;
-        if (pair)
-            be.check(be.api.osg_sampler_cfg_multistep(be.ctx, form, (float*)samp_x, eps, h0, h1, h2, h3, prompts, L, c_out[i], guidance, sigma[i], k[0], k[1],
-                                                      k[2], k[3], k[4], dcoef[2 * i], dcoef[2 * i + 1]),
-                     "osg_sampler_cfg_multistep");
-        else
-            be.check(be.api.osg_sampler_multistep_single(be.ctx, form, (float*)samp_x, eps, h0, h1, h2, h3, prompts, L, c_out[i], sigma[i], k[0], k[1], k[2],
-                                                         k[3], k[4], dcoef[2 * i], dcoef[2 * i + 1]),
-                     "osg_sampler_multistep_single");
-    }
-    float ms = 0;
-    be.check(be.api.osg_timer_stop(be.ctx, &ms), "osg_timer_stop");
-    be.check(be.api.osg_download(be.ctx, x, samp_x, xb), "osg_download");
-    runs += n_steps;
-    m_last_ms = n_steps > 0 ? ms / n_steps : 0;
-    return ms;
+    return sampler_frame(
+        fn, sample_name, timestep_name, out_name, n_steps, prompts, branches, x, c_in, t, depth[sampler], nullptr,
+        // DDIM alone prescales x, by coef[i][5]: its pair takes the rescaling launch even where the factor is 1
+        [&](int i) { return SamplerPrescale{sampler == 5, sampler == 5 ? coef[(size_t)i * 6 + 5] : 1.f}; },
+        [&](int i, float* sx, const float* eps, const float*, long L, auto&& slot) {
+            const float* k = coef + (size_t)i * 6;
+            const int form = forms[sampler][order[i]], r = reads(order[i]);
+            float* h0 = slot(0);
+            const float *h1 = r >= 1 ? slot(1) : nullptr, *h2 = r >= 2 ? slot(2) : nullptr, *h3 = r >= 3 ? slot(3) : nullptr;
+            if (pair)
+                be.check(be.api.osg_sampler_cfg_multistep(be.ctx, form, sx, eps, h0, h1, h2, h3, prompts, L, c_out[i], guidance, sigma[i], k[0], k[1], k[2],
+                                                          k[3], k[4], dcoef[2 * i], dcoef[2 * i + 1]),
+                         "osg_sampler_cfg_multistep");
+            else
+                be.check(be.api.osg_sampler_multistep_single(be.ctx, form, sx, eps, h0, h1, h2, h3, prompts, L, c_out[i], sigma[i], k[0], k[1], k[2], k[3],
+                                                             k[4], dcoef[2 * i], dcoef[2 * i + 1]),
+                         "osg_sampler_multistep_single");
+        });
 }
 
 double Plan::sampler_loop_stochastic(const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
@@ -645,87 +646,26 @@ double Plan::sampler_loop_stochastic(const std::string& sample_name, const std::
         any_draw = any_draw || draws[i];
     }
     if (any_draw && !noise) throw std::invalid_argument(fn + "a step draws noise but no noise was given.");
-    FlightGuard flight(in_flight);
-    const SamplerIO io = sampler_io(fn, sample_name, timestep_name, out_name);
-    const long L = io.L;
-    float *sample = (float*)ptr(io.in_s->staging), *tstep = (float*)ptr(io.in_t->staging);
-    const float* eps = (const float*)ptr(io.out->f32val);
-    const int H = ring ? 3 : 0;       // create_buffers, src/samplers.h:14
-    const size_t xb = (size_t)prompts * L * sizeof(float), nb = (size_t)n_steps * xb, hb = (size_t)H * xb;
-    sampler_grow(samp_x, samp_x_bytes, xb);
-    if (any_draw) sampler_grow(samp_noise, samp_noise_bytes, nb);
-    if (H) sampler_grow(samp_hist, samp_hist_bytes, hb);
-    be.check(be.api.osg_upload(be.ctx, samp_x, x, xb), "osg_upload");
-    if (any_draw) be.check(be.api.osg_upload(be.ctx, samp_noise, noise, nb), "osg_upload");
-    // history entry k of step i lives in ring slot (i - k) mod H, as in sampler_loop_multistep: the reference's shift (src/samplers.h:422) is a rotation
-    auto slot = [&](int i, int k) -> float* { return (float*)samp_hist + (size_t)(((i - k) % H + H) % H) * prompts * L; };
-    be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");
-    for (int i = 0; i < n_steps; i++) {
-        const float* k = coef + (size_t)i * 10;
-        if (!pair)
-            be.check(be.api.osg_sampler_prepare_single(be.ctx, (float*)samp_x, sample, tstep, prompts, L, k[9], c_in[i], t[i], io.TL), "osg_sampler_prepare_single");
-        else if (k[9] != 1.f)
-            be.check(be.api.osg_sampler_prepare_rescale(be.ctx, (float*)samp_x, sample, tstep, prompts, L, k[9], c_in[i], t[i], io.TL),
-                     "osg_sampler_prepare_rescale");
-        else
-            be.check(be.api.osg_sampler_prepare(be.ctx, (const float*)samp_x, sample, tstep, prompts, L, c_in[i], t[i], io.TL), "osg_sampler_prepare");
-        if (graph) be.check(be.api.osg_graph_launch(be.ctx, graph), "osg_graph_launch");
-        else run_steps();
-        const int f = form[i];
-        float* h0 = sde(f) ? slot(i, 0) : nullptr;
-        const float *h1 = f == OSG_ST_SDE1 || f == OSG_ST_SDE2 ? slot(i, 1) : nullptr, *h2 = f == OSG_ST_SDE2 ? slot(i, 2) : nullptr;
-        const float* nz = draws[i] ? (const float*)samp_noise + (size_t)i * prompts * L : nullptr;
-        if (pair)
-            be.check(be.api.osg_sampler_cfg_stochastic(be.ctx, f, (float*)samp_x, eps, nz, h0, h1, h2, prompts, L, c_out[i], guidance, sigma[i], k[0], k[1], k[2],
-                                                       k[3], k[4], k[5], k[6], k[7], k[8]),
-                     "osg_sampler_cfg_stochastic");
-        else
-            be.check(be.api.osg_sampler_stochastic_single(be.ctx, f, (float*)samp_x, eps, nz, h0, h1, h2, prompts, L, c_out[i], sigma[i], k[0], k[1], k[2], k[3],
-                                                          k[4], k[5], k[6], k[7], k[8]),
-                     "osg_sampler_stochastic_single");
-    }
-    float ms = 0;
-    be.check(be.api.osg_timer_stop(be.ctx, &ms), "osg_timer_stop");
-    be.check(be.api.osg_download(be.ctx, x, samp_x, xb), "osg_download");
-    runs += n_steps;
-    m_last_ms = n_steps > 0 ? ms / n_steps : 0;
-    return ms;
-}
-
-double Plan::run_sampler_loop_stochastic(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name,
-                                         int n_steps, int prompts, float* x, const float* c_in, const float* c_out, const float* t, const float* sigma,
-                                         const int* form, const int* draws, const float* coef, size_t n_coef, const float* noise, float guidance,
-                                         int branches) {
-    if (!m.m_plan)
-        throw std::runtime_error(std::string(branches == 2 ? "Model::hip_sampler_loop_stochastic" : "Model::hip_sampler_loop_stochastic_single") +
-                                 ": no plan (call run() first).");
-    const double ms = m.m_plan->sampler_loop_stochastic(sample_name, timestep_name, out_name, n_steps, prompts, x, c_in, c_out, t, sigma, form, draws, coef,
-                                                        n_coef, noise, guidance, branches);
-    m.m_last_ms = m.m_plan->last_ms();
-    return ms;
-}
-
-double Plan::run_sampler_loop(Model& m,const std::string& sample_name, const std::string& timestep_name, const std::string& out_name, int n_steps,
-                              int prompts, float* x, const float* noise, const float* c_in, const float* c_out, const float* t, const float* sigma,
-                              const float* d_sigma, const float* sigma_up, const float* clip, int branches) {
-    if (!m.m_plan) throw std::runtime_error("Model::hip_sampler_loop_single: no plan (call run() first).");
-    const double ms = m.m_plan->sampler_loop(sample_name, timestep_name, out_name, n_steps, prompts, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, 0.f,
-                                             clip, branches);
-    m.m_last_ms = m.m_plan->last_ms();
-    return ms;
-}
-
-double Plan::run_sampler_loop_multistep(Model& m, const std::string& sample_name, const std::string& timestep_name, const std::string& out_name,
-                                       int n_steps, int prompts, int sampler, float* x, const float* c_in, const float* c_out, const float* t,
-                                       const float* sigma, const int* order, const float* coef, size_t n_coef, const double* dcoef, size_t n_dcoef,
-                                       float guidance, int branches) {
-    if (!m.m_plan)
-        throw std::runtime_error(std::string(branches == 2 ? "Model::hip_sampler_loop_multistep" : "Model::hip_sampler_loop_multistep_single") +
-                                 ": no plan (call run() first).");
-    const double ms = m.m_plan->sampler_loop_multistep(sample_name, timestep_name, out_name, n_steps, prompts, sampler, x, c_in, c_out, t, sigma, order,
-                                                       coef, n_coef, dcoef, n_dcoef, guidance, branches);
-    m.m_last_ms = m.m_plan->last_ms();
-    return ms;
+    return sampler_frame(
+        fn, sample_name, timestep_name, out_name, n_steps, prompts, branches, x, c_in, t, ring ? 3 : 0 /* create_buffers, src/samplers.h:14 */,
+        any_draw ? noise : nullptr,
+        // coef[i][9] prescales x: the pair takes the rescaling launch only where it is not 1
+        [&](int i) { const float s = coef[(size_t)i * 10 + 9]; return SamplerPrescale{s != 1.f, s}; },
+        [&](int i, float* sx, const float* eps, const float* nz, long L, auto&& slot) {
+            const float* k = coef + (size_t)i * 10;
+            const int f = form[i];
+            float* h0 = sde(f) ? slot(0) : nullptr;
+            const float *h1 = f == OSG_ST_SDE1 || f == OSG_ST_SDE2 ? slot(1) : nullptr, *h2 = f == OSG_ST_SDE2 ? slot(2) : nullptr;
+            if (!draws[i]) nz = nullptr;
+            if (pair)
+                be.check(be.api.osg_sampler_cfg_stochastic(be.ctx, f, sx, eps, nz, h0, h1, h2, prompts, L, c_out[i], guidance, sigma[i], k[0], k[1], k[2], k[3],
+                                                           k[4], k[5], k[6], k[7], k[8]),
+                         "osg_sampler_cfg_stochastic");
+            else
+                be.check(be.api.osg_sampler_stochastic_single(be.ctx, f, sx, eps, nz, h0, h1, h2, prompts, L, c_out[i], sigma[i], k[0], k[1], k[2], k[3], k[4],
+                                                              k[5], k[6], k[7], k[8]),
+                         "osg_sampler_stochastic_single");
+        });
 }
 
 double Plan::decode_tiles(const std::string& in_name, const std::string& out_name, int images, int H, int W, float factor, const float* latents,
@@ -772,17 +712,9 @@ double Plan::decode_tiles(const std::string& in_name, const std::string& out_nam
                                     " (upscale factor " + std::to_string(up) + ").");
     if (!image && !pixels) return 0.0;
     FlightGuard flight(in_flight);
-    auto grow = [&](void*& p, size_t& have, size_t need) {
-        if (have >= need) return;
-        if (p) be.check(be.api.osg_free(be.ctx, p), "osg_free");
-        p = nullptr;
-        have = 0;
-        be.check(be.api.osg_malloc(be.ctx, need, &p), "osg_malloc");
-        have = need;
-    };
-    grow(dec_lat, dec_lat_bytes, lb);
-    if (image) grow(dec_img, dec_img_bytes, px * sizeof(float));
-    if (pixels) grow(dec_pix, dec_pix_bytes, px);
+    grow_buffer(dec_lat, dec_lat_bytes, lb);
+    if (image) grow_buffer(dec_img, dec_img_bytes, px * sizeof(float));
+    if (pixels) grow_buffer(dec_pix, dec_pix_bytes, px);
     be.check(be.api.osg_upload(be.ctx, dec_lat, latents, lb), "osg_upload");
     be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");
     be.check(be.api.osg_decode_gather(be.ctx, (const float*)dec_lat, (float*)ptr(in->staging), images, H, W, (int)t, factor), "osg_decode_gather");
@@ -797,14 +729,6 @@ double Plan::decode_tiles(const std::string& in_name, const std::string& out_nam
     if (pixels) be.check(be.api.osg_download(be.ctx, pixels, dec_pix, px), "osg_download");
     runs++;
     m_last_ms = ms;
-    return ms;
-}
-
-double Plan::run_decode(Model& m, const std::string& in_name, const std::string& out_name, int images, int H, int W, float factor, const float* latents,
-                        float* image, size_t image_elems, uint8_t* pixels, size_t pixels_elems) {
-    if (!m.m_plan) throw std::runtime_error("Model::hip_decode: no plan (call run() first).");
-    const double ms = m.m_plan->decode_tiles(in_name, out_name, images, H, W, factor, latents, image, image_elems, pixels, pixels_elems);
-    m.m_last_ms = m.m_plan->last_ms();
     return ms;
 }
 
@@ -979,9 +903,9 @@ double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long 
     const long cap = dp->dspec.cap;
     FlightGuard flight(dp->in_flight);
     // ---- entry: state, the caches into their capacity buffers (strided copies), the last row of the prompt's logits into the pass's logits buffer ----
-    dp->sampler_grow(dp->dec_tokens, dp->dec_tokens_bytes, (size_t)n_seq * max_new * 8);
-    if (logits_trace) dp->sampler_grow(dp->dec_trace, dp->dec_trace_bytes, (size_t)n_seq * max_new * V * sizeof(float));
-    if (batch) dp->sampler_grow(dp->dec_seeds, dp->dec_seeds_bytes, (size_t)n_seq * 8);
+    dp->grow_buffer(dp->dec_tokens, dp->dec_tokens_bytes, (size_t)n_seq * max_new * 8);
+    if (logits_trace) dp->grow_buffer(dp->dec_trace, dp->dec_trace_bytes, (size_t)n_seq * max_new * V * sizeof(float));
+    if (batch) dp->grow_buffer(dp->dec_seeds, dp->dec_seeds_bytes, (size_t)n_seq * 8);
     std::vector<size_t> slot((size_t)names.n_caches + 1, 0);      // scratch for host-side caches, on the way in (P rows) and out (up to P + max_new rows)
     for (int i = 0; i < names.n_caches; i++) slot[(size_t)i + 1] = slot[(size_t)i] + (((size_t)geo[i][0] * (P + max_new) * geo[i][1] * 2 + 255) & ~(size_t)255);
     struct Scratch {

@@ -129,14 +129,57 @@ static float stub_h2f(unsigned short h) {
 """
 
 
+# ---- opt-in trace (tests/test_sampler_loop_trace_cpu.py): when TRACE_ENV names a file while the stub is GENERATED, the bodies of the osg_sampler_* entry
+# points and of osg_graph_launch append one line per call to the file TRACE_ENV names while the stub RUNS: "<entry point> <param>=<value> ..." with
+# pointers as %p, integers as they are, floats and doubles as %a (exact).  ctx is left out.  With the variable unset the generated C is what it always was.
+TRACE_ENV = "OSGPU_STUB_TRACE"
+TRACE_HELPERS = r"""
+#include <stdarg.h>
+#include <stdio.h>
+static void stub_trace(const char* fmt, ...) {
+    const char* fn = getenv("%s");
+    FILE* f = fn && *fn ? fopen(fn, "a") : NULL;
+    if (!f) return;
+    va_list ap; va_start(ap, fmt); vfprintf(f, fmt, ap); va_end(ap);
+    fclose(f);
+}
+""" % TRACE_ENV
+
+
+def traced(name: str) -> bool:
+    return name.startswith("osg_sampler_") or name == "osg_graph_launch"
+
+
+def trace_body(name: str, params: str) -> str:
+    """the body of a traced no-op entry point, from its parameter list as the header declares it"""
+    fmt, args = [name], []
+    for p in params.split(","):
+        p = p.strip()
+        pname = re.search(r"([A-Za-z_][A-Za-z0-9_]*)$", p).group(1)
+        if pname == "ctx":
+            continue
+        if "*" in p:
+            fmt.append(pname + "=%p"); args.append(f"(void*){pname}")
+        elif re.search(r"\b(float|double)\b", p):
+            fmt.append(pname + "=%a"); args.append(f"(double){pname}")
+        else:
+            fmt.append(pname + "=%lld"); args.append(f"(long long){pname}")
+    return '{ stub_trace("%s\\n", %s); return 0; }' % (" ".join(fmt), ", ".join(args))
+
+
 def generate() -> str:
     src = open(os.path.join(REPO, "include", "osgpu.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    trace = bool(os.environ.get(TRACE_ENV))
     body = ['#include <math.h>', '#include <stdlib.h>', '#include <string.h>', '#include "osgpu.h"', "", HALF_HELPERS, ""]
+    if trace:
+        body += [TRACE_HELPERS, ""]
     for m in re.finditer(r"^\s*((?:const\s+)?[A-Za-z_][A-Za-z0-9_ ]*?[\s\*]+)(osg_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", src, flags=re.M | re.S):
         ret, name, params = m.group(1).strip(), m.group(2), " ".join(m.group(3).split())
         if name in SPECIAL:
             body.append(f"{ret} {name}({params}) {SPECIAL[name]}")
+        elif trace and traced(name) and ret == "int":
+            body.append(f"{ret} {name}({params}) {trace_body(name, params)}")
         elif ret == "int":
             body.append(f"{ret} {name}({params}) {{ return 0; }}")
         elif ret == "void":
