@@ -180,6 +180,37 @@ class Model:
         a = np.ascontiguousarray(data, np.float32)
         self._err(f(self._h, self._name(name), index, a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), a.size))
 
+    def hip_sampler_schedule(self, t):
+        """Name the timestep values the following sampler-loop calls walk: the first of them runs the timestep-only launches of the pass for each value
+        ahead of step 0 and keeps the results, so that no step has to (option hip_loop_hoist).  A value the loops meet without having been named here is
+        computed at its step and kept the same way."""
+        import numpy as np
+        f = self._lib.model_hip_sampler_schedule
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_ulonglong]; f.restype = ctypes.c_void_p
+        a = np.ascontiguousarray(t, np.float32).ravel()
+        self._err(f(self._h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), a.size))
+
+    def hip_loop_hoist_stats(self) -> dict:
+        """What the sampler loops of the current plan leave out of the step (all 0 before the first loop call, and with hip_loop_hoist off): launches of the
+        per-step graph, hoisted prompt-only (p_steps) and timestep-only (t_steps) plan steps, device bytes added, timestep-table hits / misses of the last
+        loop call, the input epoch and the filled table rows."""
+        f = self._lib.model_hip_loop_hoist_stats
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_ulonglong)]; f.restype = None
+        out = (ctypes.c_ulonglong * 8)()
+        f(self._h, out)
+        return dict(zip(("step_launches", "p_steps", "t_steps", "extra_bytes", "t_hits", "t_misses", "epoch", "rows"), (int(v) for v in out)))
+
+    def hip_loop_hoist_info(self) -> str:
+        """The hoisted steps, the values they write and the table state of the current plan, as text (Plan::hoist_info)."""
+        f = self._lib.model_hip_loop_hoist_info
+        f.argtypes = [ctypes.c_void_p]; f.restype = ctypes.c_void_p
+        p = f(self._h)
+        text = ctypes.cast(p, ctypes.c_char_p).value.decode("utf-8", "replace")
+        self._lib.model_free_buffer(p)
+        if text.startswith("ERROR: "):
+            raise OnnxStreamError(text[7:])
+        return text
+
     # the three device sampler loops: one marshalling helper per family; guidance None = the *_single export, which has no such argument
     def _sampler_loop(self, fname: str, sample: str, timestep: str, out: str, x, noise, c_in, c_out, t, sigma, d_sigma, sigma_up, guidance, clip):
         import numpy as np

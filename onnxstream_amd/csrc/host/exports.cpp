@@ -278,6 +278,8 @@ void model_set_option(Handle* h, char* name, unsigned int value) {
     else if (n == "hip_concat_views") m.m_hip_concat_views = b;
     else if (n == "hip_fuse_tblock") m.m_hip_fuse_tblock = b;
     else if (n == "hip_gn_stats") m.m_hip_gn_stats = (int)value;
+    else if (n == "hip_loop_hoist") Plan::loop_options(m).hoist = b;
+    else if (n == "hip_loop_hoist_rows") Plan::loop_options(m).rows = (int)value;
     else if (n == "hip_stream_weights") m.m_hip_stream_weights = b;
     else if (n == "hip_w8_resident") m.m_hip_w8_resident = b;
     else if (n == "hip_resident_outputs") m.m_hip_resident_outputs = b;
@@ -374,6 +376,17 @@ char* model_hip_replay(Handle* h, int n, float* ms_each) {
 // refresh sample `index` of a resident graph input (fp32, `count` elements) without running a pass
 char* model_hip_set_input(Handle* h, char* name, long long index, const float* data, unsigned long long count) {
     return guarded([&] { h->model.hip_set_input(name, (long)index, data, (size_t)count); });
+}
+// the timestep values (n floats) of the schedule the following sampler-loop calls walk: the first of them computes their timestep-only launches ahead of step 0
+char* model_hip_sampler_schedule(Handle* h, const float* t, unsigned long long n) { return guarded([&] { Plan::sampler_schedule(h->model, t, (size_t)n); }); }
+// the loop hoist of the current plan: out[8], see Plan::loop_hoist_stats; the text of Plan::hoist_info (malloc'ed, free with model_free_buffer; "ERROR: ..." on error)
+void model_hip_loop_hoist_stats(Handle* h, unsigned long long* out) { Plan::loop_hoist_stats(h->model, out); }
+char* model_hip_loop_hoist_info(Handle* h) {
+    try {
+        return dup_cstr(Plan::loop_hoist_info(h->model));
+    } catch (const std::exception& e) {
+        return dup_cstr(std::string("ERROR: ") + e.what());
+    }
 }
 // the reference app's denoising loop (CFG combine + Euler-Ancestral, src/sd.cpp:1397-1559, src/samplers.h:1430-1472) enqueued on the device
 // without per-step host round trips.  x:[prompts,L] fp32 is updated in place; noise:[steps,prompts,L]; the five per-step scalar arrays

@@ -851,11 +851,13 @@
                     pt.out->sink[pt.slot] = StatSinkRef{off, (int)G, (int)(C / G), (int)pt.ch_off};
                     pt.out->sink_hw = (int)HW;
                     P.steps[pt.step].what += " +gnstats";
+                    P.steps[pt.step].side = true;
                 }
                 P.add_step("GroupNorm stats< " + op.m_name, {x, g, b}, {y}, [=, this] {
                     be.check(be.api.osg_group_norm_stats_nhwc(be.ctx, P.ptr(x), P.ptr(g), P.ptr(b), P.ptr(y), (int)nb, HW, (int)C, (int)G, eps, (osg_act)act, P.gn_stats + off),
                              "GroupNorm");
                 });
+                P.steps.back().side = true;
                 return;
             }
         }

@@ -96,6 +96,8 @@ Plan::Plan(Model& model, HipBackend& backend, ConstPool& cpool, size_t batch) : 
     fuse_ln_gemm = m.m_hip_fuse_ln_gemm;
     concat_views = m.m_hip_concat_views;
     fuse_tblock = m.m_hip_fuse_tblock;
+    loop_hoist = pool.loop.hoist;
+    loop_hoist_rows = pool.loop.rows;
     gn_stats_req = m.m_hip_gn_stats;
     gn_stats_min_elems = m.m_hip_gn_stats == 2 ? (8L << 20) : 0;
     gn_stats_on = m.m_hip_gn_stats != 0 && !stream_weights && m.m_hip_fusion_level >= 2 && !m.m_use_uint8_arithmetic && !m.m_range_data_calibrate;
@@ -123,6 +125,7 @@ bool Plan::compatible(Model& mm, size_t batch) const {
     if (mm.m_hip_fusion_level != fusion_req || mm.m_hip_fuse_ln_gemm != fuse_ln_gemm || mm.m_hip_concat_views != concat_views || mm.m_hip_fuse_tblock != fuse_tblock || mm.m_hip_gn_stats != gn_stats_req ||
         mm.m_fuse_ops_in_attention != fuse_attn || mm.m_use_scaled_dp_attn_op != sdp_attn || mm.m_hip_autotune != autotune)
         return no("fusion / tuning options");
+    if (pool.loop.hoist != loop_hoist || (long)pool.loop.rows != loop_hoist_rows) return no("loop hoist option");
     if (want_stream != stream_weights || (size_t)mm.m_cuda_options.m_vram_to_use != vram_budget ||
         (mm.m_hip_w8_resident && !want_stream) != w8_resident)
         return no("weight residency options");
@@ -405,6 +408,8 @@ Plan::~Plan() {
     for (auto& r : recyclable) pool.give(be, r.first, r.second);   // (this plan's passes are over: see above)
     for (auto& kv : registered) be.api.osg_host_unregister(be.ctx, (void*)kv.first);
     if (graph) be.api.osg_graph_destroy(graph);
+    if (step_graph) be.api.osg_graph_destroy(step_graph);
+    if (hoist.tvals) be.api.osg_free(be.ctx, hoist.tvals);
     if (samp_x) be.api.osg_free(be.ctx, samp_x);
     if (samp_noise) be.api.osg_free(be.ctx, samp_noise);
     if (samp_hist) be.api.osg_free(be.ctx, samp_hist);

@@ -70,6 +70,7 @@ struct Step {
     std::function<void()> run;
     std::vector<int> reads, writes;
     double flops = 0;             // algorithmic 2*MAC count of a contraction step (0 for memory-bound steps)
+    bool side = false;            // touches memory outside its declared lists (the GroupNorm statistics block): never hoisted out of the sampler step
 };
 
 struct Lowering;
@@ -147,6 +148,16 @@ struct ConstPool {
         }
         spare.push_back({p, bytes});
     }
+    // what the Model is told about its sampler loops (option hip_loop_hoist, model_hip_sampler_schedule): kept here, with the other state a Model keeps for
+    // its plans, and reached through Plan::loop_options -- onnxstream.h, the header the reference application is compiled against, stays as it is.  Not
+    // touched by clear(): another model file does not change what the caller asked for
+    struct LoopOptions {
+        bool hoist = true;                 // hip_loop_hoist: the loops launch per step only what depends on the latent (Plan::Hoist); false: the whole pass
+        int rows = 64;                     // hip_loop_hoist_rows: rows of the timestep table; lowered by tests to reach the table-full path
+        std::vector<float> schedule;       // the timestep values the next loop calls walk; a plan fills their rows once per serial
+        unsigned long long schedule_serial = 0;
+    };
+    LoopOptions loop;
     // the resident decode plan of the Model (Plan::generate): T = 1 over key/value caches of a fixed capacity, kept across generate calls while the
     // capacity and the options it was built with (`decode_key`) still fit
     Plan* decode_plan = nullptr;
@@ -365,6 +376,51 @@ struct Plan {
     static void read_resident(Model& m, const Tensor& t, void* dst);
 
     osg_graph* graph = nullptr;
+    // ---- loop hoist (option hip_loop_hoist): the launches of the pass that do not depend on the latent leave the sampler step ----
+    // Classes, from two taint bits propagated through the declared reads / writes: per-step (reads something `sample` reaches), T (the timestep but not
+    // the sample), P (neither: the prompt, constants).  A P or T step is hoisted when it is the only writer of everything it writes and everything it
+    // reads is a constant, a graph input or the product of hoisted steps.  Everything a hoisted step writes moves out of the arena (which recycles by
+    // step index within ONE pass) into an allocation of its own; the captured passes are then recorded anew on the new addresses.
+    // P steps run eagerly once per loop call, before step 0.  T steps run on a miss of the row table: a row = the T values the per-step part reads,
+    // for one timestep value (keyed by the bits of t); a hit is one osg_copy per such value.
+    enum : char { CLS_STEP = 0, CLS_P = 1, CLS_T = 2 };
+    struct HoistLive { int val; size_t bytes, off; };           // a root val T steps write and others read: `off` inside a row
+    struct Hoist {
+        bool ready = false;
+        std::string sample, timestep;
+        std::vector<char> cls;                // per step, hoisted steps only: CLS_P / CLS_T, everything else CLS_STEP
+        size_t n_p = 0, n_t = 0;
+        std::vector<int> moved;               // the root vals that got their own allocation
+        std::vector<HoistLive> live;
+        size_t row_bytes = 0, extra_bytes = 0;
+        bool epoch_keyed = false;             // T reads something besides the timestep and constants: rows are valid for one input epoch only
+        char* table = nullptr;
+        long cap = 0;
+        std::vector<uint32_t> keys;           // keys[r]: bit pattern of t of filled row r
+        unsigned long long table_epoch = 0, schedule_seen = 0;
+        void* tvals = nullptr;                // the schedule's timestep broadcasts [n][N * TL] fp32, device (what fills rows ahead of step 0)
+        size_t tvals_bytes = 0;
+        unsigned long long hits = 0, misses = 0;   // of the last loop call
+    };
+    Hoist hoist;
+    bool loop_hoist = true;        // ConstPool::LoopOptions as they were when the plan was built
+    long loop_hoist_rows = 64;
+    // the Model's loop options (created with its pool on first use), and what the exports make of them: the schedule call, out[0..7] = launches of the
+    // per-step graph, hoisted prompt-only steps, hoisted timestep-only steps, device bytes the hoist added, table hits and misses of the last loop call,
+    // the input epoch, filled table rows (all 0 before the first loop call and with the option off, but the epoch), and hoist_info() of the Model's plan.
+    // Static members of Plan for the reason given at on_plan_of
+    static ConstPool::LoopOptions& loop_options(Model& m);
+    static void sampler_schedule(Model& m, const float* t, size_t n);
+    static void loop_hoist_stats(Model& m, unsigned long long out[8]);
+    static std::string loop_hoist_info(Model& m);
+    osg_graph* step_graph = nullptr;          // the per-step class alone; what sampler_frame launches once the hoist is ready
+    unsigned long long input_epoch = 0;       // bumped by every upload of an input other than the loop's sample / timestep
+    void drop_graphs();
+    osg_graph* capture(int cls);              // record run_steps(dyn_end, end, cls) into a new graph
+    void hoist_prepare(const SamplerIO& io, const std::string& sample_name, const std::string& timestep_name);
+    void hoist_fill_row(const float* tstep_src, float t, float* tstep, size_t tbytes);
+    long hoist_find(float t) const;
+    std::string hoist_info() const;           // "hoist P|T step <i> | <what>", "hoist val <id> ptr=.. bytes=..", "hoist live ..", table / epoch state
     Lowering* lowering = nullptr;  // kept alive: the launch closures capture it
     int runs = 0;
     bool in_capture = false;      // run_steps() is recording the hipGraph (no synchronisation allowed inside)
@@ -385,7 +441,8 @@ struct Plan {
     char* gn_stats = nullptr;      // the pass's statistics block: one [N][G][2] int64 table per such GroupNorm, zeroed at the start of every pass
     size_t gn_stats_bytes = 0;
     void zero_gn_stats();
-    void run_steps(size_t begin = 0, size_t end = (size_t)-1);   // steps [begin, end)
+    // steps [begin, end); cls >= 0: only the steps of that hoist class (the GroupNorm statistics are zeroed with the per-step class)
+    void run_steps(size_t begin = 0, size_t end = (size_t)-1, int cls = -1);
     // uint8 plans: steps [0, dyn_end) read values quantised per run (a pushed input and what merely re-arranges its codes): they run eagerly every
     // pass with the parameters of that pass, the steps after them only see range-data parameters and are captured like any other plan
     size_t dyn_end = 0;

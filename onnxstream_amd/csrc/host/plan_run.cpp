@@ -21,7 +21,7 @@ void Plan::zero_gn_stats() {
     if (gn_stats_bytes) be.check(be.api.osg_memset(be.ctx, gn_stats, 0, gn_stats_bytes), "osg_memset");
 }
 
-void Plan::run_steps(size_t begin, size_t end) {
+void Plan::run_steps(size_t begin, size_t end, int cls) {
     // measurement aid (tools/skip_probe.sh): OSG_PLAN_SKIP=<prefix>[,<prefix>...] leaves out every step whose description starts with one of
     // the prefixes -- the pass computes garbage, its captured-graph time shows what that class of launches really costs inside the chain
     static const std::vector<std::string> skip = [] {
@@ -39,8 +39,9 @@ void Plan::run_steps(size_t begin, size_t end) {
         return v;
     }();
     end = std::min(end, steps.size());
-    if (begin == 0) zero_gn_stats();
+    if (begin == 0 && cls <= CLS_STEP) zero_gn_stats();
     for (size_t si_ = begin; si_ < end; si_++) {
+        if (cls >= 0 && hoist.cls[si_] != cls) continue;
         Step& s = steps[si_];
         if (!skip.empty()) {
             bool sk = false;
@@ -84,10 +85,7 @@ void Plan::execute(const std::function<void()>& while_device_runs) {
                 vals[o.f32val].dptr = o.dev;
                 moved = true;
             }
-        if (moved && graph) {
-            be.api.osg_graph_destroy(graph);
-            graph = nullptr;
-        }
+        if (moved) drop_graphs();
     }
     static const bool exec_times = getenv("OSG_EXEC_TIMES") != nullptr;    // developer probe: host milliseconds of the phases of this call, to stderr
     const auto t_exec = std::chrono::steady_clock::now();
@@ -113,6 +111,7 @@ void Plan::execute(const std::function<void()>& while_device_runs) {
         if (cnt < 4 || (size_t)(up_hi - up_lo) > sum || !in_one_slab(up_lo, up_hi)) up_lo = up_hi = nullptr;
         else io_block.assign((size_t)(up_hi - up_lo), 0);
     }
+    bool new_epoch = false;
     for (auto& in : inputs) {
         Tensor* src = nullptr;
         for (auto& t : m.m_data)
@@ -120,6 +119,7 @@ void Plan::execute(const std::function<void()>& while_device_runs) {
         if (!src) throw std::invalid_argument("Model::get_tensor_data: input tensor not found: " + in.name);
         if (src->m_type != in.host_type || src->m_shape != in.shape)
             throw std::invalid_argument("Model::run: input '" + in.name + "' changed type or shape since the plan was built.");
+        if (!(hoist.ready && (in.name == hoist.sample || in.name == hoist.timestep))) new_epoch = true;   // (what the timestep rows may have been computed from)
         if (in.host_type == TensorDataType::int64 || vals[in.staging].numel() == 0) continue;   // plan-time value / empty tensor: nothing to stage
         if (in.resident) {   // on the device already; the tensor must still be the one the plan was built on
             if (src->m_hip_resident != in.resident) throw std::invalid_argument("Model::run: input '" + in.name + "' changed since the plan was built.");
@@ -154,6 +154,7 @@ void Plan::execute(const std::function<void()>& while_device_runs) {
         if (extra + 1 != N) throw std::invalid_argument("Model::run: inconsistent m_batch.size() across two or more tensors.");
         for (long i = 0; i < extra; i++) upload((*src->m_batch)[i], i + 1);
     }
+    if (new_epoch) input_epoch++;
     gathered_up = up_lo ? io_block.size() : 0;
     if (up_lo) be.check(be.api.osg_upload(be.ctx, up_lo, io_block.data(), io_block.size()), "osg_upload");
     ms_stage = ms_since(t_exec);
@@ -469,6 +470,7 @@ void Plan::set_input(const std::string& name, long index, const float* data, siz
             if (count != per) throw std::invalid_argument("Model::get_tensor_data: mismatch between tensor shape and data size.");
             if (index < 0 || index >= N) throw std::invalid_argument("Model::hip_set_input: sample index out of range.");
             be.check(be.api.osg_upload(be.ctx, (char*)ptr(in.staging) + index * per * sizeof(float), data, per * sizeof(float)), "osg_upload");
+            if (!(hoist.ready && (name == hoist.sample || name == hoist.timestep))) input_epoch++;
             return;
         }
     throw std::invalid_argument("Model::get_tensor_data: input tensor not found: " + name);
@@ -513,6 +515,207 @@ void Plan::grow_buffer(void*& p, size_t& have, size_t need) {
     have = need;
 }
 
+// ---- loop hoist (plan.h: Plan::Hoist) ------------------------------------------------------------------------------------------------------------------
+void Plan::drop_graphs() {
+    if (graph) be.api.osg_graph_destroy(graph);
+    if (step_graph) be.api.osg_graph_destroy(step_graph);
+    graph = step_graph = nullptr;
+}
+
+osg_graph* Plan::capture(int cls) {
+    be.check(be.api.osg_graph_begin(be.ctx), "osg_graph_begin");
+    in_capture = true;
+    osg_graph* g = nullptr;
+    try {
+        run_steps(dyn_end, (size_t)-1, cls);
+        in_capture = false;
+    } catch (...) {
+        in_capture = false;
+        be.api.osg_graph_end(be.ctx, &g);
+        if (g) be.api.osg_graph_destroy(g);
+        throw;
+    }
+    be.check(be.api.osg_graph_end(be.ctx, &g), "osg_graph_end");
+    return g;
+}
+
+// Classify the steps for the loop's (sample, timestep) pair, give what the hoisted ones write a home outside the arena and record the passes anew.  Runs
+// on the first loop call (and again should a later call name other inputs); nothing is enqueued, the plan's passes have all been waited for.
+void Plan::hoist_prepare(const SamplerIO& io, const std::string& sample_name, const std::string& timestep_name) {
+    if (!loop_hoist || (hoist.ready && hoist.sample == sample_name && hoist.timestep == timestep_name)) return;
+    Hoist& h = hoist;
+    const int rs = root_of(io.in_s->staging), rt = root_of(io.in_t->staging);
+    std::vector<char> taint(vals.size(), 0), home(vals.size(), 0);      // home[r]: the class of the hoisted step that writes root r
+    std::vector<int> writers(vals.size(), 0);
+    taint[rs] |= 1;
+    taint[rt] |= 2;
+    for (auto& s : steps) {
+        std::set<int> ws;
+        for (int w : s.writes)
+            if (w >= 0) ws.insert(root_of(w));
+        for (int w : ws) writers[w]++;
+    }
+    std::set<int> out_vals;
+    for (auto& o : outputs) out_vals.insert(root_of(o.f32val));
+    h.cls.assign(steps.size(), CLS_STEP);
+    h.n_p = h.n_t = 0;
+    for (size_t si = 0; si < steps.size(); si++) {
+        const Step& s = steps[si];
+        char bits = 0;
+        for (int r : s.reads)
+            if (r >= 0) bits |= taint[root_of(r)];
+        for (int w : s.writes)
+            if (w >= 0) taint[root_of(w)] |= bits;
+        if ((bits & 1) || s.side || s.writes.empty() || si < dyn_end) continue;
+        const char c = (bits & 2) ? CLS_T : CLS_P;
+        bool ok = true;
+        for (int w : s.writes) {
+            if (w < 0) continue;
+            const int r = root_of(w);
+            ok = ok && writers[r] == 1 && !vals[r].is_const && !vals[r].host_only && val_bytes(r) > 0;
+        }
+        for (int v : s.reads) {
+            if (v < 0) continue;
+            const int r = root_of(v);
+            // a constant, a graph input (nothing writes it), or what a hoisted step leaves in a buffer of its own: never a value the per-step part computes
+            ok = ok && (vals[r].is_const || vals[r].host_only || writers[r] == 0 || home[r] != 0);
+        }
+        if (!ok) continue;
+        h.cls[si] = c;
+        (c == CLS_T ? h.n_t : h.n_p)++;
+        for (int w : s.writes)
+            if (w >= 0) home[root_of(w)] = c;
+    }
+    // out of the arena: its packing lets a later step of the SAME pass reuse the bytes, a hoisted value must outlive the pass
+    auto aligned = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    for (size_t r = 0; r < vals.size(); r++)
+        if (home[r] && vals[r].root < 0 && !vals[r].dptr) {
+            vals[r].dptr = small_alloc(val_bytes((int)r));
+            vals[r].pinned = true;
+            h.moved.push_back((int)r);
+            h.extra_bytes += aligned(val_bytes((int)r));
+        }
+    // a row of the table: what T steps write and anything else reads
+    h.live.clear();
+    h.row_bytes = 0;
+    h.epoch_keyed = false;
+    std::vector<char> live(vals.size(), 0);
+    for (size_t si = 0; si < steps.size(); si++)
+        for (int v : steps[si].reads) {
+            if (v < 0) continue;
+            const int r = root_of(v);
+            if (h.cls[si] != CLS_T && home[r] == CLS_T) live[r] = 1;
+            if (h.cls[si] == CLS_T && r != rt && !vals[r].is_const && !vals[r].host_only && home[r] != CLS_T) h.epoch_keyed = true;
+        }
+    for (int r : out_vals)
+        if (home[r] == CLS_T) live[r] = 1;
+    for (size_t r = 0; r < vals.size(); r++)
+        if (live[r]) {
+            h.live.push_back(HoistLive{(int)r, val_bytes((int)r), h.row_bytes});
+            h.row_bytes += aligned(val_bytes((int)r));
+        }
+    h.keys.clear();
+    h.cap = std::max(0L, std::min(64L, loop_hoist_rows));
+    h.table = nullptr;
+    if (h.row_bytes && h.cap) {
+        h.table = (char*)be.malloc(h.row_bytes * (size_t)h.cap);
+        owned.push_back(h.table);
+        h.extra_bytes += h.row_bytes * (size_t)h.cap;
+    } else
+        h.cap = 0;
+    h.table_epoch = input_epoch;
+    h.schedule_seen = 0;
+    h.sample = sample_name;
+    h.timestep = timestep_name;
+    h.ready = true;
+    // the recorded passes hold the old addresses
+    const bool had = graph != nullptr;
+    drop_graphs();
+    if (had) graph = capture(-1);
+}
+
+ConstPool::LoopOptions& Plan::loop_options(Model& m) {
+    if (!m.m_pool) m.m_pool = new ConstPool();
+    return m.m_pool->loop;
+}
+
+void Plan::sampler_schedule(Model& m, const float* t, size_t n) {
+    if (n && !t) throw std::invalid_argument("model_hip_sampler_schedule: no timestep values given.");
+    ConstPool::LoopOptions& o = loop_options(m);
+    o.schedule.assign(t, t + n);
+    o.schedule_serial++;
+}
+
+void Plan::loop_hoist_stats(Model& m, unsigned long long out[8]) {
+    for (int i = 0; i < 8; i++) out[i] = 0;
+    if (!m.m_plan) return;
+    const Hoist& h = m.m_plan->hoist;
+    out[6] = m.m_plan->input_epoch;
+    if (!h.ready) return;
+    out[0] = m.m_plan->kernel_count() - h.n_p - h.n_t;
+    out[1] = h.n_p;
+    out[2] = h.n_t;
+    out[3] = h.extra_bytes;
+    out[4] = h.hits;
+    out[5] = h.misses;
+    out[7] = h.keys.size();
+}
+
+std::string Plan::loop_hoist_info(Model& m) {
+    if (!m.m_plan) throw std::runtime_error("model_hip_loop_hoist_info: no plan (call run() first).");
+    return m.m_plan->hoist_info();
+}
+
+long Plan::hoist_find(float t) const {
+    uint32_t key;
+    std::memcpy(&key, &t, 4);
+    for (size_t r = 0; r < hoist.keys.size(); r++)
+        if (hoist.keys[r] == key) return (long)r;
+    return -1;
+}
+
+// the T steps for the timestep now in the staging buffer -- today's launches in today's order -- and, while the table has room, their row
+void Plan::hoist_fill_row(const float* tstep_src, float t, float* tstep, size_t tbytes) {
+    if (tstep_src) be.check(be.api.osg_copy(be.ctx, tstep, tstep_src, tbytes), "osg_copy");
+    run_steps(0, (size_t)-1, CLS_T);
+    if ((long)hoist.keys.size() >= hoist.cap) return;
+    char* row = hoist.table + hoist.keys.size() * hoist.row_bytes;
+    for (auto& l : hoist.live) be.check(be.api.osg_copy(be.ctx, row + l.off, ptr(l.val), l.bytes), "osg_copy");
+    uint32_t key;
+    std::memcpy(&key, &t, 4);
+    hoist.keys.push_back(key);
+}
+
+std::string Plan::hoist_info() const {
+    std::string out;
+    char buf[256];
+    snprintf(buf, sizeof buf, "hoist ready=%d option=%d p=%zu t=%zu extra_bytes=%zu row_bytes=%zu cap=%ld rows=%zu epoch_keyed=%d epoch=%llu\n", (int)hoist.ready,
+             (int)loop_hoist, hoist.n_p, hoist.n_t, hoist.extra_bytes, hoist.row_bytes, hoist.cap, hoist.keys.size(), (int)hoist.epoch_keyed, input_epoch);
+    out += buf;
+    snprintf(buf, sizeof buf, "arena base=%zu bytes=%zu\n", (size_t)(uintptr_t)arena, arena_bytes);
+    out += buf;
+    if (!hoist.ready) return out;
+    for (size_t i = 0; i < steps.size(); i++)
+        if (hoist.cls[i] != CLS_STEP) {
+            snprintf(buf, sizeof buf, "hoist %c step %zu | ", hoist.cls[i] == CLS_T ? 'T' : 'P', i);
+            out += buf + steps[i].what + "\n";
+        }
+    for (size_t i = 0; i < steps.size(); i++)
+        if (hoist.cls[i] != CLS_STEP)
+            for (int w : steps[i].writes) {
+                if (w < 0) continue;
+                const int r = root_of(w);
+                snprintf(buf, sizeof buf, "hoist val %d step %zu base=%zu bytes=%zu moved=%d\n", r, i, (size_t)(uintptr_t)ptr(r), val_bytes(r),
+                         (int)(std::find(hoist.moved.begin(), hoist.moved.end(), r) != hoist.moved.end()));
+                out += buf;
+            }
+    for (auto& l : hoist.live) {
+        snprintf(buf, sizeof buf, "hoist live %d bytes=%zu off=%zu\n", l.val, l.bytes, l.off);
+        out += buf;
+    }
+    return out;
+}
+
 // The frame the three sampler loops share: everything between a loop's own table checks and its return.  H: depth of the history ring the loop needs
 // (0: none); noise: [steps, prompts, L] host, uploaded when non-NULL.  Per step one prepare launch, the pass, one update launch:
 //   prescale(i) -> {rescale, x_scale}: the pair launches osg_sampler_prepare_rescale with x_scale where `rescale` and osg_sampler_prepare otherwise; the
@@ -536,7 +739,36 @@ double Plan::sampler_frame(const std::string& fn, const std::string& sample_name
     be.check(be.api.osg_upload(be.ctx, samp_x, x, xb), "osg_upload");
     if (noise) be.check(be.api.osg_upload(be.ctx, samp_noise, noise, nb), "osg_upload");
     float* const sx = (float*)samp_x;
+    // ---- loop hoist: only the per-step class is launched per step.  The prompt-only steps run here, once per call (nothing of them is kept across calls: a
+    // run() or hip_set_input in between may have changed what they read); the timestep-only steps run where the table has no row for t[i]
+    hoist_prepare(io, sample_name, timestep_name);
+    Hoist& hz = hoist;
+    const bool hoisted = loop_hoist && hz.ready && hz.n_p + hz.n_t > 0;
+    if (hoisted && graph && !step_graph) step_graph = capture(CLS_STEP);
+    const size_t tbytes = val_bytes(io.in_t->staging);
+    if (hoisted && hz.n_t && hz.cap && pool.loop.schedule_serial != hz.schedule_seen && !pool.loop.schedule.empty()) {
+        // the schedule's timestep broadcasts, as osg_sampler_prepare* writes them, on the device before anything of this call is enqueued
+        const size_t per = tbytes / sizeof(float);
+        std::vector<float> bc(pool.loop.schedule.size() * per);
+        for (size_t k = 0; k < pool.loop.schedule.size(); k++) std::fill(bc.begin() + k * per, bc.begin() + (k + 1) * per, pool.loop.schedule[k]);
+        grow_buffer(hz.tvals, hz.tvals_bytes, bc.size() * sizeof(float));
+        be.check(be.api.osg_upload(be.ctx, hz.tvals, bc.data(), bc.size() * sizeof(float)), "osg_upload");
+    }
     be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");
+    if (hoisted) {
+        hz.hits = hz.misses = 0;
+        if (hz.n_p) run_steps(0, (size_t)-1, CLS_P);
+        if (hz.n_t && hz.epoch_keyed && hz.table_epoch != input_epoch) {   // rows computed from other inputs than are resident now
+            hz.keys.clear();
+            hz.table_epoch = input_epoch;
+        }
+        if (hz.n_t && hz.cap && pool.loop.schedule_serial != hz.schedule_seen) {
+            for (size_t k = 0; k < pool.loop.schedule.size(); k++)
+                if (hoist_find(pool.loop.schedule[k]) < 0 && (long)hz.keys.size() < hz.cap)
+                    hoist_fill_row((const float*)((const char*)hz.tvals + k * tbytes), pool.loop.schedule[k], tstep, tbytes);
+            hz.schedule_seen = pool.loop.schedule_serial;
+        }
+    }
     for (int i = 0; i < n_steps; i++) {
         const SamplerPrescale ps = prescale(i);
         if (branches != 2)
@@ -545,7 +777,19 @@ double Plan::sampler_frame(const std::string& fn, const std::string& sample_name
             be.check(be.api.osg_sampler_prepare_rescale(be.ctx, sx, sample, tstep, prompts, L, ps.x_scale, c_in[i], t[i], io.TL), "osg_sampler_prepare_rescale");
         else
             be.check(be.api.osg_sampler_prepare(be.ctx, sx, sample, tstep, prompts, L, c_in[i], t[i], io.TL), "osg_sampler_prepare");
-        if (graph) be.check(be.api.osg_graph_launch(be.ctx, graph), "osg_graph_launch");
+        if (hoisted && hz.n_t) {
+            const long r = hoist_find(t[i]);
+            if (r >= 0) {
+                hz.hits++;
+                for (auto& l : hz.live) be.check(be.api.osg_copy(be.ctx, ptr(l.val), hz.table + (size_t)r * hz.row_bytes + l.off, l.bytes), "osg_copy");
+            } else {
+                hz.misses++;
+                hoist_fill_row(nullptr, t[i], tstep, tbytes);
+            }
+        }
+        if (hoisted && step_graph) be.check(be.api.osg_graph_launch(be.ctx, step_graph), "osg_graph_launch");
+        else if (hoisted) run_steps(0, (size_t)-1, CLS_STEP);
+        else if (graph) be.check(be.api.osg_graph_launch(be.ctx, graph), "osg_graph_launch");
         else run_steps();
         const float* nz = noise ? (const float*)samp_noise + (size_t)i * row : nullptr;
         auto slot = [&](int k) -> float* { return H ? (float*)samp_hist + (size_t)(((i - k) % H + H) % H) * row : nullptr; };

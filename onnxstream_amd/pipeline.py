@@ -473,6 +473,8 @@ class Txt2Img:
             s_arr[i] = f32(sig[i])
             d_sigma[i] = f32(sigma_down - f32(sig[i]))
             s_up[i] = sigma_up
+        if getattr(self, "batched", False) and getattr(self, "unet", None) is not None:      # the schedule's timesteps: the device loops compute what depends on them alone once per value, ahead of step 0
+            self.unet.hip_sampler_schedule(ts)
         return c_in, c_out, ts, s_arr, d_sigma, s_up
 
     def multistep_table(self, sig: np.ndarray, sampler: str, xl: bool = False, turbo: bool = False):
