@@ -398,6 +398,24 @@ int osg_sdpa_len_batch(osg_ctx* ctx, osg_dtype dtype, const void* q, const void*
  * stands at a position of its own.  The arithmetic and the roundings per element are those of osg_rope. */
 int osg_rope_batch(osg_ctx* ctx, osg_dtype dtype, const void* x, const void* cos_t, const void* sin_t, void* y, long batch, long heads, long T, int d);
 
+/* ---- the prompt's half of a chat turn on the device (model_hip_turn): the prompt runs in chunks of C rows over the same capacity buffers, the chunk's
+ * first row a device int32 `base` (osg_prefill_stage writes it). */
+/* osg_sdpa for a chunk of C <= 512 query rows over capacity buffers: q, o [B][Hq][C][D], k / v [B][Hkv][cap][D] with the head and batch strides given
+ * (elements).  *base is read once at workgroup entry (negative: 0); query row i sees the keys 0 .. base + i, the key count is min(base + C, cap).  No mask
+ * tensor is read: the causal bound is a compare on the key index, a barred key gets the addend `masked` (what the graph's own mask holds there: a
+ * negative finite f16 value or -inf, as a float).  It launches the instantiation osg_sdpa launches for (that Tq = C, D, mask present), grid
+ * ceil(C / 64) x B Hq, with the same arithmetic: the output has the bits of osg_sdpa on dense copies of the first base + C rows with the explicit mask
+ * m[i][j] = 0 for j <= base + i, else `masked`.  Rows at and past base + C are never read.  batch * q_heads <= 65535. */
+int osg_sdpa_chunk(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, const void* v, void* o, const int* base, float masked,
+                   long kv_head_stride, long kv_batch_stride, long cap, int batch, int q_heads, int kv_heads, int C, int D, float scale);
+/* cache[h][*base + i][0..d) = src[h][i][0..d) for h < kv_heads, i < C: the chunk's new key or value rows, f16 [kv_heads][C][d], into a capacity buffer
+ * [kv_heads][cap][d].  A row outside [0, cap) is not written; the other rows still are. */
+int osg_kv_append_rows_at(osg_ctx* ctx, const void* src, void* cache, const int* base, int kv_heads, int C, long cap, int d);
+/* The staging of one chunk, one launch of one workgroup: for i < C, input_ids[i] = prompt[first + i] and position_ids[i] = pos0 + i while
+ * first + i < n_prompt, both 0 behind the prompt's end (padding rows); *base = pos0.  prompt: DEVICE int64 [n_prompt]; first, pos0 and C are host
+ * values (the host knows where every chunk stands), so nothing but the tokens is read.  0 <= first < n_prompt, pos0 >= 0. */
+int osg_prefill_stage(osg_ctx* ctx, const int64_t* prompt, long n_prompt, long first, long pos0, int C, int64_t* input_ids, int64_t* position_ids, int* base);
+
 /* ---- normalisation / reductions ---------------------------------------------------------------------------- */
 /* InstanceNormalization on [rows, L] (reference input [1,G,L], onnxstream.cpp:4788-5055): per row mean/var in f32,
  * y = scale[row % n_scale]*(x-mean)/sqrt(var+eps)+bias[row % n_scale]; scale/bias are f32 (forced f32 at :4802). */

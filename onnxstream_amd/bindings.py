@@ -416,6 +416,52 @@ class Model:
                     int(draw_base) & (2 ** 64 - 1)))
         return ([toks[s, :n[s]].copy() for s in range(ns)], stop, [tr[s, :n[s]].copy() for s in range(ns)] if tr is not None else None, ms.value)
 
+    def turn(self, prompt, max_new: int, n_caches: int, chunk: int = 32, capacity: int = 0, eos_id: int = -1, sync_every: int = 0, trace: bool = False,
+             vocab: int = 0, ids: str = "input_ids", pos: str = "position_ids", mask: str = "attention_mask", logits: str = "logits", cache_in: str = "pkv",
+             cache_out: str = "opkv", temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, draw_base: int = 0):
+        """One chat turn on the device (model_hip_turn): the prompt's tokens run in chunks of `chunk` rows over the conversation's caches (`cache_out`<i> as
+        a run() or a turn left them, else `cache_in`<i> as pushed -- zero rows on the first turn), then up to max_new tokens are picked and run as `generate`
+        does, the first from the prefill's own last logits row; nothing comes back to the host in between.  Leaves the caches of P + len(prompt) + n_tokens
+        rows and `logits` [1, 1, V] of the last pass that ran.  capacity > 0 asks for capacity buffers of at least that many rows, so that later turns
+        rebuild no plan.  trace needs `vocab` (the width of a logits row) unless a logits tensor is in the Model.  Returns what `generate` returns:
+        (tokens, stop, trace or None, device ms of the whole turn)."""
+        import numpy as np
+        cp, ip = ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)
+        f = self._lib.model_hip_turn
+        f.argtypes = [ctypes.c_void_p, cp, cp, cp, cp, cp, cp, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
+                      ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), ip, ip, ctypes.POINTER(ctypes.c_float),
+                      ctypes.POINTER(ctypes.c_double), ctypes.c_float, ctypes.c_longlong, ctypes.c_float, ctypes.c_ulonglong, ctypes.c_ulonglong]
+        f.restype = ctypes.c_void_p
+        pr = np.ascontiguousarray(np.asarray(prompt, np.int64).reshape(-1))
+        toks = np.zeros(max(int(max_new), 1), np.int64)
+        tr = None
+        if trace:
+            width = int(vocab)
+            if width <= 0:
+                got = self.get_tensor(logits)
+                if got is None:
+                    raise OnnxStreamError("Model::hip_turn: a logits trace needs `vocab` while no tensor '" + logits + "' is in the Model.")
+                width = got[1][-1]
+            tr = np.zeros((max(int(max_new), 1), width), np.float32)
+        n, stop, ms = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_double(0)
+        self._err(f(self._h, self._name(ids), self._name(pos), self._name(mask), self._name(logits), self._name(cache_in), self._name(cache_out), int(n_caches),
+                    pr.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)) if pr.size else None, int(pr.size), int(chunk), int(capacity), int(max_new), int(eos_id),
+                    int(sync_every), toks.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), ctypes.byref(n), ctypes.byref(stop),
+                    tr.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if tr is not None else None, ctypes.byref(ms), float(temperature), int(top_k), float(top_p),
+                    int(seed) & (2 ** 64 - 1), int(draw_base) & (2 ** 64 - 1)))
+        return toks[:n.value].copy(), stop.value, (tr[:n.value].copy() if tr is not None else None), ms.value
+
+    def hip_prefill_plan_info(self) -> str:
+        """The chunk plan `turn` built, as hip_plan_info gives a plan; its first line is "prefill chunk <C> capacity <rows>"."""
+        f = self._lib.model_hip_prefill_plan_info
+        f.argtypes = [ctypes.c_void_p]; f.restype = ctypes.c_void_p
+        p = f(self._h)
+        text = ctypes.cast(p, ctypes.c_char_p).value.decode("utf-8", "replace")
+        self._lib.model_free_buffer(p)
+        if text.startswith("ERROR: "):
+            raise OnnxStreamError(text[7:])
+        return text
+
     def get_tensor_f16(self, name: str):
         """The bits of a float16 tensor of Model::m_data (an output kept out of m_outputs_convert_set, e.g. a key/value cache of the LLM flow) as a
         numpy float16 array; a device-resident tensor is copied from where it lies and stays there (model_hip_get_tensor_f16)."""

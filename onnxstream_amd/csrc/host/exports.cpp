@@ -514,6 +514,46 @@ char* model_hip_generate_batch(Handle* h, const char* ids_name, const char* pos_
         return Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, rule, n_seq, seeds, true);
     });
 }
+// One chat turn of the reference's second application (src/llm.cpp:456-497) as one call: prompt tokens in, generated tokens out.  A run() has happened before
+// (the app's weight-loading pass counts), and the conversation so far is the caches <cache_out_prefix><i> [1, Hkv, P, d] fp16 in m_data (host or
+// device-resident) or, where those are absent, <cache_in_prefix><i> as the caller pushed them; P = 0 rows is the app's first turn (:400-412).  Neither
+// present: refused.  The call computes what this host flow computes, the prompt fed in pieces of `chunk` tokens:
+//     for each piece j:  forward(piece_j, positions P + j * chunk ..., mask ones)          (run() with the caches renamed, as the app does)
+//     then the token loop of model_hip_generate (temperature == 0: the greedy pick) or model_hip_generate_sampled, from the last row of the last piece's logits
+// A last piece of r < chunk tokens runs as a full chunk whose tail rows hold padding (token 0, position 0): they are appended behind the valid length
+// P + n_prompt and never count -- the first generated token overwrites the first of them, and no real row sees one, since every padding row stands behind
+// every real row and the attention is causal.  On the device: one upload of the prompt, then per piece osg_prefill_stage + the pass of the resident chunk
+// plan (osg_kv_append_rows_at, osg_sdpa_chunk over capacity buffers), the first token picked from the prefill's own logits row on the device; between the
+// first chunk and the end of the turn the host waits for the device only where sync_every > 0 says so.
+// It leaves in m_data: the caches <cache_out_prefix><i> [1, Hkv, P + n_prompt + n_tokens, d] where they were (host or device; an empty cache counts as
+// device-resident under hip_resident_outputs) and `logits` [1, 1, V], the row of the last pass that ran -- for max_new == 0, or when the first pick stops the
+// loop, the last real row of the prefill.  (run() leaves [1, T, V]; the app reads the last row only.)  The caches it started from are consumed.
+// capacity: rows of the capacity buffers; at least max(P + ceil(n_prompt / chunk) * chunk, P + n_prompt + max_new) are taken, rounded up to 64, and
+// capacity > 0 asks for at least that many, so that later turns rebuild nothing.  Both plans are kept across turns while their key and capacity suffice.
+// tokens / n_tokens / stop / logits_trace / sync_every / the sampling rule: as model_hip_generate_sampled.  *ms: device time of the whole turn.
+// Refused, each with "Model::hip_turn: ": what model_hip_generate_sampled refuses, n_prompt < 1, chunk outside [1, 512], capacity < 0, positions or token
+// ids (the prompt's included) beyond the smallest table they index.
+char* model_hip_turn(Handle* h, const char* ids_name, const char* pos_name, const char* mask_name, const char* logits_name, const char* cache_in_prefix,
+                     const char* cache_out_prefix, int n_caches, const long long* prompt, int n_prompt, int chunk, long long capacity, int max_new,
+                     long long eos_id, int sync_every, long long* tokens, int* n_tokens, int* stop, float* logits_trace, double* ms, float temperature,
+                     long long top_k, float top_p, unsigned long long seed, unsigned long long draw_base) {
+    return guarded(ms, [&] {
+        Plan::DecodeSpec spec;
+        spec.ids = ids_name; spec.pos = pos_name; spec.mask = mask_name; spec.logits = logits_name;
+        spec.cache_in = cache_in_prefix; spec.cache_out = cache_out_prefix; spec.n_caches = n_caches;
+        Plan::SampleRule rule;
+        rule.temperature = temperature; rule.top_k = (long)top_k; rule.top_p = top_p; rule.seed = seed; rule.draw_base = draw_base;
+        return Plan::turn(h->model, spec, prompt, n_prompt, chunk, capacity, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, rule);
+    });
+}
+// steps of the chunk plan model_hip_turn built, as model_hip_plan_info gives them, after a first line "prefill chunk <C> capacity <CAP>"; "ERROR: ..." on error
+char* model_hip_prefill_plan_info(Handle* h) {
+    try {
+        return dup_cstr(Plan::prefill_info(h->model));
+    } catch (const std::exception& e) {
+        return dup_cstr(std::string("ERROR: ") + e.what());
+    }
+}
 // steps of the decode plan model_hip_generate built, as model_hip_plan_info gives them, after a first line "decode capacity <CAP>" (a plan of n_seq > 1
 // sequences: "decode capacity <CAP> sequences <n_seq>"); "ERROR: ..." on error
 char* model_hip_decode_plan_info(Handle* h) {

@@ -1296,7 +1296,7 @@
             for (size_t k = 0; k < op.m_input.size(); k++) {
                 auto it = op.m_input[k].m_name.empty() || is_const_tensor(op.m_input[k]) ? P.by_name.end() : P.by_name.find(op.m_input[k].m_name);
                 if (it == P.by_name.end() || !P.vals[P.root_of(it->second)].dev_int || (t == "Gather" && k == 1)) continue;
-                throw std::runtime_error("Model::hip_generate: " + t + " (" + op.m_name + ") needs the value of '" + P.vals[P.root_of(it->second)].name +
+                throw std::runtime_error(P.dec_fn() + t + " (" + op.m_name + ") needs the value of '" + P.vals[P.root_of(it->second)].name +
                                          "' while the plan is built; in the device token loop it exists on the device only.");
             }
         if (!known || op.m_input.empty() || op.m_output.size() != 1) return false;

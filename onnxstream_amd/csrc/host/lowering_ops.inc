@@ -60,8 +60,33 @@
         const Val& v = P.vals[P.root_of(it->second)];
         return v.kv_cap || (v.rep_src >= 0 && P.vals[P.root_of(v.rep_src)].kv_cap);
     }
-    [[noreturn]] static void refuse_kv_cap(const Operation& op) {
-        throw std::runtime_error("Model::hip_generate: " + op.m_type + " (" + op.m_name + ") reads a key/value cache in a form the device token loop does not implement.");
+    [[noreturn]] void refuse_kv_cap(const Operation& op) const {
+        throw std::runtime_error(P.dec_fn() + op.m_type + " (" + op.m_name + ") reads a key/value cache in a form the device token loop does not implement.");
+    }
+    // chunk plans: the plan-time mask [C][CAP] of an attention over capacity buffers must be exactly the causal form osg_sdpa_chunk works out of the
+    // device-side row -- 0 where j <= CAP - C + i (the stand-in caches hold CAP - C rows), ONE other value elsewhere, which is returned (what the
+    // graph's mask holds for a barred key, rounded to f16 as an upload of the mask would round it).  Anything else is refused by name.
+    float causal_mask_value(const Operation& op, const Val* hm, long C, long cap) const {
+        auto refuse = [&](const std::string& why) {
+            throw std::runtime_error(P.dec_fn() + op.m_type + " (" + op.m_name + "): the attention mask is not the causal mask of a chunk of " + std::to_string(C) +
+                                     " rows behind " + std::to_string(cap - C) + " cached rows (" + why + "); a sliding window or a padding term is not implemented in the device prefill.");
+        };
+        if (!hm || hm->dtype == OSG_I64 || (long)hm->host_f.size() != C * cap) refuse("its values are not known while the plan is built");
+        bool have = false;
+        float masked = -65504.0f;      // (C == 1 bars nothing: the value is never applied)
+        for (long i = 0; i < C; i++)
+            for (long j = 0; j < cap; j++) {
+                const float v = half_to_float(float_to_half(hm->host_f[(size_t)(i * cap + j)]));
+                if (j <= cap - C + i) {
+                    if (v != 0.0f) refuse("a key at or before its query row is barred");
+                    continue;
+                }
+                if (!(v < 0.0f)) refuse("a key behind its query row is not barred");
+                if (have && v != masked) refuse("barred keys hold more than one value");
+                masked = v;
+                have = true;
+            }
+        return masked;
     }
 
     // Conv (reference :4494-4707 -> XnnPack::convolution :1292): group 1, dilation 1, pads re-centred (:1315-1329)
@@ -1169,8 +1194,10 @@
             need(op, es.size() == 4 && ss.size() == 5 && es[0] == 1 && es[1] == ss[1] * V(r).rep && es[2] == ss[3] && es[3] == ss[4], "invalid shape of key or value.");
             return P.alias(src, Shape{1, ss[1], ss[3], ss[4]}, Lay::plain);
         };
-        const int q = P.ensure_plain(in_val(op.m_input[0])), k = kv_operand(op.m_input[1]), mk = P.ensure_plain(in_val(op.m_input[2])), v = kv_operand(op.m_input[3]);
-        const Shape qs = V(q).shape, ks = V(k).shape, vs = V(v).shape, ms = V(mk).shape;
+        // (chunk plans: a mask known at plan time is checked and dropped below -- it gets no device storage)
+        const Val* hm = P.decode && P.dspec.chunk > 0 ? hval(op.m_input[2]) : nullptr;
+        const int q = P.ensure_plain(in_val(op.m_input[0])), k = kv_operand(op.m_input[1]), mk = hm ? -1 : P.ensure_plain(in_val(op.m_input[2])), v = kv_operand(op.m_input[3]);
+        const Shape qs = V(q).shape, ks = V(k).shape, vs = V(v).shape, ms = hm ? hm->shape : V(mk).shape;
         need(op, qs.size() == 4, "invalid shape of query.");
         need(op, ks.size() == 4, "invalid shape of key.");
         need(op, vs.size() == 4, "invalid shape of value.");
@@ -1178,14 +1205,28 @@
         const long Bq = qs[0], Hq = qs[1], T = qs[2], D = qs[3], Hkv = ks[1], S = ks[2], Dv = vs[3];
         need(op, ks[0] == Bq && vs[0] == Bq && ks[3] == D && vs[1] == Hkv && vs[2] == S && Hkv > 0 && Hq % Hkv == 0, "invalid shape of query, key or value.");
         need(op, ms[ms.size() - 2] == T && ms[ms.size() - 1] == S, "invalid shape of mask.");
-        need(op, V(q).dtype == OSG_F16 && V(k).dtype == OSG_F16 && V(v).dtype == OSG_F16 && V(mk).dtype == OSG_F16, "wrong data type of query.");
+        need(op, V(q).dtype == OSG_F16 && V(k).dtype == OSG_F16 && V(v).dtype == OSG_F16 && (hm || V(mk).dtype == OSG_F16), "wrong data type of query.");
         need(op, Dv == D && D % 8 == 0 && D <= 160, "head dims other than a multiple of 8 up to 160 with Dv == D are not implemented on the HIP backend.");
-        need(op, N == 1 || (!V(mk).batched && V(q).batched == V(k).batched && V(k).batched == V(v).batched), "q/k/v batching mismatch.");
+        need(op, N == 1 || (!hm && !V(mk).batched && V(q).batched == V(k).batched && V(k).batched == V(v).batched), "q/k/v batching mismatch.");
         const float scale = std::stof(*attr(op, "scale"));
         need(op, scale > 0.f, "a scale <= 0 is not implemented on the HIP backend.");
         const int y = out_val(op, Shape{Bq, Hq, T, Dv}, Lay::plain, V(q).batched);
         const long nb = Bq * B(q);
         const bool k_cap = V(P.root_of(k)).kv_cap, v_cap = V(P.root_of(v)).kv_cap;
+        if (P.decode && P.dspec.chunk > 0) {
+            // chunk plans: C query rows over the capacity buffers [Hkv][CAP][D]; the chunk's first row is the device-side dec_state[0], the causal bound
+            // is worked out from it in the kernel, so the mask operand is dropped once it is known to say the same
+            const long C = P.dspec.chunk, cap = P.dspec.cap;
+            if (!(k_cap && v_cap && T == C && Bq == 1 && nb == 1 && N == 1 && S == cap && V(k).view_off == 0 && V(v).view_off == 0)) refuse_kv_cap(op);
+            const float masked = causal_mask_value(op, hm, C, cap);
+            P.add_step("ScaledDotProductAttention(chunk) " + op.m_name, {q, k, v}, {y}, [=, this] {
+                be.check(be.api.osg_sdpa_chunk(be.ctx, OSG_F16, P.ptr(q), P.ptr(k), P.ptr(v), P.ptr(y), P.dec_state, masked, cap * D, cap * D * Hkv, cap, 1, (int)Hq,
+                                               (int)Hkv, (int)C, (int)D, scale),
+                         "ScaledDotProductAttention");
+            });
+            P.steps.back().flops = 4.0 * Hq * C * cap * D;
+            return;
+        }
         if (k_cap || v_cap) {
             // decode plans: key and value are capacity buffers [Hkv][CAP][D] (S == CAP here), the number of keys is the device-side cache length
             if (!(k_cap && v_cap && T == 1 && Bq == 1 && nb == N && !V(mk).batched && S == P.dspec.cap && V(k).view_off == 0 && V(v).view_off == 0)) refuse_kv_cap(op);
@@ -1453,11 +1494,19 @@
                 const Shape cs = V(c).shape;
                 need(op, r >= 0 && axis == 2 && rank == 4 && op.m_output.size() == 1 && P.cache_index(op.m_output[0].m_name, P.dspec.cache_out) == ci,
                      "in the device token loop a cache is concatenated with one new row along axis 2 into its output.");
-                need(op, V(r).shape == Shape{1, cs[1], 1, cs[3]} && V(r).dtype == OSG_F16 && V(c).dtype == OSG_F16 && V(r).ld == 0, "invalid shape of the new cache row.");
+                const long C = P.dspec.chunk > 0 ? P.dspec.chunk : 1;      // (a chunk plan appends its C rows from the device-side row on)
+                need(op, V(r).shape == Shape{1, cs[1], C, cs[3]} && V(r).dtype == OSG_F16 && V(c).dtype == OSG_F16 && V(r).ld == 0, "invalid shape of the new cache row.");
                 const Shape os{1, cs[1], P.dspec.cap, cs[3]};
                 check_out(op, os);
                 const int y = P.alias(c, os, Lay::plain, op.m_output[0].m_name);
                 const long Hkv = cs[1], d = cs[3], cap = P.dspec.cap;
+                if (P.dspec.chunk > 0) {
+                    need(op, N == 1, "the device prefill runs one sequence.");
+                    P.add_step("KVAppend(rows) " + op.m_name, {r, c}, {y}, [=, this] {
+                        be.check(be.api.osg_kv_append_rows_at(be.ctx, P.ptr(r), P.ptr(y), P.dec_state, (int)Hkv, (int)C, cap, (int)d), "osg_kv_append_rows_at");
+                    });
+                    return;
+                }
                 if (N > 1) {   // N sequences: each appends at the row of its own state
                     need(op, V(r).batched && V(c).batched, "in the device token loop of several sequences every sequence has a cache and a new row of its own.");
                     const long nb = N;
@@ -1471,7 +1520,7 @@
                 });
                 return;
             }
-            if (touches) throw std::runtime_error("Model::hip_generate: Concat (" + op.m_name + ") reads a key/value cache in a form the device token loop does not implement.");
+            if (touches) throw std::runtime_error(std::string(P.dec_fn()) + "Concat (" + op.m_name + ") reads a key/value cache in a form the device token loop does not implement.");
         }
         bool all_nhwc = rank == 4 && axis == 1;
         for (int x : xs) all_nhwc &= V(x).lay == Lay::nhwc;

@@ -548,9 +548,9 @@ void Plan::build() {
                 inp.staging = inp.val = new_val(iname, shape, OSG_F16, Lay::plain, true);
                 if (dec_cache) {
                     // a cache of the decode plan: [1, Hkv, CAP - 1, d] by its shape, in a buffer of CAP rows per head -- the Concat appends in place (lower_concat);
-                    // N sequences: N such buffers behind each other
-                    if (shape.size() != 4 || shape[0] != 1 || shape[2] != dspec.cap - 1)
-                        throw std::invalid_argument("Model::hip_generate: cache '" + iname + "' must be a [1, Hkv, P, d] tensor.");
+                    // N sequences: N such buffers behind each other.  (A chunk plan: CAP - C rows by its shape.)
+                    if (shape.size() != 4 || shape[0] != 1 || shape[2] != dspec.cap - (dspec.chunk > 0 ? dspec.chunk : 1))
+                        throw std::invalid_argument(std::string(dec_fn()) + "cache '" + iname + "' must be a [1, Hkv, P, d] tensor.");
                     vals[inp.val].dptr = small_alloc((size_t)N * shape[1] * dspec.cap * shape[3] * 2);
                     vals[inp.val].kv_cap = true;
                 } else

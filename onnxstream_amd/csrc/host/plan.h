@@ -10,6 +10,7 @@
 //   -> eager first pass, then capture into a hipGraph that later passes replay.
 #pragma once
 
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <functional>
@@ -163,8 +164,13 @@ struct ConstPool {
     Plan* decode_plan = nullptr;
     std::string decode_key;
     void drop_decode();          // (plan_run.cpp: Plan is incomplete here)
+    // the resident chunk plan beside it (Plan::turn): T = C rows of a prompt over caches of the same kind, keyed as the decode plan plus C
+    Plan* prefill_plan = nullptr;
+    std::string prefill_key;
+    void drop_prefill();
     void clear(HipBackend& be) {
         drop_decode();           // (first: its buffers go back to the lists freed below)
+        drop_prefill();
         for (auto& kv : base) be.free(kv.second.dptr);
         for (auto& kv : derived) be.free(kv.second.first);
         for (auto& sp : spare) be.free(sp.first);
@@ -351,7 +357,11 @@ struct Plan {
     // Built by the ordinary lowering over `build_inputs` (stand-ins for the graph inputs: one token, caches of CAP - 1 rows, a mask of CAP ones) instead of
     // m.m_data.  input_ids / position_ids are device values (Val::dev_int), the cache inputs live in capacity buffers [Hkv][CAP][d] (Val::kv_cap), a cache
     // Concat is osg_kv_append_at in place and the attention over it osg_sdpa_len: the pass is the same launches for every token and every cache length.
-    struct DecodeSpec { std::string ids, pos, mask, logits, cache_in, cache_out; int n_caches = 0; long cap = 0; };
+    // chunk plans (Plan::turn): the same build with `chunk` = C > 0 rows per pass -- stand-in caches of CAP - C rows, C tokens and positions, dec_state[0] the
+    // row the chunk starts at (osg_prefill_stage writes it); a cache Concat is osg_kv_append_rows_at, the attention osg_sdpa_chunk, which works the causal
+    // bound out of that row: the plan-time mask [C][CAP] is checked to be exactly causal and dropped.  dec_tokens holds the prompt (device int64).
+    struct DecodeSpec { std::string ids, pos, mask, logits, cache_in, cache_out; int n_caches = 0; long cap = 0; long chunk = 0; };
+    const char* dec_fn() const { return dspec.chunk > 0 ? "Model::hip_turn: " : "Model::hip_generate: "; }
     bool decode = false;
     DecodeSpec dspec;
     std::vector<Tensor>* build_inputs = nullptr;
@@ -369,9 +379,26 @@ struct Plan {
     struct SampleRule { float temperature = 0.0f; long top_k = 0; float top_p = 1.0f; unsigned long long seed = 0, draw_base = 0; };
     // batch (model_hip_generate_batch): n_seq sampled sequences from the one prompt in a decode plan of batch n_seq, sequence s with seeds[s] and its own
     // state, caches and stop; the outputs are arrays over the sequences and m_data is left untouched.  n_seq is part of the decode plan's key.
+    // entry (Plan::turn): the loop starts from what a prefill leaves on the device instead of from m_data -- caches of P rows in capacity buffers of
+    // `cap` rows per head, the logits row the first token is picked from; `prefill` enqueues that work (it starts the timer) after the loop's own
+    // uploads, so that the host waits for nothing between the first chunk and the end of the loop.  V, the shape of the logits tensor to leave, and
+    // whether cache i was device-resident come with it; nothing of it is read from m_data.
+    struct TurnEntry {
+        long P = 0, cap = 0, V = 0, min_cap = 0;
+        std::vector<std::array<long, 2>> geo;        // (Hkv, d) per cache
+        std::vector<const void*> caches;             // capacity buffers [Hkv][cap][d]
+        std::vector<char> was_resident;
+        std::vector<size_t> logits_shape;            // [1, T, V]: the rank to keep
+        std::function<const float*()> prefill;       // enqueues the chunks, returns the device address of the last real logits row
+    };
     static double generate(Model& m, const DecodeSpec& names, int max_new, long long eos_id, int sync_every, int64_t* tokens, int* n_tokens, int* stop,
-                           float* logits_trace, const SampleRule& rule, int n_seq = 1, const unsigned long long* seeds = nullptr, bool batch = false);
+                           float* logits_trace, const SampleRule& rule, int n_seq = 1, const unsigned long long* seeds = nullptr, bool batch = false,
+                           const TurnEntry* entry = nullptr);
     static std::string decode_info(Model& m);
+    // one chat turn on the device (model_hip_turn, exports.cpp states the contract): the prompt in chunks through the resident chunk plan, then the loop above
+    static double turn(Model& m, const DecodeSpec& names, const long long* prompt, int n_prompt, int chunk, long long capacity, int max_new, long long eos_id,
+                       int sync_every, int64_t* tokens, int* n_tokens, int* stop, float* logits_trace, const SampleRule& rule);
+    static std::string prefill_info(Model& m);
     // a copy of a device-resident tensor's bytes (Tensor::m_hip_resident) for the host; the tensor stays where it is (model_hip_get_tensor_f16)
     static void read_resident(Model& m, const Tensor& t, void* dst);
 

@@ -66,8 +66,10 @@ __device__ __forceinline__ float row4_sum(float v) {
 }
 
 // BKV: keys per tile (64, or 128 where registers and LDS allow: half the barriers, running-max updates and accumulator rescales per key)
-template <int DP, int DT, int QT, int BKV>
-__device__ __forceinline__ void attn_body(const AttnParams& p) {
+// CAUSAL (osg_sdpa_chunk): no mask tensor -- query row q sees the keys 0 .. cbase + q, a barred key gets the addend `cmasked` the graph's own mask
+// holds (fmaf(0 | cmasked, inv_scale, s): the arithmetic of the mask branch below on the mask osg_sdpa would be handed, hence its bits)
+template <int DP, int DT, int QT, int BKV, bool CAUSAL = false>
+__device__ __forceinline__ void attn_body(const AttnParams& p, int cbase = 0, float cmasked = 0.f) {
     constexpr int NT = BKV / 16;    // 16-key score tiles per KV tile
     constexpr int NS = BKV / 32;    // 32-deep contraction steps of P V
     constexpr int RPL = BKV / 64;   // KV rows staged per lane
@@ -183,7 +185,17 @@ __device__ __forceinline__ void attn_body(const AttnParams& p) {
         // ---- online softmax (log2 domain).  The kernel is VALU-bound here (28 MFMAs vs ~300 vector ops per tile and wave), so the
         // per-score work is kept to max / fma / v_exp_f32 / add: the scale rides in the fma (scores stay raw, max is tracked raw),
         // the kv-bound mask only exists on the last, partial tile, and exp2 is the bare hardware op (arguments are <= 0).
-        if (p.mask) {   // (not on the SD hot path: scalar f16 loads, clamped into range -- out-of-range scores are masked below anyway)
+        if constexpr (CAUSAL) {   // the compare runs on the CLAMPED indices the mask branch would load from (rows past Tq are not stored, keys past Tkv are barred below)
+#pragma unroll
+            for (int qt = 0; qt < QT; qt++) {
+                const int bound = cbase + min(q0 + qt * 16 + lq, p.Tq - 1);
+#pragma unroll
+                for (int t = 0; t < NT; t++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+                        s[qt][t][r] = fmaf(min(kv0 + t * 16 + g * 4 + r, p.Tkv - 1) <= bound ? 0.f : cmasked, p.inv_scale, s[qt][t][r]);
+            }
+        } else if (p.mask) {   // (not on the SD hot path: scalar f16 loads, clamped into range -- out-of-range scores are masked below anyway)
 #pragma unroll
             for (int qt = 0; qt < QT; qt++) {
                 const f16* mrow = p.mask + (long)min(q0 + qt * 16 + lq, p.Tq - 1) * p.Tkv;
@@ -306,6 +318,16 @@ __global__ __launch_bounds__(256) void attn_len_batch_kernel(AttnParams p, const
     const int b = blockIdx.y / p.heads;
     p.Tkv = min(max(tkv[b * tkv_stride], 1), cap);
     attn_body<DP, DT, 1, 64>(p);
+}
+
+// osg_sdpa_chunk: the body above for a chunk of C = p.Tq query rows whose first row stands at the device-side position *base (one scalar load at
+// entry), over capacity buffers: the instantiation launch_attn picks for Tq <= 512 (QT = 1, 64-key tiles) with the causal rule in the mask's place.
+// Keys are clamped to Tkv - 1 = min(base + C, cap) - 1: rows at and past base + C are not read.
+template <int DP, int DT>
+__global__ __launch_bounds__(256) void attn_chunk_kernel(AttnParams p, const int* __restrict__ base, int cap, float masked) {
+    const int b0 = max(*base, 0);
+    p.Tkv = min(b0 + p.Tq, cap);
+    attn_body<DP, DT, 1, 64, true>(p, b0, masked);
 }
 
 // =====================================================================================================================================
@@ -720,6 +742,27 @@ int dispatch_attn_len(osg_ctx* ctx, const AttnParams& p, int batch, const int* t
 }
 
 template <int DP, int DT>
+int launch_attn_chunk(osg_ctx* ctx, const AttnParams& p, int batch, const int* base, int cap, float masked) {
+    dim3 grid((p.Tq + 63) / 64, batch * p.heads);
+    osg_set_kernel(ctx, 0, 1, DP, DT, 1, 64, (int)(grid.x * grid.y));
+    hipLaunchKernelGGL((attn_chunk_kernel<DP, DT>), grid, dim3(256), 0, ctx->compute, p, base, cap, masked);
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int dispatch_attn_chunk(osg_ctx* ctx, const AttnParams& p, int batch, const int* base, int cap, float masked) {
+    const int D = p.D;
+    if (D <= 32) return launch_attn_chunk<32, 2>(ctx, p, batch, base, cap, masked);
+    if (D <= 48) return launch_attn_chunk<64, 3>(ctx, p, batch, base, cap, masked);
+    if (D <= 64) return launch_attn_chunk<64, 4>(ctx, p, batch, base, cap, masked);
+    if (D <= 80) return launch_attn_chunk<96, 5>(ctx, p, batch, base, cap, masked);
+    if (D <= 96) return launch_attn_chunk<96, 6>(ctx, p, batch, base, cap, masked);
+    if (D <= 128) return launch_attn_chunk<128, 8>(ctx, p, batch, base, cap, masked);
+    if (D <= 160) return launch_attn_chunk<160, 10>(ctx, p, batch, base, cap, masked);
+    OSG_FAIL(ctx, "osg_sdpa_chunk: head dim > 160 not implemented");
+}
+
+template <int DP, int DT>
 int launch_attn_len_batch(osg_ctx* ctx, const AttnParams& p, int batch, const int* tkv, long tkv_stride, int cap) {
     dim3 grid(1, batch * p.heads);
     osg_set_kernel(ctx, 0, 1, DP, DT, 1, 64, (int)grid.y);
@@ -827,6 +870,25 @@ int osg_sdpa_len_batch(osg_ctx* ctx, osg_dtype dtype, const void* q, const void*
     AttnParams p{(const f16*)q, (const f16*)k, (const f16*)v, (f16*)o, D, qh, qh * q_heads, D, kv_head_stride, kv_batch_stride, D, kv_head_stride,
                  kv_batch_stride, D, qh, qh * q_heads, q_heads, 1, 1, D, scale * 1.4426950408889634f, (const f16*)mask, 1.0f / scale, q_heads / kv_heads};
     return dispatch_attn_len_batch(ctx, p, batch, tkv, tkv_stride, (int)cap);
+}
+
+int osg_sdpa_chunk(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, const void* v, void* o, const int* base, float masked,
+                   long kv_head_stride, long kv_batch_stride, long cap, int batch, int q_heads, int kv_heads, int C, int D, float scale) {
+    if (dtype != OSG_F16) OSG_FAIL(ctx, "osg_sdpa_chunk: only f16 arithmetic is implemented on the device");
+    if (batch <= 0 || q_heads <= 0 || kv_heads <= 0 || D <= 0 || C <= 0 || cap <= 0 || cap > 0x7fffffffL || (long)batch * q_heads > 65535)
+        OSG_FAIL(ctx, "osg_sdpa_chunk: invalid shape of query, key or value.");
+    if (C > 512) OSG_FAIL(ctx, "osg_sdpa_chunk: a chunk holds at most 512 query rows");
+    if (q_heads % kv_heads) OSG_FAIL(ctx, "osg_sdpa_chunk: query heads must be a multiple of key/value heads.");
+    if (!q || !k || !v || !o || !base) OSG_FAIL(ctx, "osg_sdpa_chunk: null operand");
+    if (!(masked < 0.f)) OSG_FAIL(ctx, "osg_sdpa_chunk: the value of a barred key must be negative (a finite f16 value or -inf)");
+    if (!(scale > 0.f)) OSG_FAIL(ctx, "osg_sdpa_chunk: the fused kernel tracks the row maximum of the raw scores and needs scale > 0");
+    if (D % 8) OSG_FAIL(ctx, "osg_sdpa_chunk: head dim must be a multiple of 8");
+    if (kv_head_stride < cap * D || (kv_head_stride | kv_batch_stride) % 8 || (batch > 1 && kv_batch_stride < kv_head_stride * kv_heads))
+        OSG_FAIL(ctx, "osg_sdpa_chunk: the head stride must hold cap rows, strides must keep 16-byte alignment");
+    const long qh = (long)C * D;
+    AttnParams p{(const f16*)q, (const f16*)k, (const f16*)v, (f16*)o, D, qh, qh * q_heads, D, kv_head_stride, kv_batch_stride, D, kv_head_stride,
+                 kv_batch_stride, D, qh, qh * q_heads, q_heads, C, 1, D, scale * 1.4426950408889634f, nullptr, 1.0f / scale, q_heads / kv_heads};
+    return dispatch_attn_chunk(ctx, p, batch, base, (int)cap, masked);
 }
 
 int osg_attention(osg_ctx* ctx, osg_dtype dtype, const void* q, const void* k, const void* v, void* o, int heads, int Tq, int Tkv, int D,

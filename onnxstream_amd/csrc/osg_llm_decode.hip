@@ -7,7 +7,9 @@
 //                       of include/osgpu.h, then the same state advance
 //   osg_kv_append_at <- the cache Concat (pkv ++ new row, axis 2) in place: the new row of every head into a capacity buffer at the device-side row
 //   osg_decode_sample_batch, osg_kv_append_at_batch <- the same two for n_seq sequences side by side, each with its own state (model_hip_generate_batch)
-// (osg_sdpa_len, the attention over such buffers, lives next to osg_sdpa in osg_attention.hip.)
+//   osg_kv_append_rows_at, osg_prefill_stage <- the prompt's half of a chat turn (model_hip_turn): the C new rows of a prefill chunk into the capacity
+//                       buffer from the device-side row on, and the chunk's tokens, positions and first row into the staging of the chunk plan
+// (osg_sdpa_len and osg_sdpa_chunk, the attention over such buffers, live next to osg_sdpa in osg_attention.hip.)
 #include <cmath>
 #include <cstring>
 #include "osg_common.h"
@@ -433,6 +435,29 @@ __global__ __launch_bounds__(256) void kv_append_at_kernel(const uint16_t* __res
     cache[(h * cap + row) * d + e] = src[i];
 }
 
+// osg_kv_append_rows_at: one thread per 16-bit element of src [kv_heads][C][d]; a row outside [0, cap) is skipped, the others are written
+__global__ __launch_bounds__(256) void kv_append_rows_at_kernel(const uint16_t* __restrict__ src, uint16_t* __restrict__ cache, const int* __restrict__ base_p,
+                                                                int kv_heads, int C, long cap, int d) {
+    const long base = *base_p;
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long)kv_heads * C * d) return;
+    const long e = i % d, r = (i / d) % C, h = i / ((long)d * C);
+    const long row = base + r;
+    if (row < 0 || row >= cap) return;
+    cache[(h * cap + row) * d + e] = src[i];
+}
+
+// osg_prefill_stage: one workgroup; every number but the tokens is a kernel argument (the host knows where a chunk stands)
+__global__ __launch_bounds__(256) void prefill_stage_kernel(const int64_t* __restrict__ prompt, long first, long n_valid, long pos0, int C,
+                                                            int64_t* __restrict__ input_ids, int64_t* __restrict__ position_ids, int* __restrict__ base) {
+    for (int i = threadIdx.x; i < C; i += 256) {
+        const bool real = i < n_valid;
+        input_ids[i] = real ? prompt[first + i] : 0;
+        position_ids[i] = real ? pos0 + i : 0;
+    }
+    if (threadIdx.x == 0) *base = (int)pos0;
+}
+
 // top_p = pm * 2^-ps exactly, pm < 2^24 (the fp32 significand as an integer); pm = 0 says top-p is off
 void split_top_p(float top_p, uint32_t& pm, int& ps) {
     pm = 0;
@@ -508,6 +533,26 @@ int osg_kv_append_at_batch(osg_ctx* ctx, const void* src, void* cache, const int
     const long n = (long)kv_heads * d;
     hipLaunchKernelGGL(kv_append_at_batch_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)batch), dim3(256), 0, ctx->compute, (const uint16_t*)src,
                        (uint16_t*)cache, state, kv_heads, cap, d);
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int osg_kv_append_rows_at(osg_ctx* ctx, const void* src, void* cache, const int* base, int kv_heads, int C, long cap, int d) {
+    if (kv_heads <= 0 || C <= 0 || cap <= 0 || d <= 0) OSG_FAIL(ctx, "osg_kv_append_rows_at: invalid shape of the cache");
+    if (!src || !cache || !base) OSG_FAIL(ctx, "osg_kv_append_rows_at: null operand");
+    const long n = (long)kv_heads * C * d;
+    if ((n + 255) / 256 > 0x7fffffffL) OSG_FAIL(ctx, "osg_kv_append_rows_at: too many elements for one launch");
+    hipLaunchKernelGGL(kv_append_rows_at_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->compute, (const uint16_t*)src, (uint16_t*)cache, base,
+                       kv_heads, C, cap, d);
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int osg_prefill_stage(osg_ctx* ctx, const int64_t* prompt, long n_prompt, long first, long pos0, int C, int64_t* input_ids, int64_t* position_ids, int* base) {
+    if (n_prompt <= 0 || first < 0 || first >= n_prompt || C <= 0 || pos0 < 0 || pos0 + C > 0x7fffffffL) OSG_FAIL(ctx, "osg_prefill_stage: invalid chunk");
+    if (!prompt || !input_ids || !position_ids || !base) OSG_FAIL(ctx, "osg_prefill_stage: null operand");
+    const long left = n_prompt - first;
+    hipLaunchKernelGGL(prefill_stage_kernel, dim3(1), dim3(256), 0, ctx->compute, prompt, first, left < C ? left : (long)C, pos0, C, input_ids, position_ids, base);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }

@@ -31,6 +31,7 @@ EXPORTS = [
     "osg_sampler_prepare_single", "osg_sampler_euler_a_single", "osg_sampler_multistep_single", "osg_sampler_cfg_stochastic", "osg_sampler_stochastic_single",
     "osg_decode_gather", "osg_decode_blend", "osg_decode_pick", "osg_decode_sample", "osg_kv_append_at", "osg_sdpa_len",
     "osg_decode_sample_batch", "osg_kv_append_at_batch", "osg_sdpa_len_batch", "osg_rope_batch",
+    "osg_sdpa_chunk", "osg_kv_append_rows_at", "osg_prefill_stage",
     "osg_range_push", "osg_range_pop", "osg_marker_record", "osg_copy_wait_marker", "osg_timer_mark", "osg_timer_between", "osg_set_stat_sinks", "osg_group_norm_stats_nhwc", "osg_qu8_conv2d_nhwc", "osg_qu8_conv2d_nhwc_t", "osg_qu8_conv_tap_sums", "osg_qu8_gemm", "osg_qu8_lut", "osg_qu8_binary", "osg_qu8_instance_norm", "osg_qu8_instance_norm_nhwc", "osg_qu8_affine_act", "osg_qu8_norm_affine_act_nhwc", "osg_qu8_softmax_last", "osg_kdbg_read",
     "osg_tblock_tail_supported", "osg_tblock_tail", "osg_tblock_kv_pack_elems", "osg_tblock_kv_pack_jobs", "osg_tblock_pack_weight", 
 ]
@@ -140,6 +141,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.osg_kv_append_at_batch.argtypes = [vp, vp, vp, vp, ci, ci, cl, ci]
         lib.osg_sdpa_len_batch.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, cl, cl, cl, cl, ci, ci, ci, ci, cf]
         lib.osg_rope_batch.argtypes = [vp, ci, vp, vp, vp, vp, cl, cl, cl, ci]
+    if hasattr(lib, "osg_sdpa_chunk"):
+        lib.osg_sdpa_chunk.argtypes = [vp, ci, vp, vp, vp, vp, vp, cf, cl, cl, cl, ci, ci, ci, ci, ci, cf]
+        lib.osg_kv_append_rows_at.argtypes = [vp, vp, vp, vp, ci, ci, cl, ci]
+        lib.osg_prefill_stage.argtypes = [vp, vp, cl, cl, cl, ci, vp, vp, vp]
     lib.osg_set_stat_sinks.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, ci]
     lib.osg_group_norm_stats_nhwc.argtypes = [vp, vp, vp, vp, vp, ci, ctypes.c_long, ci, ci, cf, ci, vp]
     lib.osg_qu8_conv2d_nhwc.argtypes = [vp, vp, cf, ci, vp, cf, ci, vp, cf, ci, vp] + [ci] * 13
@@ -510,6 +515,28 @@ class Gpu:
         self._ck(self.lib.osg_sdpa_len(self.ctx, _NP2DT[q.dtype], q.ptr, k.ptr, v.ptr, self._p(mask), o.ptr, state.ptr + 4, cap * d, cap * d * hkv, cap, bsz, hq, hkv,
                                        d, scale))
         return o
+
+    def sdpa_chunk(self, q: DevBuf, k: DevBuf, v: DevBuf, base: DevBuf, masked: float, scale: float, out: Optional[DevBuf] = None):
+        """osg_sdpa_chunk: q:[B,Hq,C,D], k,v: capacity buffers [B,Hkv,CAP,D]; query row i sees the keys 0 .. base[0] + i (base: device int32), a barred key
+        gets the addend `masked`; None for `base` passes a null pointer (refused)"""
+        bsz, hq, c, d = q.shape
+        hkv, cap = k.shape[1], k.shape[2]
+        assert base is None or base.dtype == np.int32
+        o = self._out(out, q.shape, q.dtype)
+        self._ck(self.lib.osg_sdpa_chunk(self.ctx, _NP2DT[q.dtype], q.ptr, k.ptr, v.ptr, o.ptr, self._p(base), float(masked), cap * d, cap * d * hkv, cap, bsz, hq,
+                                         hkv, c, d, scale))
+        return o
+
+    def kv_append_rows_at(self, src: DevBuf, cache: DevBuf, base: DevBuf):
+        """osg_kv_append_rows_at: src f16 [Hkv, C, d] into cache [Hkv, CAP, d] from row base[0] on (device int32), in place"""
+        hkv, cap, d = cache.shape
+        assert src.shape[0] == hkv and src.shape[2] == d and base.dtype == np.int32
+        self._ck(self.lib.osg_kv_append_rows_at(self.ctx, src.ptr, cache.ptr, base.ptr, hkv, src.shape[1], cap, d))
+
+    def prefill_stage(self, prompt: DevBuf, first: int, pos0: int, ids: DevBuf, pos: DevBuf, base: DevBuf):
+        """osg_prefill_stage: ids / pos int64 [C] from prompt int64 [n] at `first` and positions pos0 .., zeros behind the prompt's end; base[0] = pos0"""
+        assert prompt.dtype == ids.dtype == pos.dtype == np.int64 and base.dtype == np.int32 and ids.size == pos.size
+        self._ck(self.lib.osg_prefill_stage(self.ctx, prompt.ptr, prompt.size, int(first), int(pos0), ids.size, ids.ptr, pos.ptr, base.ptr))
 
     def kv_append_at(self, src: DevBuf, cache: DevBuf, state: DevBuf):
         """osg_kv_append_at: src f16 [Hkv, d] into cache [Hkv, CAP, d] at row state[0] (device int32[4]), in place"""

@@ -222,6 +222,20 @@ def generate(m, cfg: LlamaConfig, max_new: int, eos_id: int = -1, sync_every: in
                       draw_base=draw_base)
 
 
+def turn(m, cfg: LlamaConfig, prompt, max_new: int, chunk: int = 32, capacity: int = 0, eos_id: int = -1, sync_every: int = 0, trace: bool = False,
+         temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, draw_base: int = 0, first: bool = False):
+    """One chat turn (src/llm.cpp:456-497) on the device: `prompt` in chunks of `chunk` tokens over the caches the Model holds, then the token loop of
+    `generate`, in one call without a host round trip (bindings.Model.turn).  first: push the app's zero-length caches pkv* (its first turn, :400-412);
+    otherwise the opkv* a forward_resident, a generate or a turn left are carried on.  Returns (tokens, stop, logits trace or None, device ms)."""
+    if first:
+        m.set_use_fp16_arithmetic(False)
+        for i in range(2 * cfg.layers):
+            m.add_tensor(f"pkv{i}", np.zeros((1, cfg.kv_heads, 0, cfg.head_dim), np.float32))
+    m.set_use_fp16_arithmetic(True)
+    return m.turn(prompt, max_new, 2 * cfg.layers, chunk=chunk, capacity=capacity, eos_id=eos_id, sync_every=sync_every, trace=trace, vocab=cfg.vocab,
+                  temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, draw_base=draw_base)
+
+
 def generate_batch(m, cfg: LlamaConfig, n_seq: int, max_new: int, eos_id: int = -1, sync_every: int = 0, trace: bool = False, temperature: float = 1.0,
                    top_k: int = 0, top_p: float = 1.0, seeds=None, seed: int = 0, draw_base: int = 0):
     """n_seq sampled continuations of the prompt in one call (bindings.Model.generate_batch), after a forward_resident(..., keep_logits=True) over it.  The

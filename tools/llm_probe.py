@@ -6,7 +6,10 @@ by that rule, then osg_decode_sample alone at V = 32000 and 128256; each option 
 (profiles/llm_generate_sampled_probe.txt: --temperature 0.8,1 --top-k 40,0 --top-p 0.9,0.95).
 --generate --sequences N[,N...] [--temperature T] [--top-k K] [--top-p P] [--seed S]: the single sampled loop (Model.generate) as the baseline, then
 Model.generate_batch with each N, 64 tokens per sequence after the 32-token prefill, all in one process: ms per pass and tokens per second
-(profiles/llm_generate_batch_probe.txt: --sequences 1,2,4,8,16 --temperature 0.8 --top-k 40 --top-p 0.9)."""
+(profiles/llm_generate_batch_probe.txt: --sequences 1,2,4,8,16 --temperature 0.8 --top-k 40 --top-p 0.9).
+--turn: two chat turns of 32 prompt tokens and 64 generated tokens each, chunk 32: Model.turn (prefill and loop on the device, one call per turn) against
+forward_resident + Model.generate on the same tokens, three conversations each way in one process: wall and device ms per turn, plans built
+(profiles/llm_turn_probe.txt)."""
 import os, sys, time, tempfile
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -188,6 +191,63 @@ def batch_leg(n_list, rule, seed, n_new=64):
     single("warm, fourth")
     m.close()
 
+
+def turn_leg(n_prompt=32, n_new=64, chunk=32, repeats=3):
+    """--turn: two chat turns (n_prompt prompt tokens then n_new generated, twice) through Model.turn against forward_resident + Model.generate on the
+    same tokens, in one process: wall and device ms per turn, and the plans each way builds.  Every way runs `repeats` conversations; the spread
+    between two repeats of the baseline is the noise the difference is read against."""
+    rng = np.random.default_rng(0)
+    prompts = [[int(t) for t in rng.integers(0, cfg.vocab, n_prompt)] for _ in range(2)]
+    m = Model(b.LIB_HOST, 0, "ram+nocache")
+    m._set_option("hip_autotune", 0)
+    m._set_option("hip_resident_outputs", 1)
+    m.add_outputs_convert("logits")
+    llama.configure(m, cfg, d, sdpa=True, upcast=True)
+    llama.forward_resident(m, cfg, [1], True, 0)      # the weight-loading pass
+    capacity = 2 * (n_prompt + n_new)
+
+    def baseline():
+        m.clear_tensors()
+        P, out, walls, devs = 0, [], [], []
+        for k, prompt in enumerate(prompts):
+            t0 = time.perf_counter()
+            llama.forward_resident(m, cfg, prompt, k == 0, P, keep_logits=True)
+            dev = m.hip_last_pass_ms()
+            toks, stop, _, ms = llama.generate(m, cfg, n_new)
+            walls.append((time.perf_counter() - t0) * 1e3)
+            devs.append(dev + ms)
+            m.drop_tensor("logits")
+            P += len(prompt) + len(toks)
+            out.append([int(t) for t in toks])
+        return out, walls, devs
+
+    def device():
+        m.clear_tensors()
+        out, walls, devs = [], [], []
+        for k, prompt in enumerate(prompts):
+            t0 = time.perf_counter()
+            toks, stop, _, ms = llama.turn(m, cfg, prompt, n_new, chunk=chunk, capacity=capacity, first=k == 0)
+            walls.append((time.perf_counter() - t0) * 1e3)
+            devs.append(ms)
+            out.append([int(t) for t in toks])
+        return out, walls, devs
+
+    ref = None
+    for name, leg in (("forward_resident + generate", baseline), ("turn", device)):
+        for r in range(repeats):
+            built = m.hip_plans_built()
+            toks, walls, devs = leg()
+            ref = ref or toks
+            same = sum(int(a == c) for x, y in zip(toks, ref) for a, c in zip(x, y))
+            print(f"{name}, repeat {r}: turn 1 wall {walls[0]:.1f} ms device {devs[0]:.1f} ms; turn 2 wall {walls[1]:.1f} ms device {devs[1]:.1f} ms; "
+                  f"{sum(len(t) for t in toks)} tokens, {same} equal the first baseline's; plans built {m.hip_plans_built() - built}", flush=True)
+    print(m.hip_prefill_plan_info().splitlines()[0] + "; " + m.hip_decode_plan_info().splitlines()[0], flush=True)
+    m.close()
+
+
+if "--turn" in sys.argv:
+    turn_leg()
+    sys.exit(0)
 
 if "--generate" in sys.argv:
     temps = _option("--temperature", None, float)
