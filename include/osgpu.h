@@ -149,6 +149,18 @@ int osg_conv2d_nhwc_v(osg_ctx* ctx, osg_dtype dtype, const void* x, const void* 
                       int Cin, int Cout, int KH, int KW, int stride_h, int stride_w, int pad_top, int pad_left, int pad_bottom, int pad_right,
                       osg_act act);
 
+/* A 3x3 / stride 1 / pad 1 convolution and a 1x1 convolution of a second tensor as ONE contraction (a ResNet's conv2 and its conv_shortcut):
+ *   y = act( f16( conv3x3(x, w_ohwi) + x2 . w2^T + bias ) )
+ * x [N,H,W,Cin], w_ohwi [Cout,3,3,Cin]; x2 [N,H,W,Cin2] NHWC, w2 [Cout][Cin2] (a 1x1 OHWI weight); bias_f32 [Cout] FLOAT (NULL = none): the caller adds the two
+ * convolutions' biases in f32.  The K dimension is 9 * Cin + Cin2, accumulated in f32 by one workgroup per tile and rounded once -- the intermediate tensor of
+ * the 1x1 convolution, its launch and its f16 rounding do not exist.  Output views and statistics sinks as in osg_conv2d_nhwc_v.
+ * Runs the halo-reuse kernel only and fails (osg_last_error) for a shape it does not take: W in {8, 16, 32, 64}, whole 128-pixel tiles (H % (128 / W) == 0; at
+ * W = 8: H = 8), Cin % 64 == 0, Cin2 % 64 == 0, Cout % 4 == 0, operands 16-byte aligned and below 2 GiB.  osg_last_route reports family 4. */
+int osg_conv2d_nhwc_cat(osg_ctx* ctx, const void* x, const void* w_ohwi, const void* x2, const void* w2, int Cin2, const float* bias_f32, void* y, long y_ld,
+                        void* y2, long y2_ld, int N, int H, int W, int Cin, int Cout, osg_act act);
+/* the number of kernel instantiations behind osg_conv2d_nhwc_cat (tests walk them through the OSG_CONV3X3_BN / _NL overrides and osg_last_route) */
+int osg_conv3x3_cat_entries(void);
+
 /* C[b] = act(A[b] (MxK, row-major, lda) * B[b] + bias + residual).  B is [K,N] row-major (b_is_nk=0, the layout
  * XNN_FLAG_TRANSPOSE_WEIGHTS gives the reference, onnxstream.cpp:977,1136) or pre-transposed [N,K] (b_is_nk=1, how
  * resident weights are kept on the device).  stride_* are element strides between batch items (0 = broadcast).
@@ -200,7 +212,8 @@ int osg_gemm_ln(osg_ctx* ctx, const void* x, const void* w_nk_folded, const floa
 int osg_gemm_rowstats(osg_ctx* ctx, const void* A, const void* B_nk, const void* bias, osg_dtype bias_dtype, const void* residual, void* C,
                       int M, int N, int K, osg_act act, float* rowstats);
 /* What the most recent contraction call on ctx ran (a host-side record, no device work; a tuner's timed candidates count as calls):
- *   out[0] family: 0 gemm2_kernel, 1 conv3x3_kernel, 2 gemm_kernel (round 1), 3 conv_cin4_mfma_kernel; -1 none yet
+ *   out[0] family: 0 gemm2_kernel, 1 conv3x3_kernel, 2 gemm_kernel (round 1), 3 conv_cin4_mfma_kernel, 4 conv3x3_cat_kernel (osg_conv2d_nhwc_cat; out[1] indexes
+ *          the entry list of osg_conv3x3_cat.hip); -1 none yet
  *   out[1] instantiation: the index into kV2Entries (family 0) / kV3Entries (family 1) of osg_gemm_routes.h; family 2: tile | vec << 2 | conv << 3, tile
  *          0 = 128 x 128, 1 = 128 x 64, 2 = 64 x 64; family 3: 0
  *   out[2] the k-slices that ran;  out[3] 1 = the split was folded in the kernel

@@ -277,6 +277,7 @@ void model_set_option(Handle* h, char* name, unsigned int value) {
     else if (n == "hip_fuse_ln_gemm") m.m_hip_fuse_ln_gemm = b;
     else if (n == "hip_concat_views") m.m_hip_concat_views = b;
     else if (n == "hip_fuse_tblock") m.m_hip_fuse_tblock = b;
+    else if (n == "hip_fuse_shortcut") Plan::plan_options(m).fuse_shortcut = b;
     else if (n == "hip_gn_stats") m.m_hip_gn_stats = (int)value;
     else if (n == "hip_loop_hoist") Plan::loop_options(m).hoist = b;
     else if (n == "hip_loop_hoist_rows") Plan::loop_options(m).rows = (int)value;

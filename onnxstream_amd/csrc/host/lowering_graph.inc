@@ -390,6 +390,7 @@
             if (has_type("osg.SiLU")) { index_graph(); cse_silu(); }
             if (has_type("osg.SiLU") && has_type("Gemm")) { index_graph(); fuse_gemm_act(); }   // (after the CSE: the 22 SiLUs behind the time embedding are one by now)
             if (has_type("Conv")) { index_graph(); fuse_image_bias(); }
+            if (P.fuse_shortcut && has_type("Conv")) { index_graph(); fuse_conv_shortcut(); }   // (behind fuse_residual, and behind the passes that may still mark either Conv)
         } else if (m.m_fuse_ops_in_attention && has_type("Softmax")) {
             index_graph(); fuse_attention(false);
         }
@@ -1129,6 +1130,8 @@
             ops()[ad] = std::move(f);
         }
     }
+
+    // (fuse_conv_shortcut, the pass behind hip_fuse_shortcut, is defined next to lower_conv in lowering_ops.inc: the two share the fused op's input layout)
 
     // Conv(..) -> osg.SiLU  ==> the activation rides in the convolution's epilogue (the Conv -> Sigmoid -> Mul triple of every block of
     // the exported YOLOv8 graphs; in the SD UNet SiLU follows the GroupNorms instead)

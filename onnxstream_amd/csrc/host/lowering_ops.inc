@@ -141,13 +141,73 @@
     std::map<int, ConvProducer> conv_producers;   // root val of a convolution's output -> its step
     std::set<size_t> viewed_steps;                // steps whose destinations were redirected (their launch must stay the view-aware one)
 
+    // Conv 3x3 (h) with osg_residual = the sole use of Conv 1x1 (x)  ==> ONE contraction over K = 9 C + Cin2 (osg_conv2d_nhwc_cat): a ResNet's conv2 and its
+    // conv_shortcut.  The 1x1 convolution dies; the 3x3 one gains (x, Ws, bs) behind its own three inputs and the mark osg_shortcut; lower_conv adds the two
+    // biases up in f32 on the host.  Only where the halo kernel's entry takes the shape (conv_cat_takes) and both weights are resident f16 constants.
+    static bool conv_cat_takes(long H, long W, long Cin, long Cin2, long Cout) {
+        if (!(W == 8 || W == 16 || W == 32 || W == 64)) return false;
+        const long TI = W == 8 ? 2 : 1, TH = 128 / (W * TI);
+        if (H % TH || (W == 8 && H != 8)) return false;
+        return Cin > 0 && Cin2 > 0 && Cin % 64 == 0 && Cin2 % 64 == 0 && Cout % 4 == 0;
+    }
+    // kernel / stride / pad / dilation / group of a Conv: all strides == st, all pads == pd, no dilation, no groups
+    bool conv_plain_geometry(const Operation& op, int st, int pd) const {
+        bool ok = true;
+        for (auto& a : op.m_attributes) {
+            if (a.first == "pads") { for (int v : int_list(a.second)) ok = ok && v == pd; }
+            else if (a.first == "strides") { for (int v : int_list(a.second)) ok = ok && v == st; }
+            else if (a.first == "dilations") { for (int v : int_list(a.second)) ok = ok && v == 1; }
+            else if (a.first == "group") ok = ok && std::stoi(a.second) == 1;
+        }
+        if (pd != 0 && !attr(op, "pads")) ok = false;
+        return ok;
+    }
+    void fuse_conv_shortcut() {
+        if (!P.fuse_shortcut || P.stream_weights || P.w8_resident) return;
+        for (size_t i = 0; i < ops().size(); i++) {
+            if (!is((int)i, "Conv")) continue;
+            Operation& op = ops()[i];
+            if (!attr(op, "osg_residual") || attr(op, "osg_image_bias") || attr(op, "osg_shortcut") || op.m_input.size() != 4 || op.m_output.size() != 1) continue;
+            const Val* w = cval(op.m_input[1]);
+            if (!w || w->dtype != OSG_F16 || w->shape.size() != 4 || w->shape[2] != 3 || w->shape[3] != 3 || !conv_plain_geometry(op, 1, 1)) continue;
+            const int sc = prod_of(op.m_input[3]);
+            if (!is(sc, "Conv") || sc == (int)i || use_count(op.m_input[3].m_name) != 1) continue;
+            const Operation& so = ops()[sc];
+            if (attr(so, "osg_residual") || attr(so, "osg_image_bias") || attr(so, "osg_act") || attr(so, "osg_shortcut") || so.m_output.size() != 1) continue;
+            if (so.m_input.size() < 2 || so.m_input.size() > 3 || !act(so.m_input[0]) || !act(op.m_input[0])) continue;
+            const Val* ws = cval(so.m_input[1]);
+            if (!ws || ws->dtype != OSG_F16 || ws->shape.size() != 4 || ws->shape[2] != 1 || ws->shape[3] != 1 || !conv_plain_geometry(so, 1, 0)) continue;
+            const auto& hs = op.m_input[0].m_shape;
+            const auto& xs = so.m_input[0].m_shape;
+            if (hs.size() != 4 || xs.size() != 4 || hs[0] != 1 || xs[0] != 1 || hs[2] != xs[2] || hs[3] != xs[3]) continue;
+            const long C = (long)hs[1], Cin2 = (long)xs[1], Cout = w->shape[0];
+            if (w->shape[1] != C || ws->shape[1] != Cin2 || ws->shape[0] != Cout || !conv_cat_takes((long)hs[2], (long)hs[3], C, Cin2, Cout)) continue;
+            // both biases (where present) must be readable at plan time: [Cout] constants
+            auto bias_ok = [&](const Operation& o) {
+                if (o.m_input.size() < 3 || o.m_input[2].m_name.empty()) return true;
+                const Val* b = cval(o.m_input[2]);
+                return b && b->host_valid && (long)b->host_f.size() == Cout;
+            };
+            if (!bias_ok(op) || !bias_ok(so)) continue;
+            const Tensor none;
+            op.m_input[3] = so.m_input[0];
+            op.m_input.push_back(so.m_input[1]);
+            op.m_input.push_back(so.m_input.size() > 2 ? so.m_input[2] : none);
+            for (auto it = op.m_attributes.begin(); it != op.m_attributes.end(); ++it)
+                if (it->first == "osg_residual") { op.m_attributes.erase(it); break; }
+            op.m_attributes.emplace_back("osg_shortcut", "1");
+            dead[sc] = 1;
+        }
+    }
+
     struct Conv1dOut { int y = -1; long Cout = 0, Lo = 0; } conv1d_out;
     void lower_conv(const Operation& op) {
         const bool has_res = attr(op, "osg_residual") != nullptr;
         const bool has_ib = attr(op, "osg_image_bias") != nullptr;
         const osg_act cact = attr(op, "osg_act") ? OSG_ACT_SILU : OSG_ACT_NONE;
         const size_t nin = op.m_input.size();
-        need(op, nin == 2 || nin == 3 || (has_res && nin == 4) || (has_ib && nin == 5), "wrong number of inputs.");
+        const bool has_sc = attr(op, "osg_shortcut") != nullptr;   // fuse_conv_shortcut: inputs (h, W, b | -, x, Ws, bs | -)
+        need(op, has_sc ? (nin == 6 && !has_res && !has_ib) : (nin == 2 || nin == 3 || (has_res && nin == 4) || (has_ib && nin == 5)), "wrong number of inputs.");
         need(op, op.m_output.size() == 1, "wrong number of outputs.");
         std::vector<int> dil = {1, 1}, ks, pads = {0, 0, 0, 0}, strides = {1, 1};
         int group = 1;
@@ -157,7 +217,7 @@
             else if (a.first == "kernel_shape") ks = int_list(a.second);
             else if (a.first == "pads") pads = int_list(a.second);
             else if (a.first == "strides") strides = int_list(a.second);
-            else if (a.first == "osg_residual" || a.first == "osg_image_bias" || a.first == "osg_act") {}
+            else if (a.first == "osg_residual" || a.first == "osg_image_bias" || a.first == "osg_act" || a.first == "osg_shortcut") {}
             else throw std::invalid_argument(op.m_type + ": unrecognized attribute: " + a.first + ".");
         }
         int x = in_val(op.m_input[0]);
@@ -215,7 +275,43 @@
         if (is1d) conv1d_out = Conv1dOut{y, Cout, Ho};   // (lower() hands the [1, O, Lo, 1] result on as the graph's [1, O, Lo] once the launch is planned)
         const long nb = B(x);
         const int sh = strides[0], sw = strides[1];
+        // fuse_conv_shortcut: the 1x1 convolution of x2 rides as a second K segment of this launch (osg_conv2d_nhwc_cat); the two biases, both constants of the
+        // model, meet in f32 on the host, once, and reach the epilogue as one f32 vector
+        int x2 = -1, w2 = -1;
+        long Cin2 = 0;
+        if (has_sc) {
+            x2 = P.ensure_nhwc(in_val(op.m_input[3]));
+            w2 = in_val(op.m_input[4]);
+            const Shape x2s = V(x2).shape, w2s = V(w2).shape;
+            need(op, KH == 3 && KW == 3 && sh == 1 && sw == 1 && pt == 1 && pl == 1 && pb == 1 && pr == 1 && V(w).dtype == OSG_F16, "a fused shortcut needs a 3x3 / stride 1 / pad 1 convolution with f16 weights.");
+            need(op, x2s.size() == 4 && x2s[0] == 1 && x2s[2] == H && x2s[3] == W && V(x2).batched == V(x).batched, "invalid shape of the shortcut's input.");
+            Cin2 = x2s[1];
+            need(op, V(w2).is_const && V(w2).dtype == OSG_F16 && V(w2).lay == Lay::nhwc && w2s == Shape{Cout, Cin2, 1, 1}, "invalid shape of the shortcut's weights.");
+            std::vector<float> sum((size_t)Cout, 0.f);
+            // the derived constant's tag names both source tensors and the length: Plan::const_alloc hands the SAME buffer to equal tags (and replaces a buffer
+            // whose size differs), so two fused pairs may share one only where they add up the same two vectors
+            std::string tag = "shortcut_bias|" + std::to_string(Cout);
+            int present = 0;
+            for (int bi : {2, 5}) {
+                if (op.m_input[bi].m_name.empty()) { tag += "|-"; continue; }
+                const Val& b = V(in_val(op.m_input[bi]));
+                need(op, b.host_valid && (long)b.host_f.size() == Cout, "invalid shape of bias.");
+                for (long c = 0; c < Cout; c++) sum[c] += b.host_f[c];
+                tag += "|" + b.name;
+                present++;
+            }
+            bias = -1;                                      // neither convolution has a bias: the launch takes none (no derived constant)
+            if (present) {
+                bias = P.new_val("", {Cout}, OSG_F32, Lay::plain, false);
+                V(bias).is_const = true;
+                V(bias).name = tag;
+                bool fresh;
+                V(bias).dptr = P.const_alloc(tag, (size_t)Cout * 4, &fresh);
+                if (fresh) be.check(be.api.osg_upload_sync(be.ctx, V(bias).dptr, sum.data(), sum.size() * 4), "osg_upload_sync");
+            }
+        }
         std::vector<int> reads = {x, w};
+        if (has_sc) { reads.push_back(x2); reads.push_back(w2); }
         if (bias >= 0) reads.push_back(bias);
         if (res >= 0) reads.push_back(res);
         if (ib >= 0) reads.push_back(ib);
@@ -226,7 +322,7 @@
         const int qz = w8 ? V(w).qzp : 0;
         auto co = std::make_shared<ConvOut>();
         co->dst = y;
-        P.add_step((w8 ? "Conv w8 " : "Conv ") + op.m_name, reads, {y}, [=, this] {
+        P.add_step((w8 ? "Conv w8 " : "Conv ") + op.m_name + (has_sc ? " +shortcut" : ""), reads, {y}, [=, this] {
             const ConvOut& o = *co;
             if (o.sink[0].off >= 0 || o.sink[1].off >= 0)
                 be.check(be.api.osg_set_stat_sinks(be.ctx, o.sink[0].off >= 0 ? P.gn_stats + o.sink[0].off : nullptr, o.sink[0].groups, o.sink[0].cpg, o.sink[0].ch_off,
@@ -239,6 +335,10 @@
                                                      o.dst2 >= 0 ? (char*)P.ptr(o.dst2) + o.dst2_off : nullptr, o.dst2_ld, (int)nb, (int)H, (int)W, (int)Cin,
                                                      (int)Cout, (int)KH, (int)KW, sh, sw, pt, pl, pb, pr, cact),
                          "Conv");
+            else if (has_sc)
+                be.check(be.api.osg_conv2d_nhwc_cat(be.ctx, P.ptr(x), P.ptr(w), P.ptr(x2), P.ptr(w2), (int)Cin2, bias >= 0 ? (const float*)P.ptr(bias) : nullptr, (char*)P.ptr(o.dst) + o.dst_off, o.dst_ld,
+                                                    o.dst2 >= 0 ? (char*)P.ptr(o.dst2) + o.dst2_off : nullptr, o.dst2_ld, (int)nb, (int)H, (int)W, (int)Cin, (int)Cout, cact),
+                         "Conv +shortcut");
             else
             be.check(be.api.osg_conv2d_nhwc_v(be.ctx, OSG_F16, P.ptr(x), P.ptr(w), bias >= 0 ? P.ptr(bias) : nullptr,
                                               bias >= 0 ? P.vals[bias].dtype : OSG_F16, ib >= 0 ? P.ptr(ib) : nullptr, ib_ld,
@@ -247,7 +347,7 @@
                                               (int)KH, (int)KW, sh, sw, pt, pl, pb, pr, cact),
                      "Conv");
         });
-        P.steps.back().flops = 2.0 * nb * Ho * Wo * Cout * KH * KW * Cin;
+        P.steps.back().flops = 2.0 * nb * Ho * Wo * Cout * (KH * KW * Cin + Cin2);
         if (V(w).dtype == OSG_F16 || w8) conv_producers[P.root_of(y)] = ConvProducer{P.steps.size() - 1, co, y};
         if (KH == 1 && KW == 1 && sh == 1 && sw == 1 && ph == 0 && pw == 0 && ib < 0 && cact == OSG_ACT_NONE)   // a 1x1 convolution IS a GEMM over the pixels (OHWI == [N,K])
             if (!w8) note_rs_producer(x, w, bias, res, y, nb * Ho * Wo, Cout, Cin);

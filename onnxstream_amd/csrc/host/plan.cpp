@@ -96,6 +96,7 @@ Plan::Plan(Model& model, HipBackend& backend, ConstPool& cpool, size_t batch) : 
     fuse_ln_gemm = m.m_hip_fuse_ln_gemm;
     concat_views = m.m_hip_concat_views;
     fuse_tblock = m.m_hip_fuse_tblock;
+    fuse_shortcut = pool.opts.fuse_shortcut;
     loop_hoist = pool.loop.hoist;
     loop_hoist_rows = pool.loop.rows;
     gn_stats_req = m.m_hip_gn_stats;
@@ -122,7 +123,7 @@ bool Plan::compatible(Model& mm, size_t batch) const {
     const bool want_stream = mm.m_hip_stream_weights || mm.m_cuda_options.m_vram_to_use > 0;
     if ((long)batch != N) return no("batch size");
     if (mm.m_use_fp16_arithmetic != fp16 || mm.m_use_uint8_arithmetic != u8 || mm.m_use_uint8_qdq != u8_qdq) return no("arithmetic type");
-    if (mm.m_hip_fusion_level != fusion_req || mm.m_hip_fuse_ln_gemm != fuse_ln_gemm || mm.m_hip_concat_views != concat_views || mm.m_hip_fuse_tblock != fuse_tblock || mm.m_hip_gn_stats != gn_stats_req ||
+    if (mm.m_hip_fusion_level != fusion_req || mm.m_hip_fuse_ln_gemm != fuse_ln_gemm || mm.m_hip_concat_views != concat_views || mm.m_hip_fuse_tblock != fuse_tblock || pool.opts.fuse_shortcut != fuse_shortcut || mm.m_hip_gn_stats != gn_stats_req ||
         mm.m_fuse_ops_in_attention != fuse_attn || mm.m_use_scaled_dp_attn_op != sdp_attn || mm.m_hip_autotune != autotune)
         return no("fusion / tuning options");
     if (pool.loop.hoist != loop_hoist || (long)pool.loop.rows != loop_hoist_rows) return no("loop hoist option");
@@ -459,7 +460,7 @@ void Plan::build() {
     const bool cacheable = m.m_support_dynamic_shapes && !stream_weights && !budgeted;
     if (cacheable) {
         key = std::to_string(fusion) + "|" + std::to_string(m.m_hip_fusion_level) + (u8 ? "|u8" : "|f") + (fp16 ? "h" : "-") + (w8_resident ? "8" : "-") + (fuse_attn ? "a" : "-") +
-              (sdp_attn ? "s" : "-") + (fuse_ln_gemm ? "l" : "-") + "|" + std::to_string(m.m_attention_fused_ops_parts) + "|" + std::to_string(m.m_ops.size()) + "|";
+              (sdp_attn ? "s" : "-") + (fuse_ln_gemm ? "l" : "-") + (fuse_shortcut ? "c" : "-") + "|" + std::to_string(m.m_attention_fused_ops_parts) + "|" + std::to_string(m.m_ops.size()) + "|";
         for (auto& e : extra_outputs) key += e + ",";
         key += "|";
         if (m.m_requires_upcast)

@@ -159,6 +159,14 @@ struct ConstPool {
         unsigned long long schedule_serial = 0;
     };
     LoopOptions loop;
+    // planner options added after the reference application was compiled against onnxstream.h (which therefore stays as it is), reached through Plan::plan_options.
+    // Not touched by clear() either
+    struct PlanOptions {
+        // hip_fuse_shortcut: a ResNet's 1x1 conv_shortcut runs as a second K segment of its 3x3 conv2 (osg_conv2d_nhwc_cat), no launch of its own.  Off by
+        // default: the output loses one f16 rounding, so its bits are not the un-fused plan's
+        bool fuse_shortcut = false;
+    };
+    PlanOptions opts;
     // the resident decode plan of the Model (Plan::generate): T = 1 over key/value caches of a fixed capacity, kept across generate calls while the
     // capacity and the options it was built with (`decode_key`) still fit
     Plan* decode_plan = nullptr;
@@ -437,6 +445,7 @@ struct Plan {
     // the input epoch, filled table rows (all 0 before the first loop call and with the option off, but the epoch), and hoist_info() of the Model's plan.
     // Static members of Plan for the reason given at on_plan_of
     static ConstPool::LoopOptions& loop_options(Model& m);
+    static ConstPool::PlanOptions& plan_options(Model& m);
     static void sampler_schedule(Model& m, const float* t, size_t n);
     static void loop_hoist_stats(Model& m, unsigned long long out[8]);
     static std::string loop_hoist_info(Model& m);
@@ -461,6 +470,7 @@ struct Plan {
     bool fuse_ln_gemm = false;
     bool concat_views = true;     // m_hip_concat_views
     bool fuse_tblock = true;      // m_hip_fuse_tblock
+    bool fuse_shortcut = false;   // hip_fuse_shortcut (ConstPool::PlanOptions)
     bool in_flight = false;       // a pass of this plan may still be running on the device (set while execute() / replay() are between enqueue and wait)
     bool gn_stats_on = false;
     int gn_stats_req = 2;          // m_hip_gn_stats as requested (0 off, 1 all eligible, 2 large tensors only)

@@ -639,6 +639,11 @@ ConstPool::LoopOptions& Plan::loop_options(Model& m) {
     return m.m_pool->loop;
 }
 
+ConstPool::PlanOptions& Plan::plan_options(Model& m) {
+    if (!m.m_pool) m.m_pool = new ConstPool();
+    return m.m_pool->opts;
+}
+
 void Plan::sampler_schedule(Model& m, const float* t, size_t n) {
     if (n && !t) throw std::invalid_argument("model_hip_sampler_schedule: no timestep values given.");
     ConstPool::LoopOptions& o = loop_options(m);

@@ -2,6 +2,7 @@
 // (uint8 weight codes resident, WQ = 1).  The description is at the top of osg_conv3x3.hip.
 #pragma once
 #include "osg_gemm_common.h"
+#include "osg_conv3x3_cat_plan.h"
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -59,15 +60,39 @@ struct Geo {
     }
 };
 
+// ---- CAT = 1 (osg_conv3x3_cat.hip): a second K segment.  Behind the last (slab, tap) unit the workgroup walks Cin2 / 64 further k-tiles of a 1x1 convolution over a
+// second NHWC tensor x2 [M][Cin2] with a second weight [N][Cin2] (the ResNet shortcut), into the same accumulators; the epilogue runs once.  A k-tile of this phase
+// brings a fresh A tile (the tile's 128 pixels x 64 channels, 16 KiB, rows swizzled like the patch's) AND a weight stage, so the LDS is carved again, behind a
+// workgroup barrier, as a ring of NS2 stages of (A tile + weight stage) with D2 = NS2 - 1 units in flight.  The k-slices of a split divide the combined unit list
+// (osg_conv3x3_cat_plan.h).  Barriers per workgroup, loader and math waves alike: 1 + 9 * slabs of the 3x3 phase, then 2 + k-tiles where the slice holds k-tiles, then one
+// behind the loaders' final vmcnt(0) (their tail loads zero-fill ring stages the epilogue's statistics staging reuses).  A split ends in the reduce launch: this variant
+// never runs splitk_fold_acc (osg_conv3x3_cat.hip).
+struct CatArgs { const void* x2; const void* w2; int Cin2; unsigned a2_bytes, b2_bytes; };
+template <int W_, int BN, int NLW>
+struct Geo2 {
+    using G = Geo<W_, BN, NLW, 0>;
+    static_assert(G::BST_BYTES == cat_bst_bytes(BN, NLW), "osg_conv3x3_cat_plan.h restates the weight stage");
+    static constexpr int A2_BYTES = kCatATileBytes;
+    static constexpr int NA2 = A2_BYTES / 1024 / NLW;         // A wave-loads per loader wave per k-tile
+    static constexpr int ST2 = cat_stage_bytes(G::BST_BYTES);
+    static constexpr int NS2 = cat_stages(G::BST_BYTES);
+    static constexpr int D2 = NS2 - 1;
+    static constexpr int LPU = NA2 + G::WLB;                  // wave-loads per loader wave per k-tile
+    static constexpr size_t SMEM = (size_t)NS2 * ST2 > G::SMEM ? (size_t)NS2 * ST2 : G::SMEM;
+    static constexpr bool OK = D2 >= 3 && (D2 - 1) * LPU <= 63 && NA2 * NLW * 1024 == A2_BYTES;
+};
+
 // W_: image width (= tile width); BN: output channels per tile; WGM x WGN: grid of the 4 MATH waves.
 // 512 threads = 4 math waves + 4 LOADER waves (one pair per SIMD).  Measured (tools/pmc_conv.sh): one `buffer_load ... lds`
 // costs its issuing wave ~100+ cycles, so with loads and MFMAs in the same instruction stream the matrix pipe idled 75 % of
 // the time whatever the ring depth; with the DMA issue moved to waves that do nothing else, the math waves' stream is
 // ds_read + MFMA only and the two streams overlap on the SIMD.
 // (the body is a __device__ function: hipcc emits no host stub for a __global__ template whose body holds a generic lambda)
-template <int W_, int BN, int WGM, int WGN, int MODE, int NLW, int WQ = 0>
-__device__ __forceinline__ void conv3x3_body(const GemmParams& p) {
+template <int W_, int BN, int WGM, int WGN, int MODE, int NLW, int WQ = 0, int CAT = 0>
+__device__ __forceinline__ void conv3x3_body(const GemmParams& p, const CatArgs& cat = CatArgs{}) {
     using G = Geo<W_, BN, NLW, WQ>;
+    using G2 = Geo2<W_, BN, NLW>;
+    static_assert(!CAT || (WQ == 0 && MODE == 0), "the second K segment takes f16 weights");
     constexpr int TI = G::TI, TH = G::TH, PW = G::PW, PPI = G::PPI, PP = G::PP, NPW = G::NPW, PATCH_BYTES = G::PATCH_BYTES;
     constexpr int WLB = G::WLB, BST_BYTES = G::BST_BYTES, NSTW = G::NSTW, D = G::D, PPT = G::PPT;
     constexpr int WM = 128 / WGM, WN = BN / WGN, TM = WM / 16, TN = WN / 16;
@@ -101,8 +126,13 @@ __device__ __forceinline__ void conv3x3_body(const GemmParams& p) {
         zs = L / (p.nt); n_tile = L - zs * p.nt;
     }
     const int m0 = m_tile * 128, n0 = n_tile * BN;
-    const int slab_b = zs * (p.k_per_split >> 6);
-    const int slab_e = min(p.Cin >> 6, slab_b + (p.k_per_split >> 6));
+    int slab_b = zs * (p.k_per_split >> 6);
+    int slab_e = min(p.Cin >> 6, slab_b + (p.k_per_split >> 6));
+    int kt_b = 0, kt_e = 0;                          // CAT: this slice's k-tiles of the second segment
+    if constexpr (CAT) {                             // (k_per_split holds the units per slice of the combined list here)
+        const CatSlice cs = cat_slice(p.Cin >> 6, cat.Cin2 >> 6, p.k_per_split, zs);
+        slab_b = cs.slab_b; slab_e = cs.slab_e; kt_b = cs.kt_b; kt_e = cs.kt_e;
+    }
 
     if (loader) {
         // =========================================== LOADER waves ==============================================================
@@ -176,6 +206,52 @@ __device__ __forceinline__ void conv3x3_body(const GemmParams& p) {
             });
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // retire the dummy tail loads before the LDS is released
+        if constexpr (CAT) {
+            if (kt_b < kt_e) {
+                // ======================================= the 1x1 phase: a ring of NS2 (A tile + weight stage) stages =======================================
+                constexpr int NA2 = G2::NA2, ST2 = G2::ST2, NS2 = G2::NS2, D2 = G2::D2, LPU = G2::LPU, A2_BYTES = G2::A2_BYTES;
+                __builtin_amdgcn_s_barrier();                   // the math waves are done with the patches and the weight ring: the LDS is carved again
+                __amdgpu_buffer_rsrc_t rsA2 = __builtin_amdgcn_make_buffer_rsrc((void*)cat.x2, 0, cat.a2_bytes, 0x00020000);
+                __amdgpu_buffer_rsrc_t rsB2 = __builtin_amdgcn_make_buffer_rsrc((void*)cat.w2, 0, cat.b2_bytes, 0x00020000);
+                unsigned a2_off[NA2], b2_off[WLB];
+#pragma unroll
+                for (int pc = 0; pc < NA2; pc++) {              // wave-load g = pc * NLW + wave covers rows g * 8 .. + 7 of the tile's 128 pixels
+                    const int mrow = m0 + (pc * NLW + wave) * 8 + rsub;
+                    a2_off[pc] = mrow < p.M ? (unsigned)((mrow * cat.Cin2 + gch * 8) * 2) : OOB;
+                }
+#pragma unroll
+                for (int j = 0; j < WLB; j++) {
+                    const int nl = (j * NLW + wave) * 8 + rsub;
+                    const int n = n0 + nl;
+                    b2_off[j] = (nl < BN && n < p.N) ? (unsigned)((n * cat.Cin2 + gch * 8) * 2) : OOB;
+                }
+                auto issue_unit2 = [&](int stage, int kt) {       // kt may be past the end: dummy (zero-filling) loads, so that the counted waits stay the same
+                    const unsigned kill = kt < kt_e ? 0u : OOB;
+                    char* dst = smem3 + stage * ST2;
+#pragma unroll
+                    for (int pc = 0; pc < NA2; pc++)
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA2, (lds_ptr)(dst + (pc * NLW + wave) * 1024), 16, a2_off[pc] | kill, kt * 128, 0, 0);
+#pragma unroll
+                    for (int j = 0; j < WLB; j++)
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB2, (lds_ptr)(dst + A2_BYTES + (j * NLW + wave) * 1024), 16, b2_off[j] | kill, kt * 128, 0, 0);
+                };
+#pragma unroll
+                for (int d = 0; d < D2; d++) issue_unit2(d, kt_b + d);
+                wait_vmcnt<(D2 - 1) * LPU>();                   // k-tile 0 has landed
+                __builtin_amdgcn_s_barrier();
+                int st2 = 0;
+                for (int kt = kt_b; kt < kt_e; kt++) {
+                    wait_vmcnt<(D2 - 2) * LPU>();               // k-tile u + 1 is resident too: what the previous D2 - 2 units issued may stay in flight
+                    __builtin_amdgcn_s_barrier();
+                    int std_ = st2 + D2;
+                    std_ = std_ >= NS2 ? std_ - NS2 : std_;
+                    issue_unit2(std_, kt + D2);                 // into the stage unit u - 1 just released
+                    st2 = st2 + 1 == NS2 ? 0 : st2 + 1;
+                }
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            __builtin_amdgcn_s_barrier();                       // every DMA of this workgroup has landed: the math waves may reuse the LDS (statistics staging)
+        }
         return;
     }
 
@@ -353,6 +429,39 @@ __device__ __forceinline__ void conv3x3_body(const GemmParams& p) {
             }
         });
     }
+    if constexpr (CAT) {
+        if (kt_b < kt_e) {
+            // the 1x1 phase (see the loader waves): same unit structure, both operands out of the ring stage of the unit
+            constexpr int ST2 = G2::ST2, NS2 = G2::NS2, A2_BYTES = G2::A2_BYTES;
+            const int a_rd2 = (wm0 + frow) * 128 + ((fq ^ (frow & 7)) << 4);      // row ml = wm0 + i * 16 + frow of the A tile: (ml & 7) == (frow & 7)
+            auto read_frags2 = [&](f16x8 (&fa)[TM], f16x8 (&fb)[TN], const char* sbuf, int ks) {
+#pragma unroll
+                for (int i = 0; i < TM; i++) fa[i] = *reinterpret_cast<const f16x8*>(sbuf + ((a_rd2 + i * 16 * 128) ^ (ks << 6)));
+#pragma unroll
+                for (int j = 0; j < TN; j++) fb[j] = *reinterpret_cast<const f16x8*>(sbuf + A2_BYTES + ((b_rd + j * 16 * 128) ^ (ks << 6)));
+            };
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's last fragment reads of the 3x3 phase have left the LDS before the loaders overwrite it
+            __builtin_amdgcn_s_barrier();                       // the LDS is carved again
+            __builtin_amdgcn_s_barrier();                       // k-tile 0 has landed
+            read_frags2(fa0, fb0, smem3, 0);
+            int st2 = 0;
+            for (int kt = kt_b; kt < kt_e; kt++) {
+                __builtin_amdgcn_s_barrier();                   // units <= u + 1 resident; the loaders may now overwrite unit u - 1's stage
+                read_frags2(fa1, fb1, smem3 + st2 * ST2, 1);
+                mma(fa0, fb0);
+                static_for<0, TM + TN>([&](auto) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); });
+                __builtin_amdgcn_sched_group_barrier(0x008, TM * TN - (TM + TN), 0);
+                __builtin_amdgcn_sched_barrier(0);
+                st2 = st2 + 1 == NS2 ? 0 : st2 + 1;
+                read_frags2(fa0, fb0, smem3 + st2 * ST2, 0);
+                mma(fa1, fb1);
+                static_for<0, TM + TN>([&](auto) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 1, 0); });
+                __builtin_amdgcn_sched_group_barrier(0x008, TM * TN - (TM + TN), 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        __builtin_amdgcn_s_barrier();                           // the loader waves have retired every DMA (their tail loads fill stages of the ring with zeros)
+    }
     kdbg_stamp(p, 3);
     if constexpr (WQ) { if constexpr (W8SC) w8_scale_acc<TM, TN>(w8, acc); else w8_scale_acc_late<TM, TN>(p, acc, n0, wn0, lane); }
     kdbg_stamp(p, 4);
@@ -361,7 +470,7 @@ __device__ __forceinline__ void conv3x3_body(const GemmParams& p) {
         __builtin_amdgcn_s_barrier();           // (the loader waves have left: the four math waves) every one is done with patches and weight stages
         stat_lds = reinterpret_cast<float*>(smem3) + (wave8 & 3) * (WN * 2);
     }
-    if constexpr (MODE == 0) {
+    if constexpr (MODE == 0 && !CAT) {   // (CAT: the launcher never asks for the fold, osg_conv3x3_cat.hip)
         if (OSG_UNLIKELY(p.splits > 1 && p.fold_acc)) {
             // split-K over slabs, folded by the last workgroup to arrive at the tile (osg_gemm_common.h splitk_fold_acc; only the 4 math waves are still here:
             // tid 0..255): it then runs the fused epilogue of an unsplit launch
@@ -391,12 +500,29 @@ __global__ __launch_bounds__(256 + 64 * NLW) void conv3x3_kernel(const void* A, 
     conv3x3_body<W_, BN, WGM, WGN, MODE, NLW, WQ>(p);
 }
 
-template <int W_, int BN, int WGM, int WGN, int MODE = 0, int NLW = 4, int WQ = 0>
-int launch3(osg_ctx* ctx, GemmParams& p) {
-    constexpr size_t smem = Geo<W_, BN, NLW, WQ>::SMEM;
+// CAT = 1: the second (activation, weight) pair behind the preloaded parameters
+template <int W_, int BN, int WGM, int WGN, int NLW>
+__global__ __launch_bounds__(256 + 64 * NLW) void conv3x3_cat_kernel(const void* A, const void* Bt, int M, int N, int K, int k_per_split, unsigned a_bytes, unsigned b_bytes, int grid,
+                                                                     int H, int Cin, unsigned sp_nm, CatArgs cat, GemmParams pk) {
+    GemmParams p = pk;
+    p.A = (const f16*)A; p.Bt = (const f16*)Bt; p.M = M; p.N = N; p.K = K; p.k_per_split = k_per_split; p.a_bytes = a_bytes; p.b_bytes = b_bytes; p.grid = grid; p.H = H; p.Cin = Cin;
+    p.splits = (int)(sp_nm & ((1u << kPackSplitsBits) - 1)); p.n_major = (sp_nm & kPackNMajor) != 0;
+    p.mt = (M + 127) / 128; p.nt = (N + BN - 1) / BN;
+    p.kdbg = nullptr;
+    if (OSG_UNLIKELY(sp_nm & kPackKdbg)) p.kdbg = kernarg_rare(pk.kdbg);
+    conv3x3_body<W_, BN, WGM, WGN, 0, NLW, 0, 1>(p, cat);
+}
+
+template <int W_, int BN, int WGM, int WGN, int MODE, int NLW, int WQ, int CAT>
+int launch3_any(osg_ctx* ctx, GemmParams& p, const CatArgs* cat) {
+    constexpr size_t smem = CAT ? Geo2<W_, BN, NLW>::SMEM : Geo<W_, BN, NLW, WQ>::SMEM;
     static_assert(smem <= 160 * 1024, "LDS budget");
     static_assert(Geo<W_, BN, NLW, WQ>::OK, "pipeline depth out of range");
-    auto kern = conv3x3_kernel<W_, BN, WGM, WGN, MODE, NLW, WQ>;
+    static_assert(!CAT || Geo2<W_, BN, NLW>::OK, "pipeline depth of the 1x1 phase out of range");
+    auto kern = [] {
+        if constexpr (CAT) return conv3x3_cat_kernel<W_, BN, WGM, WGN, NLW>;
+        else return conv3x3_kernel<W_, BN, WGM, WGN, MODE, NLW, WQ>;
+    }();
     static unsigned long long attr_mask = 0;   // (per device: hipFuncSetAttribute is, and a process may hold several)
     if (osg_first_on_device(attr_mask)) {
         OSG_HIP(ctx, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
@@ -415,12 +541,18 @@ int launch3(osg_ctx* ctx, GemmParams& p) {
     int lda32;
     unsigned sp_nm;
     const int bad = kernarg_pack(ctx, 0, p.splits, p.n_major, p.kdbg != nullptr, false, &lda32, &sp_nm);
+    if constexpr (CAT) {
+        if (!bad) hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(256 + 64 * NLW), smem, ctx->compute, (const void*)p.A, (const void*)p.Bt, p.M, p.N, p.K, p.k_per_split, p.a_bytes, p.b_bytes, p.grid, p.H, p.Cin, sp_nm, *cat, p);
+    } else {
     if (!bad) hipLaunchKernelGGL(kern, dim3((unsigned)p.grid), dim3(256 + 64 * NLW), smem, ctx->compute, (const void*)p.A, (const void*)p.Bt, p.M, p.N, p.K, p.k_per_split, p.a_bytes, p.b_bytes, p.grid, p.H, p.Cin, sp_nm, p);
+    }
     p.sink[0] = sinks_in[0]; p.sink[1] = sinks_in[1];
     if (bad) return 1;
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
+template <int W_, int BN, int WGM, int WGN, int MODE = 0, int NLW = 4, int WQ = 0>
+int launch3(osg_ctx* ctx, GemmParams& p) { return launch3_any<W_, BN, WGM, WGN, MODE, NLW, WQ, 0>(ctx, p, nullptr); }
 
 // the launchers of the kV3Entries (osg_gemm_routes.h) translation unit UNIT instantiates, indexed by entry (nullptr: another unit's)
 using V3Launch = int (*)(osg_ctx*, GemmParams&);

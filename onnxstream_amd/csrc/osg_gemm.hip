@@ -783,16 +783,27 @@ int osg_set_stat_sinks(osg_ctx* ctx, void* table0, int groups0, int cpg0, int ch
 }
 
 struct W8Quant { int on; float scale; int zp; const float* sc; const float* zv; };   // uint8 weight codes + (scale, zero point): scalars or [N] vectors
+struct Cat2 { const void* x2; const void* w2; int Cin2; };                            // osg_conv2d_nhwc_cat: the second (activation, weight) pair
+static int conv2d_cat_route(osg_ctx* ctx, GemmParams& p, const Cat2& cat, int KH, int KW, int sh, int sw, int pt, int pl, int pb, int pr);
 
 static int conv2d_v(osg_ctx* ctx, const W8Quant& q, const void* x, const void* w, const void* bias, osg_dtype bias_dtype,
                     const void* image_bias, long image_bias_ld, const void* residual, void* y, long y_ld, void* y2, long y2_ld, int N, int H, int W,
-                    int Cin, int Cout, int KH, int KW, int sh, int sw, int pt, int pl, int pb, int pr, osg_act act);
+                    int Cin, int Cout, int KH, int KW, int sh, int sw, int pt, int pl, int pb, int pr, osg_act act, const struct Cat2* cat = nullptr);
 
 int osg_conv2d_nhwc_v(osg_ctx* ctx, osg_dtype dtype, const void* x, const void* w, const void* bias, osg_dtype bias_dtype,
                       const void* image_bias, long image_bias_ld, const void* residual, void* y, long y_ld, void* y2, long y2_ld, int N, int H, int W,
                       int Cin, int Cout, int KH, int KW, int sh, int sw, int pt, int pl, int pb, int pr, osg_act act) {
     if (dtype != OSG_F16) OSG_FAIL(ctx, "osg_conv2d_nhwc: only f16 arithmetic is implemented on the device");
     return conv2d_v(ctx, W8Quant{}, x, w, bias, bias_dtype, image_bias, image_bias_ld, residual, y, y_ld, y2, y2_ld, N, H, W, Cin, Cout, KH, KW, sh, sw, pt, pl, pb, pr, act);
+}
+
+// osg_conv2d_nhwc_v with a second K segment: y = f16(conv3x3(x, w) + x2 . w2^T + bias), x2 [N, H, W, Cin2] NHWC, w2 [Cout][Cin2], bias [Cout] f32 (the sum of
+// both convolutions' biases).  One launch of the halo-reuse kernel (osg_conv3x3_cat.hip); a shape it does not take is an error, not another route.
+int osg_conv2d_nhwc_cat(osg_ctx* ctx, const void* x, const void* w, const void* x2, const void* w2, int Cin2, const float* bias_f32, void* y, long y_ld, void* y2,
+                        long y2_ld, int N, int H, int W, int Cin, int Cout, osg_act act) {
+    if (!x || !w || !x2 || !w2 || !y) OSG_FAIL(ctx, "osg_conv2d_nhwc_cat: invalid argument");
+    const Cat2 cat{x2, w2, Cin2};
+    return conv2d_v(ctx, W8Quant{}, x, w, bias_f32, OSG_F32, nullptr, 0, nullptr, y, y_ld, y2, y2_ld, N, H, W, Cin, Cout, 3, 3, 1, 1, 1, 1, 1, 1, act, &cat);
 }
 
 static int w8_check(osg_ctx* ctx, const char* who, const W8Quant& q, int N, int K, const void* a, const void* b) {
@@ -847,7 +858,7 @@ int osg_gemm_kernarg_check(osg_ctx* ctx, long lda, int splits) {
 
 static int conv2d_v(osg_ctx* ctx, const W8Quant& q, const void* x, const void* w, const void* bias, osg_dtype bias_dtype,
                     const void* image_bias, long image_bias_ld, const void* residual, void* y, long y_ld, void* y2, long y2_ld, int N, int H, int W,
-                    int Cin, int Cout, int KH, int KW, int sh, int sw, int pt, int pl, int pb, int pr, osg_act act) {
+                    int Cin, int Cout, int KH, int KW, int sh, int sw, int pt, int pl, int pb, int pr, osg_act act, const Cat2* cat) {
     if (y_ld < 0 || (y_ld && y_ld < Cout) || (y2 && y2_ld < Cout)) OSG_FAIL(ctx, "osg_conv2d_nhwc_v: an output pitch is smaller than Cout");
     if (Cout % 4 == 0 && ((y_ld & 3) || (y2 && (y2_ld & 3)))) OSG_FAIL(ctx, "osg_conv2d_nhwc_v: output pitches must be multiples of 4 elements");
     if ((y_ld && ((uintptr_t)y & 7)) || (y2 && ((uintptr_t)y2 & 7))) OSG_FAIL(ctx, "osg_conv2d_nhwc_v: output views must be 8-byte aligned");
@@ -882,9 +893,31 @@ static int conv2d_v(osg_ctx* ctx, const W8Quant& q, const void* x, const void* w
     ctx->sink_fused = false;
     if (want_sinks && (p.sink_hw <= 0 || p.sink_hw != Ho * Wo)) OSG_FAIL(ctx, "osg_conv2d_nhwc_v: the statistics sinks were set for another image size");
     if (epi_check(ctx, p)) return 1;
-    const int rc = conv2d_route(ctx, p, N, Cin, Cout, KH, KW, sh, sw, pt, pl, pb, pr);
+    const int rc = cat ? conv2d_cat_route(ctx, p, *cat, KH, KW, sh, sw, pt, pl, pb, pr) : conv2d_route(ctx, p, N, Cin, Cout, KH, KW, sh, sw, pt, pl, pb, pr);
     if (rc || !want_sinks || ctx->sink_fused) return rc;
     return osg_mm::launch_colstats(ctx, p.C, p.ldc ? p.ldc : (long)Cout, p.M, Cout, p.sink_hw, p.sink);
+}
+
+// the fused conv2 + shortcut launch: the halo kernel or an error.  Tile choice: the table's row of the UN-fused conv2 shape (the same launch with a residual
+// in place of the second segment) where it names the halo kernel, else the halo cost model's first candidate; nothing is timed and no miss is counted.
+static int conv2d_cat_route(osg_ctx* ctx, GemmParams& p, const Cat2& cat, int KH, int KW, int sh, int sw, int pt, int pl, int pb, int pr) {
+    if (p.w8 || KH != 3 || KW != 3 || sh != 1 || sw != 1 || pt != 1 || pl != 1 || pb != 1 || pr != 1 || cat.Cin2 <= 0 || cat.Cin2 % 64 || osg_conv3x3_prepare(ctx, p))
+        OSG_FAIL(ctx, "osg_conv2d_nhwc_cat: takes 3x3 / stride 1 / pad 1 at W in {8, 16, 32, 64} in whole 128-pixel tiles, Cin % 64 == 0, Cin2 % 64 == 0, Cout % 4 == 0, 16-byte aligned operands");
+    Halo3Choice ch = model_halo3(select_env(ctx), select_shape(p, 1));
+    if (apply_knobs<Halo3Choice>(kHalo3Knobs, nullptr)) apply_knobs(kHalo3Knobs, &ch);
+    else if (ctx->autotune) {
+        KeyForm f = key_form(p);
+        f.residual = true;
+        for (int b32 = 0; b32 < 2; b32++) {
+            f.bias_f32 = b32 != 0;
+            osg_tune::Choice row;
+            if (osg_tune::peek(tune_key(1, select_shape(p, 1), f), &row)) {
+                if (row.family == 1) ch = row_halo3(row);
+                break;
+            }
+        }
+    }
+    return osg_conv3x3_cat_launch(ctx, p, cat.x2, cat.w2, cat.Cin2, ch);
 }
 
 static int conv2d_route(osg_ctx* ctx, GemmParams& p, int N, int Cin, int Cout, int KH, int KW, int sh, int sw, int pt, int pl, int pb, int pr) {

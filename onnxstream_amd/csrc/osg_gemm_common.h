@@ -1009,3 +1009,5 @@ int osg_conv3x3_run(osg_ctx* ctx, osg_mm::GemmParams& p);
 // the same in pieces, for the measured configuration choice (osg_tune.h): shape gate (fills the buffer extents), one launch
 int osg_conv3x3_prepare(osg_ctx* ctx, osg_mm::GemmParams& p);
 int osg_conv3x3_launch(osg_ctx* ctx, osg_mm::GemmParams p, osg_mm::Halo3Choice ch);
+// osg_conv3x3_cat.hip: the same launch with a second K segment, a 1x1 convolution of x2 [M][Cin2] with w2 [N][Cin2] into the same accumulators (f16 weights)
+int osg_conv3x3_cat_launch(osg_ctx* ctx, osg_mm::GemmParams p, const void* x2, const void* w2, int Cin2, osg_mm::Halo3Choice ch);

@@ -21,6 +21,7 @@ bool lookup(const Key& k, Choice* out);
 inline bool frozen() { static const bool v = getenv("OSG_TUNE_FROZEN") && atoi(getenv("OSG_TUNE_FROZEN")) != 0; return v; }
 void store(const Key& k, const Choice& c);
 void remember(const Key& k, const Choice& c);   // in memory only (the untimed choice of a shape a frozen table does not hold)
+bool peek(const Key& k, Choice* out);           // lookup that counts no miss
 int misses();                                   // lookups that found nothing, since the process started
 
 // microseconds per launch of f() (which enqueues the whole operation, reduce kernel included, and returns 0 on success); < 0 on failure

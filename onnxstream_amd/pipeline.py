@@ -12,6 +12,7 @@ Out of scope (host glue of the app): tokenizer, text enc
 from __future__ import annotations
 
 import math
+import os
 from typing import Callable, Dict, List, Optional
 
 import numpy as np
@@ -293,6 +294,8 @@ class Txt2Img:
                 m._set_option("hip_device", device)
                 if fusion is not None:
                     m._set_option("hip_fusion_level", fusion)
+                if m is self.unet:      # conv2 + conv_shortcut of the channel-changing ResNets as one launch (OSA_FUSE_SHORTCUT=0: A/B runs against the un-fused plan)
+                    m._set_option("hip_fuse_shortcut", int(os.environ.get("OSA_FUSE_SHORTCUT", "1") != "0"))
                 if autotune is not None:
                     m._set_option("hip_autotune", int(bool(autotune)))
             m.read_file(d + "model.txt")
