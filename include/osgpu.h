@@ -379,6 +379,45 @@ int osg_decode_pick(osg_ctx* ctx, const float* logits, long T, long V, long long
 int osg_decode_sample(osg_ctx* ctx, const float* logits, long T, long V, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
                       int64_t* tokens, long max_tokens, float temperature, long top_k, float top_p, unsigned long long seed,
                       unsigned long long draw_base);
+/* ---- repetition, presence and frequency penalties and min-p: the rule above with a step 0 in front of step 1 and a step 3b behind step 3.
+ *   Counts.  c_i (int32) = how often token i occurs among the caller's history tokens plus the tokens this sequence has appended in this call: a device
+ *      table [V] per sequence, filled from the history by osg_decode_count and raised by the _ext entry points below -- where step 6 (and the same
+ *      place of osg_decode_pick) appends tok, c_tok += 1, by the thread that appends.  A launch that appends nothing (stop != 0, the budget spent, the
+ *      eos token, an invalid row) changes no count.  Counts stay below 2^24 (the callers see to it), so (float)c_i is exact.
+ *   0. Penalties (osg_decode_penalize): the raw fp32 logit l_i becomes a_i, and steps 1-6 run on a instead of l.
+ *      c_i = 0: a_i has the bits of l_i.   c_i > 0, in this order, every operation rounded on its own (no product and sum is contracted into an fma):
+ *        b = l_i > 0 ? l_i * inv_r : l_i * r     one fp32 multiply; r = the repetition penalty, inv_r = 1.0f / r computed once on the host in fp32
+ *                                                (a MULTIPLY by the reciprocal, as step 3 does with the temperature); l_i = +-0 takes the second branch
+ *        u = presence + frequency * (float)c_i   the product rounded, then the sum rounded
+ *        a_i = b - u                             one rounding
+ *      NaN stays NaN and +-inf stays +-inf: nothing is special-cased, steps 1-6 handle a NaN and an infinite top as they always did.
+ *   3b. min-p, behind the weights' x_i = (a_i - m) * inv_t of step 3 and before top-p: a token with x_i < x_min drops out.  x_min = the fp32 nearest
+ *      to the double-precision log of min_p's fp32 value, computed once on the host; min_p = 0 turns the step off (x_min = -inf).  The compare is on
+ *      x, not on exp(x): it is exact.  The first token of the order has x = 0 and is always kept; the kept set is a prefix of step 1's order, so the
+ *      step commutes with top-k.
+ *   Greedy with penalties is osg_decode_pick over a (the scan still starts at -1.0f, the last of equal maxima wins); it has no min-p.
+ * Deviation from a single fused kernel: step 0 is a launch of its own into a scratch row, so the radix passes of the sample kernel are untouched and
+ * re-read no counts; the callers launch it only while a penalty is active and hand the scratch row to the _ext entry point as its logits. */
+/* counts[t] += 1 for each of the n DEVICE tokens (int64) with 0 <= t < V; a token outside [0, V) writes nothing.  Integer atomics: the table does not
+ * depend on the order of arrival.  n = 0 launches nothing. */
+int osg_decode_count(osg_ctx* ctx, const int64_t* tokens, long n, int* counts, long V);
+/* Step 0 for n_seq rows: out[s][i] = a_i of row s = rows + s * row_stride (elements) under the counts counts[s][0..V), s < n_seq <= 65535; counts and
+ * out are dense [n_seq][V].  The row is read with 16-byte loads from its first aligned element on; the counts and the output go 16 bytes at a time
+ * where their rows stand likewise, else element by element.  out must not overlap rows. */
+int osg_decode_penalize(osg_ctx* ctx, const float* rows, long row_stride, long V, int n_seq, const int* counts, float* out, float r, float inv_r,
+                        float presence, float frequency);
+/* osg_decode_pick / osg_decode_sample / osg_decode_sample_batch plus min_p in [0, 1] (the sample forms; 0 = off) and the count table `counts` (device
+ * int32 [V]; [n_seq][V] for the batch form; may be NULL).  `logits` is what steps 1-6 run on: the raw row, or the row osg_decode_penalize wrote.
+ * The thread that appends tok raises counts[tok].  With min_p = 0 and counts = NULL each IS the old entry point (which forwards here): the same launch
+ * of the same device code, the same bits. */
+int osg_decode_pick_ext(osg_ctx* ctx, const float* logits, long T, long V, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
+                        int64_t* tokens, long max_tokens, int* counts);
+int osg_decode_sample_ext(osg_ctx* ctx, const float* logits, long T, long V, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
+                          int64_t* tokens, long max_tokens, float temperature, long top_k, float top_p, unsigned long long seed,
+                          unsigned long long draw_base, float min_p, int* counts);
+int osg_decode_sample_batch_ext(osg_ctx* ctx, const float* logits, long V, int n_seq, long long eos_id, int* state, int64_t* input_ids,
+                                int64_t* position_ids, int64_t* tokens, long max_tokens, float temperature, long top_k, float top_p,
+                                const unsigned long long* seeds, unsigned long long draw_base, float min_p, int* counts);
 /* cache[h][*row][0..d) = src[h][0..d) for h < kv_heads: the new key or value row of every head, f16 [kv_heads][d], into a capacity buffer
  * [kv_heads][cap][d] at the row a device int names (state + 0).  A row outside [0, cap) writes nothing. */
 int osg_kv_append_at(osg_ctx* ctx, const void* src, void* cache, const int* row, int kv_heads, long cap, int d);

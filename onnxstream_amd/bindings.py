@@ -28,6 +28,23 @@ class _GetTensorReturnLayout(ctypes.Structure):
 _WP_NAMES = ("ram", "nocache", "prefetch", "ram+nocache", "ram+prefetch")
 
 
+class SampleExt(ctypes.Structure):
+    """model_hip_sample_ext (exports.cpp): the penalties, min-p and the token history of the three _ext calls"""
+    _fields_ = [("repetition_penalty", ctypes.c_float), ("presence_penalty", ctypes.c_float), ("frequency_penalty", ctypes.c_float), ("min_p", ctypes.c_float),
+                ("history", ctypes.POINTER(ctypes.c_longlong)), ("n_history", ctypes.c_longlong)]
+
+
+def sample_ext(repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, min_p=0.0, history=None):
+    """(SampleExt, the array that backs its history) when one of the five is set, else (None, None): the caller then takes the export without _ext"""
+    import numpy as np
+    if repetition_penalty == 1.0 and presence_penalty == 0.0 and frequency_penalty == 0.0 and min_p == 0.0 and history is None:
+        return None, None
+    hist = np.ascontiguousarray(np.asarray([] if history is None else history, np.int64).reshape(-1))
+    ext = SampleExt(float(repetition_penalty), float(presence_penalty), float(frequency_penalty), float(min_p),
+                    hist.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)) if hist.size else None, int(hist.size))
+    return ext, hist
+
+
 class Model:
     def __init__(self, library_path: str, threads_count: int = 0, weights_provider_name: str = "prefetch"):
         self._lib = ctypes.CDLL(library_path)
@@ -346,7 +363,8 @@ class Model:
 
     def generate(self, max_new: int, n_caches: int, eos_id: int = -1, sync_every: int = 0, trace: bool = False, ids: str = "input_ids",
                  pos: str = "position_ids", mask: str = "attention_mask", logits: str = "logits", cache_in: str = "pkv", cache_out: str = "opkv",
-                 temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, draw_base: int = 0):
+                 temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, draw_base: int = 0, repetition_penalty: float = 1.0,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, min_p: float = 0.0, history=None):
         """The LLM app's greedy token loop on the device (model_hip_generate): after a run() over the prompt has left `logits` (fp32) and the caches
         `cache_out`<i> (fp16, i < n_caches) in the Model, up to max_new tokens are picked (the app's argmax) and run through the resident T = 1 plan
         without a host round trip per token; the caches and the last logits are left as the host loop would leave them.  Returns
@@ -354,18 +372,26 @@ class Model:
         sync_every > 0: the stop code is read after every sync_every passes and the call ends early.
         temperature > 0 samples instead (model_hip_generate_sampled; the rule is stated in include/osgpu.h at osg_decode_sample): logits / temperature,
         the top_k largest (0 = off), the shortest prefix holding top_p of the mass (1 = off), a Philox draw keyed by the 64-bit `seed` at draw index
-        draw_base + n_tokens; stop 2 then means a row without a finite maximum.  temperature == 0 is the greedy call, whatever the other four say."""
+        draw_base + n_tokens; stop 2 then means a row without a finite maximum.  temperature == 0 is the greedy call, whatever the other four say.
+        repetition_penalty (1 = off), presence_penalty, frequency_penalty (0 = off), min_p (0 = off; needs temperature > 0) and `history` (tokens the
+        penalties count from the start; None = nothing, the prompt went through run() and is not known here) take the call through
+        model_hip_generate_sampled_ext (steps 0 and 3b of the rule in include/osgpu.h); with temperature == 0 the pick then runs over the penalized
+        logits.  The trace keeps the raw logits.  With all five at their defaults the call is the one it always was."""
         import numpy as np
         cp, ip = ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)
         argtypes = [ctypes.c_void_p, cp, cp, cp, cp, cp, cp, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), ip, ip,
                     ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double)]
         rule = ()
-        if temperature == 0:
+        ext, _hist = sample_ext(repetition_penalty, presence_penalty, frequency_penalty, min_p, history)
+        if temperature == 0 and ext is None:
             f = self._lib.model_hip_generate
         else:
-            f = self._lib.model_hip_generate_sampled
+            f = self._lib.model_hip_generate_sampled if ext is None else self._lib.model_hip_generate_sampled_ext
             argtypes += [ctypes.c_float, ctypes.c_longlong, ctypes.c_float, ctypes.c_ulonglong, ctypes.c_ulonglong]
             rule = (float(temperature), int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(draw_base) & (2 ** 64 - 1))
+            if ext is not None:
+                argtypes += [ctypes.POINTER(SampleExt)]
+                rule += (ctypes.byref(ext),)
         f.argtypes = argtypes
         f.restype = ctypes.c_void_p
         toks = np.zeros(max(int(max_new), 1), np.int64)
@@ -383,17 +409,21 @@ class Model:
 
     def generate_batch(self, n_seq: int, max_new: int, n_caches: int, seeds, temperature: float, top_k: int = 0, top_p: float = 1.0, draw_base: int = 0,
                        eos_id: int = -1, sync_every: int = 0, trace: bool = False, ids: str = "input_ids", pos: str = "position_ids",
-                       mask: str = "attention_mask", logits: str = "logits", cache_in: str = "pkv", cache_out: str = "opkv"):
+                       mask: str = "attention_mask", logits: str = "logits", cache_in: str = "pkv", cache_out: str = "opkv", repetition_penalty: float = 1.0,
+                       presence_penalty: float = 0.0, frequency_penalty: float = 0.0, min_p: float = 0.0, history=None):
         """n_seq sampled continuations of the one prompt in one call (model_hip_generate_batch): sequence s is `generate` with seed = seeds[s], on caches and
         a state of its own, and all of them share every pass of a decode plan of batch n_seq.  A sequence that stops, stops alone.  The Model's tensors are
         left as they were.  seeds: n_seq 64-bit integers (None: the call is refused).  Returns (tokens: list of n_seq int64 arrays [n_tokens[s]],
-        stop int32 [n_seq], traces: list of n_seq float32 arrays [n_tokens[s], V] or None, device ms)."""
+        stop int32 [n_seq], traces: list of n_seq float32 arrays [n_tokens[s], V] or None, device ms).
+        repetition_penalty, presence_penalty, frequency_penalty, min_p, history: as `generate` (model_hip_generate_batch_ext); every sequence starts
+        from the same history and counts its own tokens from there."""
         import numpy as np
         cp, ip = ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)
-        f = self._lib.model_hip_generate_batch
+        ext, _hist = sample_ext(repetition_penalty, presence_penalty, frequency_penalty, min_p, history)
+        f = self._lib.model_hip_generate_batch if ext is None else self._lib.model_hip_generate_batch_ext
         f.argtypes = [ctypes.c_void_p, cp, cp, cp, cp, cp, cp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_int,
                       ctypes.POINTER(ctypes.c_longlong), ip, ip, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_double), ctypes.c_float,
-                      ctypes.c_longlong, ctypes.c_float, ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_ulonglong]
+                      ctypes.c_longlong, ctypes.c_float, ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_ulonglong] + ([ctypes.POINTER(SampleExt)] if ext is not None else [])
         f.restype = ctypes.c_void_p
         ns, mn = max(int(n_seq), 1), max(int(max_new), 1)
         sd = None
@@ -413,26 +443,33 @@ class Model:
                     int(n_seq), int(max_new), int(eos_id), int(sync_every), toks.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), n.ctypes.data_as(ip),
                     stop.ctypes.data_as(ip), tr.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if tr is not None else None, ctypes.byref(ms),
                     float(temperature), int(top_k), float(top_p), sd.ctypes.data_as(ctypes.POINTER(ctypes.c_ulonglong)) if sd is not None else None,
-                    int(draw_base) & (2 ** 64 - 1)))
+                    int(draw_base) & (2 ** 64 - 1), *([ctypes.byref(ext)] if ext is not None else [])))
         return ([toks[s, :n[s]].copy() for s in range(ns)], stop, [tr[s, :n[s]].copy() for s in range(ns)] if tr is not None else None, ms.value)
 
     def turn(self, prompt, max_new: int, n_caches: int, chunk: int = 32, capacity: int = 0, eos_id: int = -1, sync_every: int = 0, trace: bool = False,
              vocab: int = 0, ids: str = "input_ids", pos: str = "position_ids", mask: str = "attention_mask", logits: str = "logits", cache_in: str = "pkv",
-             cache_out: str = "opkv", temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, draw_base: int = 0):
+             cache_out: str = "opkv", temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, draw_base: int = 0,
+             repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0, min_p: float = 0.0, history=None):
         """One chat turn on the device (model_hip_turn): the prompt's tokens run in chunks of `chunk` rows over the conversation's caches (`cache_out`<i> as
         a run() or a turn left them, else `cache_in`<i> as pushed -- zero rows on the first turn), then up to max_new tokens are picked and run as `generate`
         does, the first from the prefill's own last logits row; nothing comes back to the host in between.  Leaves the caches of P + len(prompt) + n_tokens
         rows and `logits` [1, 1, V] of the last pass that ran.  capacity > 0 asks for capacity buffers of at least that many rows, so that later turns
         rebuild no plan.  trace needs `vocab` (the width of a logits row) unless a logits tensor is in the Model.  Returns what `generate` returns:
-        (tokens, stop, trace or None, device ms of the whole turn)."""
+        (tokens, stop, trace or None, device ms of the whole turn).
+        repetition_penalty, presence_penalty, frequency_penalty, min_p: as `generate` (model_hip_turn_ext).  history: the tokens the penalties count from
+        the start; None = this turn's prompt (the export itself adds nothing: an earlier turn's tokens count only when the caller passes them)."""
         import numpy as np
         cp, ip = ctypes.c_char_p, ctypes.POINTER(ctypes.c_int)
-        f = self._lib.model_hip_turn
+        pr = np.ascontiguousarray(np.asarray(prompt, np.int64).reshape(-1))
+        ext, _hist = sample_ext(repetition_penalty, presence_penalty, frequency_penalty, min_p, history)
+        if ext is not None and history is None:
+            ext, _hist = sample_ext(repetition_penalty, presence_penalty, frequency_penalty, min_p, pr)
+        f = self._lib.model_hip_turn if ext is None else self._lib.model_hip_turn_ext
         f.argtypes = [ctypes.c_void_p, cp, cp, cp, cp, cp, cp, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), ctypes.c_int, ctypes.c_int, ctypes.c_longlong,
                       ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.POINTER(ctypes.c_longlong), ip, ip, ctypes.POINTER(ctypes.c_float),
-                      ctypes.POINTER(ctypes.c_double), ctypes.c_float, ctypes.c_longlong, ctypes.c_float, ctypes.c_ulonglong, ctypes.c_ulonglong]
+                      ctypes.POINTER(ctypes.c_double), ctypes.c_float, ctypes.c_longlong, ctypes.c_float, ctypes.c_ulonglong, ctypes.c_ulonglong] + (
+                          [ctypes.POINTER(SampleExt)] if ext is not None else [])
         f.restype = ctypes.c_void_p
-        pr = np.ascontiguousarray(np.asarray(prompt, np.int64).reshape(-1))
         toks = np.zeros(max(int(max_new), 1), np.int64)
         tr = None
         if trace:
@@ -448,7 +485,7 @@ class Model:
                     pr.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)) if pr.size else None, int(pr.size), int(chunk), int(capacity), int(max_new), int(eos_id),
                     int(sync_every), toks.ctypes.data_as(ctypes.POINTER(ctypes.c_longlong)), ctypes.byref(n), ctypes.byref(stop),
                     tr.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if tr is not None else None, ctypes.byref(ms), float(temperature), int(top_k), float(top_p),
-                    int(seed) & (2 ** 64 - 1), int(draw_base) & (2 ** 64 - 1)))
+                    int(seed) & (2 ** 64 - 1), int(draw_base) & (2 ** 64 - 1), *([ctypes.byref(ext)] if ext is not None else [])))
         return toks[:n.value].copy(), stop.value, (tr[:n.value].copy() if tr is not None else None), ms.value
 
     def hip_prefill_plan_info(self) -> str:

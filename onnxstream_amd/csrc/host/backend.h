@@ -25,7 +25,7 @@ namespace onnxstream {
     X(osg_attention_strided) X(osg_sdpa) X(osg_rms_norm) X(osg_rope) X(osg_instance_norm) X(osg_group_norm_nhwc) X(osg_layer_norm) \
     X(osg_reduce_mean_last) X(osg_softmax_last) X(osg_unary) X(osg_binary) X(osg_geglu) X(osg_transpose) \
     X(osg_copy_2d) X(osg_concat2) X(osg_resize_nearest) X(osg_gather_rows) X(osg_maxpool_nhwc) X(osg_convert) \
-    X(osg_sampler_prepare) X(osg_sampler_cfg_euler_a) X(osg_sampler_cfg_multistep) X(osg_sampler_prepare_rescale) X(osg_sampler_prepare_single) X(osg_sampler_euler_a_single) X(osg_sampler_multistep_single) X(osg_sampler_cfg_stochastic) X(osg_sampler_stochastic_single) X(osg_decode_gather) X(osg_decode_blend) X(osg_decode_pick) X(osg_decode_sample) X(osg_kv_append_at) X(osg_sdpa_len) X(osg_decode_sample_batch) X(osg_kv_append_at_batch) X(osg_sdpa_len_batch) X(osg_rope_batch) X(osg_sdpa_chunk) X(osg_kv_append_rows_at) X(osg_prefill_stage) X(osg_qu8_conv2d_nhwc) X(osg_qu8_conv2d_nhwc_t) X(osg_qu8_conv_tap_sums) X(osg_qu8_gemm) X(osg_qu8_lut) X(osg_qu8_binary) \
+    X(osg_sampler_prepare) X(osg_sampler_cfg_euler_a) X(osg_sampler_cfg_multistep) X(osg_sampler_prepare_rescale) X(osg_sampler_prepare_single) X(osg_sampler_euler_a_single) X(osg_sampler_multistep_single) X(osg_sampler_cfg_stochastic) X(osg_sampler_stochastic_single) X(osg_decode_gather) X(osg_decode_blend) X(osg_decode_pick) X(osg_decode_sample) X(osg_kv_append_at) X(osg_sdpa_len) X(osg_decode_sample_batch) X(osg_kv_append_at_batch) X(osg_sdpa_len_batch) X(osg_rope_batch) X(osg_sdpa_chunk) X(osg_kv_append_rows_at) X(osg_prefill_stage) X(osg_decode_count) X(osg_decode_penalize) X(osg_decode_pick_ext) X(osg_decode_sample_ext) X(osg_decode_sample_batch_ext) X(osg_qu8_conv2d_nhwc) X(osg_qu8_conv2d_nhwc_t) X(osg_qu8_conv_tap_sums) X(osg_qu8_gemm) X(osg_qu8_lut) X(osg_qu8_binary) \
     X(osg_qu8_instance_norm) X(osg_qu8_instance_norm_nhwc) X(osg_qu8_affine_act) X(osg_qu8_norm_affine_act_nhwc) X(osg_qu8_softmax_last) X(osg_range_push) X(osg_range_pop) X(osg_marker_record) \
     X(osg_copy_wait_marker) X(osg_timer_mark) X(osg_timer_between) X(osg_tblock_tail_supported) X(osg_tblock_tail) X(osg_tblock_kv_pack_elems) X(osg_tblock_kv_pack_jobs) X(osg_tblock_pack_weight)
 

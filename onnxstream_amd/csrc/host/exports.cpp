@@ -474,6 +474,34 @@ char* model_hip_generate(Handle* h, const char* ids_name, const char* pos_name, 
         return Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, Plan::SampleRule());
     });
 }
+// repetition, presence and frequency penalties, min-p and the token history they count over (include/osgpu.h states steps 0 and 3b of the rule): the last
+// argument of the three _ext calls below.  NULL is the call without the suffix.  The history is what the caller passes -- model_hip_turn_ext does not add
+// the prompt by itself; every sequence of a batch starts from the same history.  Refused, each with the call's own prefix: a repetition penalty that is
+// NaN, <= 0, infinite or whose fp32 reciprocal is not finite; a presence or frequency penalty that is NaN or infinite (negative values are allowed); min_p
+// NaN, < 0 or > 1; min_p > 0 with temperature == 0; a history token outside [0, V); n_history < 0, or history == NULL with n_history > 0;
+// n_history + max_new >= 2^24.  With a penalty active and temperature == 0 the greedy pick runs over the adjusted logits.  logits_trace keeps the raw logits.
+struct model_hip_sample_ext {
+    float repetition_penalty, presence_penalty, frequency_penalty, min_p;
+    const long long* history;
+    long long n_history;
+};
+static void apply_ext(Plan::SampleRule& rule, const model_hip_sample_ext* ext) {
+    if (!ext) return;
+    rule.repetition = ext->repetition_penalty; rule.presence = ext->presence_penalty; rule.frequency = ext->frequency_penalty; rule.min_p = ext->min_p;
+    rule.history = ext->history; rule.n_history = ext->n_history;
+}
+char* model_hip_generate_sampled_ext(Handle* h, const char* ids_name, const char* pos_name, const char* mask_name, const char* logits_name,
+                                     const char* cache_in_prefix, const char* cache_out_prefix, int n_caches, int max_new, long long eos_id, int sync_every,
+                                     long long* tokens, int* n_tokens, int* stop, float* logits_trace, double* ms, float temperature, long long top_k, float top_p,
+                                     unsigned long long seed, unsigned long long draw_base, const model_hip_sample_ext* ext);
+char* model_hip_generate_batch_ext(Handle* h, const char* ids_name, const char* pos_name, const char* mask_name, const char* logits_name,
+                                   const char* cache_in_prefix, const char* cache_out_prefix, int n_caches, int n_seq, int max_new, long long eos_id,
+                                   int sync_every, long long* tokens, int* n_tokens, int* stop, float* logits_trace, double* ms, float temperature,
+                                   long long top_k, float top_p, const unsigned long long* seeds, unsigned long long draw_base, const model_hip_sample_ext* ext);
+char* model_hip_turn_ext(Handle* h, const char* ids_name, const char* pos_name, const char* mask_name, const char* logits_name, const char* cache_in_prefix,
+                         const char* cache_out_prefix, int n_caches, const long long* prompt, int n_prompt, int chunk, long long capacity, int max_new,
+                         long long eos_id, int sync_every, long long* tokens, int* n_tokens, int* stop, float* logits_trace, double* ms, float temperature,
+                         long long top_k, float top_p, unsigned long long seed, unsigned long long draw_base, const model_hip_sample_ext* ext);
 // model_hip_generate with a sampling rule in the argmax's place (osg_decode_sample, include/osgpu.h states the rule in full): temperature > 0 divides the
 // logits, top_k > 0 keeps the k largest, top_p < 1 the shortest prefix that holds that share of the mass, and the token is drawn with Philox4x32-10 keyed by
 // `seed` at draw index draw_base + n_tokens -- so a call of N tokens equals calls of a and N - a tokens, the second with draw_base = a.  temperature = 0
@@ -484,12 +512,20 @@ char* model_hip_generate_sampled(Handle* h, const char* ids_name, const char* po
                                  const char* cache_out_prefix, int n_caches, int max_new, long long eos_id, int sync_every, long long* tokens, int* n_tokens,
                                  int* stop, float* logits_trace, double* ms, float temperature, long long top_k, float top_p, unsigned long long seed,
                                  unsigned long long draw_base) {
+    return model_hip_generate_sampled_ext(h, ids_name, pos_name, mask_name, logits_name, cache_in_prefix, cache_out_prefix, n_caches, max_new, eos_id, sync_every,
+                                          tokens, n_tokens, stop, logits_trace, ms, temperature, top_k, top_p, seed, draw_base, nullptr);
+}
+char* model_hip_generate_sampled_ext(Handle* h, const char* ids_name, const char* pos_name, const char* mask_name, const char* logits_name,
+                                     const char* cache_in_prefix, const char* cache_out_prefix, int n_caches, int max_new, long long eos_id, int sync_every,
+                                     long long* tokens, int* n_tokens, int* stop, float* logits_trace, double* ms, float temperature, long long top_k, float top_p,
+                                     unsigned long long seed, unsigned long long draw_base, const model_hip_sample_ext* ext) {
     return guarded(ms, [&] {
         Plan::DecodeSpec spec;
         spec.ids = ids_name; spec.pos = pos_name; spec.mask = mask_name; spec.logits = logits_name;
         spec.cache_in = cache_in_prefix; spec.cache_out = cache_out_prefix; spec.n_caches = n_caches;
         Plan::SampleRule rule;
         rule.temperature = temperature; rule.top_k = (long)top_k; rule.top_p = top_p; rule.seed = seed; rule.draw_base = draw_base;
+        apply_ext(rule, ext);
         return Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, rule);
     });
 }
@@ -506,12 +542,20 @@ char* model_hip_generate_batch(Handle* h, const char* ids_name, const char* pos_
                                const char* cache_out_prefix, int n_caches, int n_seq, int max_new, long long eos_id, int sync_every, long long* tokens,
                                int* n_tokens, int* stop, float* logits_trace, double* ms, float temperature, long long top_k, float top_p,
                                const unsigned long long* seeds, unsigned long long draw_base) {
+    return model_hip_generate_batch_ext(h, ids_name, pos_name, mask_name, logits_name, cache_in_prefix, cache_out_prefix, n_caches, n_seq, max_new, eos_id,
+                                        sync_every, tokens, n_tokens, stop, logits_trace, ms, temperature, top_k, top_p, seeds, draw_base, nullptr);
+}
+char* model_hip_generate_batch_ext(Handle* h, const char* ids_name, const char* pos_name, const char* mask_name, const char* logits_name,
+                                   const char* cache_in_prefix, const char* cache_out_prefix, int n_caches, int n_seq, int max_new, long long eos_id,
+                                   int sync_every, long long* tokens, int* n_tokens, int* stop, float* logits_trace, double* ms, float temperature,
+                                   long long top_k, float top_p, const unsigned long long* seeds, unsigned long long draw_base, const model_hip_sample_ext* ext) {
     return guarded(ms, [&] {
         Plan::DecodeSpec spec;
         spec.ids = ids_name; spec.pos = pos_name; spec.mask = mask_name; spec.logits = logits_name;
         spec.cache_in = cache_in_prefix; spec.cache_out = cache_out_prefix; spec.n_caches = n_caches;
         Plan::SampleRule rule;
         rule.temperature = temperature; rule.top_k = (long)top_k; rule.top_p = top_p; rule.draw_base = draw_base;
+        apply_ext(rule, ext);
         return Plan::generate(h->model, spec, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, rule, n_seq, seeds, true);
     });
 }
@@ -538,12 +582,20 @@ char* model_hip_turn(Handle* h, const char* ids_name, const char* pos_name, cons
                      const char* cache_out_prefix, int n_caches, const long long* prompt, int n_prompt, int chunk, long long capacity, int max_new,
                      long long eos_id, int sync_every, long long* tokens, int* n_tokens, int* stop, float* logits_trace, double* ms, float temperature,
                      long long top_k, float top_p, unsigned long long seed, unsigned long long draw_base) {
+    return model_hip_turn_ext(h, ids_name, pos_name, mask_name, logits_name, cache_in_prefix, cache_out_prefix, n_caches, prompt, n_prompt, chunk, capacity,
+                              max_new, eos_id, sync_every, tokens, n_tokens, stop, logits_trace, ms, temperature, top_k, top_p, seed, draw_base, nullptr);
+}
+char* model_hip_turn_ext(Handle* h, const char* ids_name, const char* pos_name, const char* mask_name, const char* logits_name, const char* cache_in_prefix,
+                         const char* cache_out_prefix, int n_caches, const long long* prompt, int n_prompt, int chunk, long long capacity, int max_new,
+                         long long eos_id, int sync_every, long long* tokens, int* n_tokens, int* stop, float* logits_trace, double* ms, float temperature,
+                         long long top_k, float top_p, unsigned long long seed, unsigned long long draw_base, const model_hip_sample_ext* ext) {
     return guarded(ms, [&] {
         Plan::DecodeSpec spec;
         spec.ids = ids_name; spec.pos = pos_name; spec.mask = mask_name; spec.logits = logits_name;
         spec.cache_in = cache_in_prefix; spec.cache_out = cache_out_prefix; spec.n_caches = n_caches;
         Plan::SampleRule rule;
         rule.temperature = temperature; rule.top_k = (long)top_k; rule.top_p = top_p; rule.seed = seed; rule.draw_base = draw_base;
+        apply_ext(rule, ext);
         return Plan::turn(h->model, spec, prompt, n_prompt, chunk, capacity, max_new, eos_id, sync_every, (int64_t*)tokens, n_tokens, stop, logits_trace, rule);
     });
 }

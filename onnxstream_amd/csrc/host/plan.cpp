@@ -421,6 +421,9 @@ Plan::~Plan() {
     if (dec_tokens) be.api.osg_free(be.ctx, dec_tokens);
     if (dec_trace) be.api.osg_free(be.ctx, dec_trace);
     if (dec_seeds) be.api.osg_free(be.ctx, dec_seeds);
+    if (dec_counts) be.api.osg_free(be.ctx, dec_counts);
+    if (dec_adjusted) be.api.osg_free(be.ctx, dec_adjusted);
+    if (dec_history) be.api.osg_free(be.ctx, dec_history);
     if (ring) be.free(ring);
     for (void* p : owned) be.free(p);
     if (arena && !arena_pooled) be.free(arena);

@@ -379,12 +379,27 @@ struct Plan {
     void* dec_trace = nullptr;                // device fp32 [N][max_new, V]
     void* dec_seeds = nullptr;                // device uint64 [N]: the seeds of a generate_batch call
     size_t dec_tokens_bytes = 0, dec_trace_bytes = 0, dec_seeds_bytes = 0;
+    // penalties and min-p (SampleRule below): kept with the decode plan, allocated by the first call that needs them, no part of its key, capture or text
+    void* dec_counts = nullptr;               // device int32 [N][V]: how often sequence s has seen token i (history + what it appended)
+    void* dec_adjusted = nullptr;             // device fp32 [N][V]: the logits after step 0 (osg_decode_penalize), what the pick / sample then reads
+    void* dec_history = nullptr;              // device int64 [n_history]: the caller's history, uploaded per call
+    size_t dec_counts_bytes = 0, dec_adjusted_bytes = 0, dec_history_bytes = 0;
     int cache_index(const std::string& name, const std::string& prefix) const;   // i of "<prefix><i>", i < n_caches; -1 otherwise
     // the reference app's token loop (src/llm.cpp:472-496) on the device: see model_hip_generate (exports.cpp) for the contract.  A static member of Plan
     // for the reason given at on_plan_of; the decode plan itself is kept in the Model's ConstPool.
     // how a token is taken from the logits: default-constructed = greedy, the app's argmax (osg_decode_pick); temperature > 0 = the sampling rule of
     // include/osgpu.h (osg_decode_sample).  Sampling is outside the decode plan: the plan, its capacity, its capture and its text are the same either way.
-    struct SampleRule { float temperature = 0.0f; long top_k = 0; float top_p = 1.0f; unsigned long long seed = 0, draw_base = 0; };
+    // repetition / presence / frequency / min_p and the history (host int64 [n_history]): step 0 and step 3b of the rule.  counted() = the loop keeps the
+    // count table and hands it to the _ext entry points; penalized() = step 0 changes a logit, so osg_decode_penalize runs before every pick.
+    struct SampleRule {
+        float temperature = 0.0f; long top_k = 0; float top_p = 1.0f; unsigned long long seed = 0, draw_base = 0;
+        float repetition = 1.0f, presence = 0.0f, frequency = 0.0f, min_p = 0.0f;
+        const long long* history = nullptr; long long n_history = 0;
+        bool penalized() const { return repetition != 1.0f || presence != 0.0f || frequency != 0.0f; }
+        bool extended() const { return penalized() || min_p != 0.0f; }
+        // what every call refuses, `fn` its prefix; V < 0: the vocabulary is not known yet (the history's tokens are checked once it is)
+        void check(const std::string& fn, long long max_new, long V) const;
+    };
     // batch (model_hip_generate_batch): n_seq sampled sequences from the one prompt in a decode plan of batch n_seq, sequence s with seeds[s] and its own
     // state, caches and stop; the outputs are arrays over the sequences and m_data is left untouched.  n_seq is part of the decode plan's key.
     // entry (Plan::turn): the loop starts from what a prefill leaves on the device instead of from m_data -- caches of P rows in capacity buffers of

@@ -997,6 +997,23 @@ std::string Plan::decode_info(Model& m) {
     return m.m_pool->decode_plan->info();
 }
 
+// what model_hip_generate_sampled_ext, _batch_ext and model_hip_turn_ext refuse of the four controls and the history (exports.cpp lists it)
+void Plan::SampleRule::check(const std::string& fn, long long max_new, long V) const {
+    if (!(repetition > 0.0f) || std::isinf(repetition) || !std::isfinite(1.0f / repetition))
+        throw std::invalid_argument(fn + "repetition_penalty must be > 0 and finite, with a finite 1 / repetition_penalty (1 = off).");
+    if (!std::isfinite(presence)) throw std::invalid_argument(fn + "presence_penalty must be finite (0 = off).");
+    if (!std::isfinite(frequency)) throw std::invalid_argument(fn + "frequency_penalty must be finite (0 = off).");
+    if (!(min_p >= 0.0f) || !(min_p <= 1.0f)) throw std::invalid_argument(fn + "min_p must be in [0, 1] (0 = off).");
+    if (min_p > 0.0f && temperature == 0.0f) throw std::invalid_argument(fn + "min_p needs temperature > 0 (the greedy pick keeps one token anyway).");
+    if (n_history < 0) throw std::invalid_argument(fn + "n_history must be >= 0.");
+    if (n_history > 0 && !history) throw std::invalid_argument(fn + "no history tokens (n_history > 0).");
+    if (n_history + std::max(max_new, 0LL) >= (1LL << 24))
+        throw std::invalid_argument(fn + "n_history + max_new must be below 2^24 (a count must stay exact in fp32).");
+    for (long long i = 0; i < n_history && V >= 0; i++)
+        if (history[i] < 0 || history[i] >= V)
+            throw std::invalid_argument(fn + "history token " + std::to_string(history[i]) + " at " + std::to_string(i) + " is outside [0, " + std::to_string(V) + ").");
+}
+
 // The reference app's token loop (src/llm.cpp:472-496) with the argmax, the cache append and the cache length on the device: max_new x (osg_decode_pick + the
 // T = 1 pass of the Model's resident decode plan) enqueued back to back.  model_hip_generate (exports.cpp) states the contract.  With a sampling rule
 // (model_hip_generate_sampled) osg_decode_sample stands where the pick stands; nothing else differs.
@@ -1018,6 +1035,7 @@ double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long 
     if (rule.temperature > 0.0f && std::isinf(1.0f / rule.temperature)) throw std::invalid_argument(fn + "temperature is too small: 1 / temperature is not finite.");
     if (rule.top_k < 0) throw std::invalid_argument(fn + "top_k must be >= 0 (0 = off).");
     if (!(rule.top_p > 0.0f) || !(rule.top_p <= 1.0f)) throw std::invalid_argument(fn + "top_p must be in (0, 1] (1 = off).");
+    rule.check(fn, max_new, -1);
     if (names.n_caches <= 0) throw std::invalid_argument(fn + "needs at least one key/value cache.");
     if (!m.m_plan || !m.m_backend || !m.m_pool || m.m_plan->runs < 1)
         throw std::runtime_error(fn + "run() once first (the prompt's logits and key/value caches must be in the Model).");
@@ -1064,6 +1082,7 @@ double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long 
             geo.push_back({(long)c.m_shape[1], (long)c.m_shape[3]});
         }
     }
+    rule.check(fn, max_new, V);      // (the history's tokens, now that V is known)
     if (max_new == 0) return 0.0;
     HipBackend& be = *m.m_backend;
     ConstPool& pool = *m.m_pool;
@@ -1174,6 +1193,25 @@ double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long 
     for (int s = 0; s < n_seq; s++) { st[4 * (size_t)s] = -1; st[4 * (size_t)s + 1] = (int)P; }
     be.check(be.api.osg_upload(be.ctx, dp->dec_state, st.data(), st.size() * sizeof(int)), "osg_upload");
     if (batch) be.check(be.api.osg_upload(be.ctx, dp->dec_seeds, seeds, (size_t)n_seq * 8), "osg_upload");
+    // penalties: the count table [n_seq][V], zeroed and filled from the history per call (every sequence starts from the same history), and the row
+    // step 0 writes; min-p alone needs neither.  With all four controls off nothing here runs and the loop below launches what it always launched.
+    const bool penalized = rule.penalized(), extended = rule.extended();
+    int* counts = nullptr;
+    float* adjusted = nullptr;
+    if (penalized) {
+        dp->grow_buffer(dp->dec_counts, dp->dec_counts_bytes, (size_t)n_seq * V * sizeof(int));
+        dp->grow_buffer(dp->dec_adjusted, dp->dec_adjusted_bytes, (size_t)n_seq * V * sizeof(float));
+        counts = (int*)dp->dec_counts;
+        adjusted = (float*)dp->dec_adjusted;
+        be.check(be.api.osg_memset(be.ctx, counts, 0, (size_t)n_seq * V * sizeof(int)), "osg_memset");
+        if (rule.n_history > 0) {
+            dp->grow_buffer(dp->dec_history, dp->dec_history_bytes, (size_t)rule.n_history * 8);
+            be.check(be.api.osg_upload(be.ctx, dp->dec_history, rule.history, (size_t)rule.n_history * 8), "osg_upload");
+            for (int s = 0; s < n_seq; s++)
+                be.check(be.api.osg_decode_count(be.ctx, (const int64_t*)dp->dec_history, (long)rule.n_history, counts + (size_t)s * V, V), "osg_decode_count");
+        }
+    }
+    const float inv_r = 1.0f / rule.repetition;
     const std::vector<int64_t> zeros((size_t)n_seq, 0);
     be.check(be.api.osg_upload(be.ctx, dp->ptr(in_ids->staging), zeros.data(), zeros.size() * 8), "osg_upload");
     be.check(be.api.osg_upload(be.ctx, dp->ptr(in_pos->staging), zeros.data(), zeros.size() * 8), "osg_upload");
@@ -1214,7 +1252,23 @@ double Plan::generate(Model& m, const DecodeSpec& names, int max_new, long long 
     int passes = 0;
     if (!entry) be.check(be.api.osg_timer_start(be.ctx), "osg_timer_start");      // (a turn's time starts at its first chunk)
     for (int n = 0; n < max_new; n++) {
-        if (batch)
+        if (penalized)      // step 0 into the scratch rows; the logits buffer (and with it the trace) keeps what the model computed
+            be.check(be.api.osg_decode_penalize(be.ctx, lg_dev, V, V, n_seq, counts, adjusted, rule.repetition, inv_r, rule.presence, rule.frequency),
+                     "osg_decode_penalize");
+        const float* from = penalized ? adjusted : lg_dev;
+        if (batch && extended)
+            be.check(be.api.osg_decode_sample_batch_ext(be.ctx, from, V, n_seq, eos_id, dp->dec_state, ids_dev, pos_dev, (int64_t*)dp->dec_tokens, max_new,
+                                                        rule.temperature, rule.top_k, rule.top_p, (const unsigned long long*)dp->dec_seeds, rule.draw_base,
+                                                        rule.min_p, counts),
+                     "osg_decode_sample_batch_ext");
+        else if (extended && rule.temperature > 0.0f)
+            be.check(be.api.osg_decode_sample_ext(be.ctx, from, 1, V, eos_id, dp->dec_state, ids_dev, pos_dev, (int64_t*)dp->dec_tokens, max_new, rule.temperature,
+                                                  rule.top_k, rule.top_p, rule.seed, rule.draw_base, rule.min_p, counts),
+                     "osg_decode_sample_ext");
+        else if (extended)
+            be.check(be.api.osg_decode_pick_ext(be.ctx, from, 1, V, eos_id, dp->dec_state, ids_dev, pos_dev, (int64_t*)dp->dec_tokens, max_new, counts),
+                     "osg_decode_pick_ext");
+        else if (batch)
             be.check(be.api.osg_decode_sample_batch(be.ctx, lg_dev, V, n_seq, eos_id, dp->dec_state, ids_dev, pos_dev, (int64_t*)dp->dec_tokens, max_new,
                                                     rule.temperature, rule.top_k, rule.top_p, (const unsigned long long*)dp->dec_seeds, rule.draw_base),
                      "osg_decode_sample_batch");
@@ -1360,6 +1414,7 @@ double Plan::turn(Model& m, const DecodeSpec& names, const long long* prompt, in
     if (rule.temperature > 0.0f && std::isinf(1.0f / rule.temperature)) throw std::invalid_argument(fn + "temperature is too small: 1 / temperature is not finite.");
     if (rule.top_k < 0) throw std::invalid_argument(fn + "top_k must be >= 0 (0 = off).");
     if (!(rule.top_p > 0.0f) || !(rule.top_p <= 1.0f)) throw std::invalid_argument(fn + "top_p must be in (0, 1] (1 = off).");
+    rule.check(fn, max_new, -1);
     if (names.n_caches <= 0) throw std::invalid_argument(fn + "needs at least one key/value cache.");
     if (!m.m_plan || !m.m_backend || !m.m_pool || m.m_plan->runs < 1)
         throw std::runtime_error(fn + "run() once first (the weights must be on the device; the app's weight-loading pass counts).");
@@ -1495,6 +1550,7 @@ double Plan::turn(Model& m, const DecodeSpec& names, const long long* prompt, in
     if (V > cp->dec_tok_limit)
         throw std::invalid_argument(fn + "the logits name " + std::to_string(V) + " tokens, the smallest table indexed by '" + names.ids + "' has " +
                                     std::to_string(cp->dec_tok_limit) + " rows.");
+    rule.check(fn, max_new, V);
     for (int i = 0; i < n_prompt; i++)
         if (prompt[i] < 0 || prompt[i] >= cp->dec_tok_limit)
             throw std::invalid_argument(fn + "prompt token " + std::to_string(prompt[i]) + " at " + std::to_string(i) + " is outside the smallest table indexed by '" + names.ids +

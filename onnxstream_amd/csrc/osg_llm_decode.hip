@@ -5,6 +5,9 @@
 //                       argmax set the stop code, after which every further launch is a predicated no-op
 //   osg_decode_sample <- in the pick's place when the caller samples: temperature, top-k, top-p and a seeded draw over the same row by the integer rule
 //                       of include/osgpu.h, then the same state advance
+//   osg_decode_count, osg_decode_penalize, osg_decode_*_ext <- repetition, presence and frequency penalties and min-p: a count per vocabulary entry on the
+//                       device, step 0 of the rule as a launch of its own into a scratch row (the radix passes read adjusted logits as they read raw
+//                       ones), the min-p compare inside the weights, and the count of the appended token raised by the thread that appends it
 //   osg_kv_append_at <- the cache Concat (pkv ++ new row, axis 2) in place: the new row of every head into a capacity buffer at the device-side row
 //   osg_decode_sample_batch, osg_kv_append_at_batch <- the same two for n_seq sequences side by side, each with its own state (model_hip_generate_batch)
 //   osg_kv_append_rows_at, osg_prefill_stage <- the prompt's half of a chat turn (model_hip_turn): the C new rows of a prefill chunk into the capacity
@@ -25,7 +28,7 @@ constexpr int kPickThreads = 1024;
 
 __global__ __launch_bounds__(kPickThreads) void decode_pick_kernel(const float* __restrict__ row, long V, long long eos_id, int* __restrict__ state,
                                                                    int64_t* __restrict__ input_ids, int64_t* __restrict__ position_ids,
-                                                                   int64_t* __restrict__ tokens, long max_tokens) {
+                                                                   int64_t* __restrict__ tokens, long max_tokens, int* __restrict__ counts) {
     // stopped, or the token budget of this call is spent: nothing is read or written any more (uniform: every lane sees the same state)
     if (state[3] != 0 || (long)state[2] >= max_tokens) return;
     __shared__ float sv[kPickThreads / 64];
@@ -57,6 +60,7 @@ __global__ __launch_bounds__(kPickThreads) void decode_pick_kernel(const float* 
     state[0] = len;
     state[1] = len + 1;
     state[2] = n + 1;
+    if (counts) counts[tok] += 1;   // (one thread, one launch at a time on the stream: no atomic needed)
 }
 
 // ---- osg_decode_sample: the rule of include/osgpu.h.  One workgroup; every pass re-reads the row (coalesced, out of L1 / L2), nothing is sorted. ----
@@ -83,9 +87,12 @@ __device__ __forceinline__ uint32_t sample_key(float v) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float sample_key_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-// q of step 3: floor(min(exp((v - m) * inv_t), 1) * 2^32); the product by 2^32 is exact, the conversion truncates
-__device__ __forceinline__ u64 sample_q(float v, float m, float inv_t) {
-    const float w = fminf(expf((v - m) * inv_t), 1.0f);
+// q of step 3: floor(min(exp((v - m) * inv_t), 1) * 2^32); the product by 2^32 is exact, the conversion truncates.  Step 3b (min-p) is the compare
+// on x: a token under x_min has no mass, as one whose q is 0 (x_min = -inf: off, the compare is never true -- x is no NaN here)
+__device__ __forceinline__ u64 sample_q(float v, float m, float inv_t, float x_min) {
+    const float x = (v - m) * inv_t;
+    if (x < x_min) return 0;
+    const float w = fminf(expf(x), 1.0f);
     return (u64)(w * 4294967296.0f);
 }
 // the composite of element i with value v; false for a NaN.  -0.0 and +0.0 are one value: both take the key of +0.0
@@ -167,8 +174,8 @@ __device__ __forceinline__ u64 wave_scan(u64 s, int lane) {   // inclusive, lane
 // Seven digits from the top: the four bytes of the key, then the index as 8 + 8 + 4 bits.  It ends early once a whole bin is kept, which is the
 // usual case after the key's four bytes (one token holds that key, or all its equals are kept): the lower bits of the cut are 0 then.
 template <bool MASS>
-__device__ u64 sample_select(const float* __restrict__ row, long V, int head, float m, float inv_t, u64 floor_c, u64 target, uint32_t pm, int ps,
-                             SampleShared& sh) {
+__device__ u64 sample_select(const float* __restrict__ row, long V, int head, float m, float inv_t, float x_min, u64 floor_c, u64 target, uint32_t pm,
+                             int ps, SampleShared& sh) {
     const int tid = threadIdx.x, lane = tid & 63;
     u64 prefix = 0, above = 0;
     for (int d = 0; d < 7; d++) {
@@ -183,7 +190,7 @@ __device__ u64 sample_select(const float* __restrict__ row, long V, int head, fl
             u64 w = 1;
             if (MASS) {
                 if (c < floor_c) return;
-                w = sample_q(v, m, inv_t);
+                w = sample_q(v, m, inv_t, x_min);
                 if (w == 0) return;
             }
             atomicAdd(&sh.hist[((c >> shift) & (u64)((1 << bits) - 1)) * kHistCopies + (lane & (kHistCopies - 1))], w);
@@ -226,7 +233,7 @@ __device__ u64 sample_select(const float* __restrict__ row, long V, int head, fl
         target = sh.bc[3];
         if (above + binw == target) return prefix;
         if (MASS && d == 3) {   // one key, one q: the bin holds binw / q equal tokens, of which the ceil((target - above) / q) largest indices are kept
-            const u64 q = sample_q(sample_key_value((uint32_t)(prefix >> 20)), m, inv_t);
+            const u64 q = sample_q(sample_key_value((uint32_t)(prefix >> 20)), m, inv_t, x_min);
             if ((target - above + q - 1) / q * q == binw) return prefix;
         }
     }
@@ -254,7 +261,8 @@ __device__ __forceinline__ u64 sample_philox(u64 seed, u64 n) {
 // row, state, staging slots, token list and seed -- ONE body, so the two cannot drift apart
 __device__ __forceinline__ void decode_sample_body(const float* __restrict__ row, long V, long long eos_id, int* __restrict__ state,
                                                    int64_t* __restrict__ input_ids, int64_t* __restrict__ position_ids, int64_t* __restrict__ tokens,
-                                                   long max_tokens, float inv_t, long top_k, uint32_t pm, int ps, u64 seed, u64 draw_base) {
+                                                   long max_tokens, float inv_t, long top_k, uint32_t pm, int ps, u64 seed, u64 draw_base, float x_min,
+                                                   int* __restrict__ counts) {
     const int n_tok = state[2];
     if (state[3] != 0 || (long)n_tok >= max_tokens) return;   // as osg_decode_pick: uniform, nothing is read or written any more
     __shared__ SampleShared sh;
@@ -286,9 +294,9 @@ __device__ __forceinline__ void decode_sample_body(const float* __restrict__ row
     }
     // ---- steps 2 and 4: the cut ----
     u64 cut = 0;
-    if (top_k > 0 && top_k < (long)cnt) cut = sample_select<false>(row, V, head, m, inv_t, 0, (u64)top_k, 0, 0, sh);
+    if (top_k > 0 && top_k < (long)cnt) cut = sample_select<false>(row, V, head, m, inv_t, x_min, 0, (u64)top_k, 0, 0, sh);
     if (pm != 0) {
-        const u64 p_cut = sample_select<true>(row, V, head, m, inv_t, cut, 0, pm, ps, sh);
+        const u64 p_cut = sample_select<true>(row, V, head, m, inv_t, x_min, cut, 0, pm, ps, sh);
         cut = p_cut > cut ? p_cut : cut;
     }
     // ---- step 5: the draw, in ascending index order, in two levels: wave w sums the indices [head + w * cw, head + (w + 1) * cw), every thread finds the
@@ -297,7 +305,7 @@ __device__ __forceinline__ void decode_sample_body(const float* __restrict__ row
     auto kept_q = [&](long i, float v) -> u64 {
         u64 c;
         if (!sample_comp(i, v, c) || c < cut) return 0;
-        return sample_q(v, m, inv_t);
+        return sample_q(v, m, inv_t, x_min);
     };
     auto block_q = [&](long i, long hi, const float (&v)[4], u64 (&q)[4]) -> u64 {   // (tokens at and past `hi` belong to the next range, or to nobody)
         u64 sum = 0;
@@ -395,23 +403,25 @@ __device__ __forceinline__ void decode_sample_body(const float* __restrict__ row
     state[0] = len;
     state[1] = len + 1;
     state[2] = n_tok + 1;
+    if (counts) counts[tok] += 1;   // (the one thread that appends)
 }
 
 __global__ __launch_bounds__(kSampleThreads) void decode_sample_kernel(const float* __restrict__ row, long V, long long eos_id, int* __restrict__ state,
                                                                        int64_t* __restrict__ input_ids, int64_t* __restrict__ position_ids,
                                                                        int64_t* __restrict__ tokens, long max_tokens, float inv_t, long top_k, uint32_t pm,
-                                                                       int ps, u64 seed, u64 draw_base) {
-    decode_sample_body(row, V, eos_id, state, input_ids, position_ids, tokens, max_tokens, inv_t, top_k, pm, ps, seed, draw_base);
+                                                                       int ps, u64 seed, u64 draw_base, float x_min, int* __restrict__ counts) {
+    decode_sample_body(row, V, eos_id, state, input_ids, position_ids, tokens, max_tokens, inv_t, top_k, pm, ps, seed, draw_base, x_min, counts);
 }
 
 // workgroup s = sequence s: everything it touches is indexed by blockIdx.x alone (uniform: the seed is one scalar load)
 __global__ __launch_bounds__(kSampleThreads) void decode_sample_batch_kernel(const float* __restrict__ logits, long V, long long eos_id, int* __restrict__ state,
                                                                              int64_t* __restrict__ input_ids, int64_t* __restrict__ position_ids,
                                                                              int64_t* __restrict__ tokens, long max_tokens, float inv_t, long top_k,
-                                                                             uint32_t pm, int ps, const u64* __restrict__ seeds, u64 draw_base) {
+                                                                             uint32_t pm, int ps, const u64* __restrict__ seeds, u64 draw_base, float x_min,
+                                                                             int* __restrict__ counts) {
     const long s = blockIdx.x;
     decode_sample_body(logits + s * V, V, eos_id, state + 4 * s, input_ids + s, position_ids + s, tokens + s * max_tokens, max_tokens, inv_t, top_k, pm, ps,
-                       seeds[s], draw_base);
+                       seeds[s], draw_base, x_min, counts ? counts + s * V : nullptr);
 }
 
 __global__ __launch_bounds__(256) void kv_append_at_batch_kernel(const uint16_t* __restrict__ src, uint16_t* __restrict__ cache, const int* __restrict__ state,
@@ -458,6 +468,68 @@ __global__ __launch_bounds__(256) void prefill_stage_kernel(const int64_t* __res
     if (threadIdx.x == 0) *base = (int)pos0;
 }
 
+// osg_decode_count: one thread per token; integer atomics, so the table does not depend on the order the threads arrive in
+__global__ __launch_bounds__(256) void decode_count_kernel(const int64_t* __restrict__ tokens, long n, int* __restrict__ counts, long V) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const long t = (long)tokens[i];
+    if (t < 0 || t >= V) return;
+    atomicAdd(&counts[t], 1);
+}
+
+// step 0 of the rule for one element: every product and sum is rounded on its own.  __fmul_rn and its kin are plain operators to this compiler, which
+// contracts a product and a sum into an fma by default: the pragma and the empty asm below are what keep the roundings apart.
+__device__ __forceinline__ float penalized(float l, int c, float r, float inv_r, float presence, float frequency) {
+#pragma clang fp contract(off)
+    if (c <= 0) return l;
+    float b = l > 0.0f ? __fmul_rn(l, inv_r) : __fmul_rn(l, r);
+    float f = __fmul_rn(frequency, (float)c);
+    asm volatile("" : "+v"(b), "+v"(f));   // (the products are opaque from here on: the code generator fuses across the pragma once it vectorises)
+    const float u = __fadd_rn(presence, f);
+    return __fsub_rn(b, u);
+}
+
+// osg_decode_penalize: blockIdx.y = the sequence.  A thread takes one 16-byte group of the row from its first aligned element on, as sample_for_each
+// lays a row out; the 0-3 elements before it and the 0-3 behind the last whole group go to the threads after the groups', one element each.  The counts
+// and the output are read and written 16 bytes at a time where their own rows stand as the logits row does, else element by element.
+__global__ __launch_bounds__(256) void decode_penalize_kernel(const float* __restrict__ rows, long row_stride, long V, const int* __restrict__ counts,
+                                                              float* __restrict__ out, float r, float inv_r, float presence, float frequency) {
+    const long s = blockIdx.y;
+    const float* __restrict__ row = rows + s * row_stride;
+    const int* __restrict__ cnt = counts + s * V;
+    float* __restrict__ o = out + s * V;
+    const int head = sample_head(row, V);
+    const long nvec = (V - head) / 4;
+    const long g = (long)blockIdx.x * 256 + threadIdx.x;
+    if (g < nvec) {
+        const long i = head + 4 * g;
+        const float4 x = *(const float4*)(row + i);
+        int c[4];
+        if ((((uintptr_t)(cnt + i)) & 15) == 0) {
+            const int4 cc = *(const int4*)(cnt + i);
+            c[0] = cc.x; c[1] = cc.y; c[2] = cc.z; c[3] = cc.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) c[k] = cnt[i + k];
+        }
+        float4 y;
+        y.x = penalized(x.x, c[0], r, inv_r, presence, frequency);
+        y.y = penalized(x.y, c[1], r, inv_r, presence, frequency);
+        y.z = penalized(x.z, c[2], r, inv_r, presence, frequency);
+        y.w = penalized(x.w, c[3], r, inv_r, presence, frequency);
+        if ((((uintptr_t)(o + i)) & 15) == 0) *(float4*)(o + i) = y;
+        else { o[i] = y.x; o[i + 1] = y.y; o[i + 2] = y.z; o[i + 3] = y.w; }
+        return;
+    }
+    // the head [0, head), then the tail [head + 4 nvec, V): at most six elements in all
+    long e = g - nvec;
+    if (e >= head) e = head + 4 * nvec + (e - head);
+    if (e < V) o[e] = penalized(row[e], cnt[e], r, inv_r, presence, frequency);
+}
+
+// min_p's x_min: the fp32 nearest to the double-precision log of min_p's fp32 value; 0 turns the step off
+float min_p_x(float min_p) { return min_p > 0.0f ? (float)std::log((double)min_p) : -INFINITY; }
+
 // top_p = pm * 2^-ps exactly, pm < 2^24 (the fp32 significand as an integer); pm = 0 says top-p is off
 void split_top_p(float top_p, uint32_t& pm, int& ps) {
     pm = 0;
@@ -475,19 +547,32 @@ void split_top_p(float top_p, uint32_t& pm, int& ps) {
 
 extern "C" {
 
+// the old entry points are the _ext ones with min_p = 0 and no count table: ONE launch path, ONE device body behind both
 int osg_decode_pick(osg_ctx* ctx, const float* logits, long T, long V, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
                     int64_t* tokens, long max_tokens) {
+    return osg_decode_pick_ext(ctx, logits, T, V, eos_id, state, input_ids, position_ids, tokens, max_tokens, nullptr);
+}
+
+int osg_decode_pick_ext(osg_ctx* ctx, const float* logits, long T, long V, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
+                        int64_t* tokens, long max_tokens, int* counts) {
     if (T <= 0 || V <= 0) OSG_FAIL(ctx, "osg_decode_pick: invalid shape of the logits");
     if (!logits || !state || !input_ids || !position_ids || !tokens) OSG_FAIL(ctx, "osg_decode_pick: null operand");
     if (max_tokens < 0 || max_tokens > 0x7fffffffL) OSG_FAIL(ctx, "osg_decode_pick: invalid token budget");
     hipLaunchKernelGGL(decode_pick_kernel, dim3(1), dim3(kPickThreads), 0, ctx->compute, logits + (T - 1) * V, V, eos_id, state, input_ids, position_ids,
-                       tokens, max_tokens);
+                       tokens, max_tokens, counts);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
 
 int osg_decode_sample(osg_ctx* ctx, const float* logits, long T, long V, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
                       int64_t* tokens, long max_tokens, float temperature, long top_k, float top_p, unsigned long long seed, unsigned long long draw_base) {
+    return osg_decode_sample_ext(ctx, logits, T, V, eos_id, state, input_ids, position_ids, tokens, max_tokens, temperature, top_k, top_p, seed, draw_base, 0.0f,
+                                 nullptr);
+}
+
+int osg_decode_sample_ext(osg_ctx* ctx, const float* logits, long T, long V, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
+                          int64_t* tokens, long max_tokens, float temperature, long top_k, float top_p, unsigned long long seed, unsigned long long draw_base,
+                          float min_p, int* counts) {
     if (T <= 0 || V <= 0) OSG_FAIL(ctx, "osg_decode_sample: invalid shape of the logits");
     if (V > (1L << 20)) OSG_FAIL(ctx, "osg_decode_sample: more than 2^20 logits per row");
     if (!logits || !state || !input_ids || !position_ids || !tokens) OSG_FAIL(ctx, "osg_decode_sample: null operand");
@@ -497,11 +582,12 @@ int osg_decode_sample(osg_ctx* ctx, const float* logits, long T, long V, long lo
         OSG_FAIL(ctx, "osg_decode_sample: temperature and 1 / temperature must be positive and finite");
     if (top_k < 0) OSG_FAIL(ctx, "osg_decode_sample: top_k must be >= 0");
     if (!(top_p > 0.0f) || !(top_p <= 1.0f)) OSG_FAIL(ctx, "osg_decode_sample: top_p must be in (0, 1]");
+    if (!(min_p >= 0.0f) || !(min_p <= 1.0f)) OSG_FAIL(ctx, "osg_decode_sample: min_p must be in [0, 1]");
     uint32_t pm;
     int ps;
     split_top_p(top_p, pm, ps);
     hipLaunchKernelGGL(decode_sample_kernel, dim3(1), dim3(kSampleThreads), 0, ctx->compute, logits + (T - 1) * V, V, eos_id, state, input_ids, position_ids,
-                       tokens, max_tokens, inv_t, top_k, pm, ps, seed, draw_base);
+                       tokens, max_tokens, inv_t, top_k, pm, ps, seed, draw_base, min_p_x(min_p), counts);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }
@@ -509,6 +595,13 @@ int osg_decode_sample(osg_ctx* ctx, const float* logits, long T, long V, long lo
 int osg_decode_sample_batch(osg_ctx* ctx, const float* logits, long V, int n_seq, long long eos_id, int* state, int64_t* input_ids, int64_t* position_ids,
                             int64_t* tokens, long max_tokens, float temperature, long top_k, float top_p, const unsigned long long* seeds,
                             unsigned long long draw_base) {
+    return osg_decode_sample_batch_ext(ctx, logits, V, n_seq, eos_id, state, input_ids, position_ids, tokens, max_tokens, temperature, top_k, top_p, seeds,
+                                       draw_base, 0.0f, nullptr);
+}
+
+int osg_decode_sample_batch_ext(osg_ctx* ctx, const float* logits, long V, int n_seq, long long eos_id, int* state, int64_t* input_ids,
+                                int64_t* position_ids, int64_t* tokens, long max_tokens, float temperature, long top_k, float top_p,
+                                const unsigned long long* seeds, unsigned long long draw_base, float min_p, int* counts) {
     if (V <= 0 || n_seq <= 0 || n_seq > 65535) OSG_FAIL(ctx, "osg_decode_sample_batch: invalid shape of the logits");
     if (V > (1L << 20)) OSG_FAIL(ctx, "osg_decode_sample_batch: more than 2^20 logits per row");
     if (!logits || !state || !input_ids || !position_ids || !tokens || !seeds) OSG_FAIL(ctx, "osg_decode_sample_batch: null operand");
@@ -518,11 +611,35 @@ int osg_decode_sample_batch(osg_ctx* ctx, const float* logits, long V, int n_seq
         OSG_FAIL(ctx, "osg_decode_sample_batch: temperature and 1 / temperature must be positive and finite");
     if (top_k < 0) OSG_FAIL(ctx, "osg_decode_sample_batch: top_k must be >= 0");
     if (!(top_p > 0.0f) || !(top_p <= 1.0f)) OSG_FAIL(ctx, "osg_decode_sample_batch: top_p must be in (0, 1]");
+    if (!(min_p >= 0.0f) || !(min_p <= 1.0f)) OSG_FAIL(ctx, "osg_decode_sample_batch: min_p must be in [0, 1]");
     uint32_t pm;
     int ps;
     split_top_p(top_p, pm, ps);
     hipLaunchKernelGGL(decode_sample_batch_kernel, dim3((unsigned)n_seq), dim3(kSampleThreads), 0, ctx->compute, logits, V, eos_id, state, input_ids, position_ids,
-                       tokens, max_tokens, inv_t, top_k, pm, ps, (const u64*)seeds, draw_base);
+                       tokens, max_tokens, inv_t, top_k, pm, ps, (const u64*)seeds, draw_base, min_p_x(min_p), counts);
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int osg_decode_count(osg_ctx* ctx, const int64_t* tokens, long n, int* counts, long V) {
+    if (n < 0 || V <= 0) OSG_FAIL(ctx, "osg_decode_count: invalid number of tokens or of vocabulary entries");
+    if (n == 0) return 0;
+    if (!tokens || !counts) OSG_FAIL(ctx, "osg_decode_count: null operand");
+    if ((n + 255) / 256 > 0x7fffffffL) OSG_FAIL(ctx, "osg_decode_count: too many tokens for one launch");
+    hipLaunchKernelGGL(decode_count_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->compute, tokens, n, counts, V);
+    OSG_LAUNCH_CHECK(ctx);
+    return 0;
+}
+
+int osg_decode_penalize(osg_ctx* ctx, const float* rows, long row_stride, long V, int n_seq, const int* counts, float* out, float r, float inv_r,
+                        float presence, float frequency) {
+    if (V <= 0 || n_seq <= 0 || n_seq > 65535 || row_stride < 0) OSG_FAIL(ctx, "osg_decode_penalize: invalid shape of the logits");
+    if (!rows || !counts || !out) OSG_FAIL(ctx, "osg_decode_penalize: null operand");
+    if ((((uintptr_t)rows) & 3) || (((uintptr_t)counts) & 3) || (((uintptr_t)out) & 3)) OSG_FAIL(ctx, "osg_decode_penalize: operands must be 4-byte aligned");
+    const long threads = V / 4 + 6;      // at most V / 4 whole groups, three elements before them and three behind
+    if ((threads + 255) / 256 > 0x7fffffffL) OSG_FAIL(ctx, "osg_decode_penalize: too many elements for one launch");
+    hipLaunchKernelGGL(decode_penalize_kernel, dim3((unsigned)((threads + 255) / 256), (unsigned)n_seq), dim3(256), 0, ctx->compute, rows, row_stride, V, counts,
+                       out, r, inv_r, presence, frequency);
     OSG_LAUNCH_CHECK(ctx);
     return 0;
 }

@@ -32,6 +32,7 @@ EXPORTS = [
     "osg_decode_gather", "osg_decode_blend", "osg_decode_pick", "osg_decode_sample", "osg_kv_append_at", "osg_sdpa_len",
     "osg_decode_sample_batch", "osg_kv_append_at_batch", "osg_sdpa_len_batch", "osg_rope_batch",
     "osg_sdpa_chunk", "osg_kv_append_rows_at", "osg_prefill_stage",
+    "osg_decode_count", "osg_decode_penalize", "osg_decode_pick_ext", "osg_decode_sample_ext", "osg_decode_sample_batch_ext",
     "osg_range_push", "osg_range_pop", "osg_marker_record", "osg_copy_wait_marker", "osg_timer_mark", "osg_timer_between", "osg_set_stat_sinks", "osg_group_norm_stats_nhwc", "osg_qu8_conv2d_nhwc", "osg_qu8_conv2d_nhwc_t", "osg_qu8_conv_tap_sums", "osg_qu8_gemm", "osg_qu8_lut", "osg_qu8_binary", "osg_qu8_instance_norm", "osg_qu8_instance_norm_nhwc", "osg_qu8_affine_act", "osg_qu8_norm_affine_act_nhwc", "osg_qu8_softmax_last", "osg_kdbg_read",
     "osg_tblock_tail_supported", "osg_tblock_tail", "osg_tblock_kv_pack_elems", "osg_tblock_kv_pack_jobs", "osg_tblock_pack_weight", 
 ]
@@ -147,6 +148,12 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         lib.osg_sdpa_chunk.argtypes = [vp, ci, vp, vp, vp, vp, vp, cf, cl, cl, cl, ci, ci, ci, ci, ci, cf]
         lib.osg_kv_append_rows_at.argtypes = [vp, vp, vp, vp, ci, ci, cl, ci]
         lib.osg_prefill_stage.argtypes = [vp, vp, cl, cl, cl, ci, vp, vp, vp]
+    if hasattr(lib, "osg_decode_penalize"):
+        lib.osg_decode_count.argtypes = [vp, vp, cl, vp, cl]
+        lib.osg_decode_penalize.argtypes = [vp, vp, cl, cl, ci, vp, vp, cf, cf, cf, cf]
+        lib.osg_decode_pick_ext.argtypes = [vp, vp, cl, cl, ctypes.c_longlong, vp, vp, vp, vp, cl, vp]
+        lib.osg_decode_sample_ext.argtypes = [vp, vp, cl, cl, ctypes.c_longlong, vp, vp, vp, vp, cl, cf, cl, cf, ctypes.c_ulonglong, ctypes.c_ulonglong, cf, vp]
+        lib.osg_decode_sample_batch_ext.argtypes = [vp, vp, cl, ci, ctypes.c_longlong, vp, vp, vp, vp, cl, cf, cl, cf, vp, ctypes.c_ulonglong, cf, vp]
     lib.osg_set_stat_sinks.argtypes = [vp, vp, ci, ci, ci, vp, ci, ci, ci, ci]
     lib.osg_group_norm_stats_nhwc.argtypes = [vp, vp, vp, vp, vp, ci, ctypes.c_long, ci, ci, cf, ci, vp]
     lib.osg_qu8_conv2d_nhwc.argtypes = [vp, vp, cf, ci, vp, cf, ci, vp, cf, ci, vp] + [ci] * 13
@@ -570,6 +577,55 @@ class Gpu:
         assert ids.size >= ns and pos.size >= ns and tokens.shape[0] == ns and seeds.dtype == np.uint64 and seeds.size >= ns
         self._ck(self.lib.osg_decode_sample_batch(self.ctx, logits.ptr, vv, ns, int(eos_id), state.ptr, ids.ptr, pos.ptr, tokens.ptr, tokens.shape[1],
                                                   float(temperature), int(top_k), float(top_p), seeds.ptr, int(draw_base) & (2 ** 64 - 1)))
+
+    def decode_count(self, tokens: DevBuf, counts: DevBuf, n: Optional[int] = None):
+        """osg_decode_count: counts int32 [V] += the occurrences of the first n (default: all) device tokens int64; tokens outside [0, V) are ignored"""
+        assert tokens.dtype == np.int64 and counts.dtype == np.int32
+        n = tokens.size if n is None else int(n)
+        assert 0 <= n <= tokens.size
+        self._ck(self.lib.osg_decode_count(self.ctx, tokens.ptr, n, counts.ptr, counts.size))
+
+    def decode_penalize(self, logits: DevBuf, counts: DevBuf, repetition: float = 1.0, presence: float = 0.0, frequency: float = 0.0, row: int = 0,
+                        n_seq: int = 1, out: Optional[DevBuf] = None) -> DevBuf:
+        """osg_decode_penalize (step 0 of the rule, include/osgpu.h): rows row .. row + n_seq - 1 of logits fp32 [T, V] under counts int32 [n_seq, V]
+        -> fp32 [n_seq, V]; inv_r = 1 / repetition is taken in fp32 here, as the host library takes it"""
+        t, vv = logits.shape
+        assert logits.dtype == np.float32 and counts.dtype == np.int32 and counts.size == n_seq * vv and 0 <= row and row + n_seq <= t
+        o = self._out(out, (n_seq, vv), np.float32)
+        r = np.float32(repetition)
+        with np.errstate(all="ignore"):
+            inv_r = np.float32(1.0) / r
+        self._ck(self.lib.osg_decode_penalize(self.ctx, logits.ptr + 4 * row * vv, vv, vv, n_seq, counts.ptr, o.ptr, float(r), float(inv_r), float(presence),
+                                              float(frequency)))
+        return o
+
+    def decode_pick_ext(self, logits: DevBuf, eos_id: int, state: DevBuf, ids: DevBuf, pos: DevBuf, tokens: DevBuf, counts: Optional[DevBuf] = None):
+        """osg_decode_pick_ext: decode_pick, and counts int32 [V] (or None) raised at the token it appends"""
+        t, vv = logits.shape
+        assert logits.dtype == np.float32 and state.dtype == np.int32 and state.size >= 4 and ids.dtype == pos.dtype == tokens.dtype == np.int64
+        assert counts is None or (counts.dtype == np.int32 and counts.size == vv)
+        self._ck(self.lib.osg_decode_pick_ext(self.ctx, logits.ptr, t, vv, int(eos_id), state.ptr, ids.ptr, pos.ptr, tokens.ptr, tokens.size, self._p(counts)))
+
+    def decode_sample_ext(self, logits: DevBuf, eos_id: int, state: DevBuf, ids: DevBuf, pos: DevBuf, tokens: DevBuf, temperature: float, top_k: int = 0,
+                          top_p: float = 1.0, seed: int = 0, draw_base: int = 0, min_p: float = 0.0, counts: Optional[DevBuf] = None):
+        """osg_decode_sample_ext: decode_sample plus min_p (0 = off) and counts int32 [V] (or None) raised at the token it appends"""
+        t, vv = logits.shape
+        assert logits.dtype == np.float32 and state.dtype == np.int32 and state.size >= 4 and ids.dtype == pos.dtype == tokens.dtype == np.int64
+        assert counts is None or (counts.dtype == np.int32 and counts.size == vv)
+        self._ck(self.lib.osg_decode_sample_ext(self.ctx, logits.ptr, t, vv, int(eos_id), state.ptr, ids.ptr, pos.ptr, tokens.ptr, tokens.size, float(temperature),
+                                                int(top_k), float(top_p), int(seed) & (2 ** 64 - 1), int(draw_base) & (2 ** 64 - 1), float(min_p),
+                                                self._p(counts)))
+
+    def decode_sample_batch_ext(self, logits: DevBuf, eos_id: int, state: DevBuf, ids: DevBuf, pos: DevBuf, tokens: DevBuf, seeds: DevBuf, temperature: float,
+                                top_k: int = 0, top_p: float = 1.0, draw_base: int = 0, min_p: float = 0.0, counts: Optional[DevBuf] = None):
+        """osg_decode_sample_batch_ext: decode_sample_batch plus min_p and counts int32 [n_seq, V] (or None)"""
+        ns, vv = logits.shape
+        assert logits.dtype == np.float32 and state.dtype == np.int32 and state.size >= 4 * ns and ids.dtype == pos.dtype == tokens.dtype == np.int64
+        assert ids.size >= ns and pos.size >= ns and tokens.shape[0] == ns and seeds.dtype == np.uint64 and seeds.size >= ns
+        assert counts is None or (counts.dtype == np.int32 and counts.size == ns * vv)
+        self._ck(self.lib.osg_decode_sample_batch_ext(self.ctx, logits.ptr, vv, ns, int(eos_id), state.ptr, ids.ptr, pos.ptr, tokens.ptr, tokens.shape[1],
+                                                      float(temperature), int(top_k), float(top_p), seeds.ptr, int(draw_base) & (2 ** 64 - 1), float(min_p),
+                                                      self._p(counts)))
 
     def kv_append_at_batch(self, src: DevBuf, cache: DevBuf, state: DevBuf):
         """osg_kv_append_at_batch: src f16 [B, Hkv, d] into cache [B, Hkv, CAP, d], batch b at row state[b, 0] (device int32 [B, 4]), in place"""

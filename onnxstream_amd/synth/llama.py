@@ -212,32 +212,39 @@ def forward_resident(m, cfg: LlamaConfig, input_ids, first: bool, P: int, fp16: 
 
 
 def generate(m, cfg: LlamaConfig, max_new: int, eos_id: int = -1, sync_every: int = 0, trace: bool = False, temperature: float = 0.0, top_k: int = 0,
-             top_p: float = 1.0, seed: int = 0, draw_base: int = 0):
+             top_p: float = 1.0, seed: int = 0, draw_base: int = 0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+             frequency_penalty: float = 0.0, min_p: float = 0.0, history=None):
     """The app's token loop (src/llm.cpp:472-496) on the device, after a forward_resident(..., keep_logits=True) over the prompt: greedy tokens picked and
     run through the Model's resident T = 1 plan without a host round trip per token (bindings.Model.generate).  Leaves the caches opkv* and the logits of
     the last pass in the Model, as the host loop would.  Returns (tokens, stop, logits trace [n_tokens, V] or None, device ms).
-    temperature > 0: sampled tokens instead (temperature, top_k, top_p, seed, draw_base: bindings.Model.generate)."""
+    temperature > 0: sampled tokens instead (temperature, top_k, top_p, seed, draw_base: bindings.Model.generate).
+    repetition_penalty, presence_penalty, frequency_penalty, min_p, history: bindings.Model.generate (history None = nothing)."""
     m.set_use_fp16_arithmetic(True)
     return m.generate(max_new, 2 * cfg.layers, eos_id=eos_id, sync_every=sync_every, trace=trace, temperature=temperature, top_k=top_k, top_p=top_p, seed=seed,
-                      draw_base=draw_base)
+                      draw_base=draw_base,
+                      repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p, history=history)
 
 
 def turn(m, cfg: LlamaConfig, prompt, max_new: int, chunk: int = 32, capacity: int = 0, eos_id: int = -1, sync_every: int = 0, trace: bool = False,
-         temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, draw_base: int = 0, first: bool = False):
+         temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int = 0, draw_base: int = 0, first: bool = False, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+         frequency_penalty: float = 0.0, min_p: float = 0.0, history=None):
     """One chat turn (src/llm.cpp:456-497) on the device: `prompt` in chunks of `chunk` tokens over the caches the Model holds, then the token loop of
     `generate`, in one call without a host round trip (bindings.Model.turn).  first: push the app's zero-length caches pkv* (its first turn, :400-412);
-    otherwise the opkv* a forward_resident, a generate or a turn left are carried on.  Returns (tokens, stop, logits trace or None, device ms)."""
+    otherwise the opkv* a forward_resident, a generate or a turn left are carried on.  Returns (tokens, stop, logits trace or None, device ms).
+    repetition_penalty, presence_penalty, frequency_penalty, min_p, history: bindings.Model.turn (history None = this turn's prompt)."""
     if first:
         m.set_use_fp16_arithmetic(False)
         for i in range(2 * cfg.layers):
             m.add_tensor(f"pkv{i}", np.zeros((1, cfg.kv_heads, 0, cfg.head_dim), np.float32))
     m.set_use_fp16_arithmetic(True)
     return m.turn(prompt, max_new, 2 * cfg.layers, chunk=chunk, capacity=capacity, eos_id=eos_id, sync_every=sync_every, trace=trace, vocab=cfg.vocab,
-                  temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, draw_base=draw_base)
+                  temperature=temperature, top_k=top_k, top_p=top_p, seed=seed, draw_base=draw_base,
+                  repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p, history=history)
 
 
 def generate_batch(m, cfg: LlamaConfig, n_seq: int, max_new: int, eos_id: int = -1, sync_every: int = 0, trace: bool = False, temperature: float = 1.0,
-                   top_k: int = 0, top_p: float = 1.0, seeds=None, seed: int = 0, draw_base: int = 0):
+                   top_k: int = 0, top_p: float = 1.0, seeds=None, seed: int = 0, draw_base: int = 0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                   frequency_penalty: float = 0.0, min_p: float = 0.0, history=None):
     """n_seq sampled continuations of the prompt in one call (bindings.Model.generate_batch), after a forward_resident(..., keep_logits=True) over it.  The
     sequences share every pass of one decode plan of batch n_seq; each has its seed, its caches and its stop.  seeds: one 64-bit integer per sequence; when
     None, `seed` expands to seed + s modulo 2^64.  Leaves the Model's tensors as they were.  Returns (list of token arrays, stop [n_seq], list of logits
@@ -246,7 +253,8 @@ def generate_batch(m, cfg: LlamaConfig, n_seq: int, max_new: int, eos_id: int = 
         seeds = [(int(seed) + s) % 2 ** 64 for s in range(max(int(n_seq), 0))]
     m.set_use_fp16_arithmetic(True)
     return m.generate_batch(n_seq, max_new, 2 * cfg.layers, seeds, temperature, top_k=top_k, top_p=top_p, draw_base=draw_base, eos_id=eos_id,
-                            sync_every=sync_every, trace=trace)
+                            sync_every=sync_every, trace=trace,
+                            repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, frequency_penalty=frequency_penalty, min_p=min_p, history=history)
 
 
 def configure(m, cfg: LlamaConfig, model_dir: str, sdpa: bool = False, ops_cache: bool = True, upcast: bool = False):

@@ -7,6 +7,10 @@ by that rule, then osg_decode_sample alone at V = 32000 and 128256; each option 
 --generate --sequences N[,N...] [--temperature T] [--top-k K] [--top-p P] [--seed S]: the single sampled loop (Model.generate) as the baseline, then
 Model.generate_batch with each N, 64 tokens per sequence after the 32-token prefill, all in one process: ms per pass and tokens per second
 (profiles/llm_generate_batch_probe.txt: --sequences 1,2,4,8,16 --temperature 0.8 --top-k 40 --top-p 0.9).
+--generate --penalties [--off-only] [--seed S]: the warm sampled loop (T 0.8, top_k 40, top_p 0.9) with the four controls off and with
+repetition 1.1, presence 0.2, frequency 0.1, min_p 0.05 over a 32-token history (the prompt), alternating, five calls each after one cold call: ms per
+token of every call, the range of each leg and the difference of the medians.  --off-only runs the controls-off calls alone, which a library of an older
+tree can run too (OSA_LIB_HOST names its host library, its libosgpu.so beside it): the A/B of profiles/llm_generate_penalties_probe.txt.
 --turn: two chat turns of 32 prompt tokens and 64 generated tokens each, chunk 32: Model.turn (prefill and loop on the device, one call per turn) against
 forward_resident + Model.generate on the same tokens, three conversations each way in one process: wall and device ms per turn, plans built
 (profiles/llm_turn_probe.txt)."""
@@ -139,6 +143,44 @@ def sampled_leg(rules, seed, n_new=64):
     g.close()
 
 
+def penalties_leg(seed, off_only, n_new=64, repeats=5):
+    """--generate --penalties: warm device-loop calls of n_new tokens after the 32-token prefill in one process, the controls off and on in turn; the
+    range of the controls-off calls among themselves is the noise the difference is read against."""
+    rng = np.random.default_rng(0)
+    prompt = [int(t) for t in rng.integers(0, cfg.vocab, 32)]
+    m = Model(b.LIB_HOST, 0, "ram+nocache")
+    m._set_option("hip_autotune", 0)
+    m._set_option("hip_resident_outputs", 1)
+    m.add_outputs_convert("logits")
+    llama.configure(m, cfg, d, sdpa=True, upcast=True)
+    rule = dict(temperature=0.8, top_k=40, top_p=0.9, seed=seed)
+    controls = dict(repetition_penalty=1.1, presence_penalty=0.2, frequency_penalty=0.1, min_p=0.05, history=prompt)
+
+    def leg(name, **kw):
+        m.clear_tensors()
+        llama.forward_resident(m, cfg, prompt, True, 0, keep_logits=True)
+        built = m.hip_plans_built()
+        t0 = time.perf_counter()
+        toks, stop, _, ms = llama.generate(m, cfg, n_new, **rule, **kw)
+        wall = (time.perf_counter() - t0) * 1e3
+        print(f"sampled loop, {name}: device {ms / n_new:.4f} ms/token, wall {wall / n_new:.4f} ms/token, {len(toks)} tokens ({len(set(int(t) for t in toks))} distinct), "
+              f"stop {stop}, plans built by the call {m.hip_plans_built() - built}", flush=True)
+        return ms / n_new
+
+    print(f"host library {os.path.basename(os.path.dirname(b.LIB_HOST))}/{os.path.basename(b.LIB_HOST)}", flush=True)
+    leg("controls off, cold (builds and captures the plan)")
+    off, on = [], []
+    for r in range(repeats):
+        off.append(leg(f"controls off, warm {r}"))
+        if not off_only:
+            on.append(leg(f"controls on (1.1, 0.2, 0.1, min_p 0.05, history 32), warm {r}", **controls))
+    print(f"controls off: min {min(off):.4f} median {np.median(off):.4f} max {max(off):.4f} ms/token over {repeats} calls", flush=True)
+    if on:
+        print(f"controls on:  min {min(on):.4f} median {np.median(on):.4f} max {max(on):.4f} ms/token over {repeats} calls; median on - median off "
+              f"{np.median(on) - np.median(off):+.4f} ms/token ({(np.median(on) / np.median(off) - 1) * 100:+.2f} %)", flush=True)
+    m.close()
+
+
 def batch_leg(n_list, rule, seed, n_new=64):
     """--generate --sequences ...: per N a cold call (the decode plan of batch N is built and captured) and two warm ones; before, between and after them the
     single-sequence sampled loop, whose calls among themselves show the run-to-run spread.  No sequence can stop (eos -1): every call is n_new passes."""
@@ -252,7 +294,9 @@ if "--turn" in sys.argv:
 if "--generate" in sys.argv:
     temps = _option("--temperature", None, float)
     seqs = _option("--sequences", None, int)
-    if seqs is not None:
+    if "--penalties" in sys.argv:
+        penalties_leg(_option("--seed", 0, int)[0], "--off-only" in sys.argv)
+    elif seqs is not None:
         rule = ((temps or [0.8])[0], _option("--top-k", 40, int)[0], _option("--top-p", 0.9, float)[0])
         batch_leg(seqs, rule, _option("--seed", 0, int)[0])
     elif temps is None:
