@@ -171,7 +171,7 @@ struct ConstPool {
     // capacity and the options it was built with (`decode_key`) still fit
     Plan* decode_plan = nullptr;
     std::string decode_key;
-    void drop_decode();          // (plan_run.cpp: Plan is incomplete here)
+    void drop_decode();          // (plan_llm.cpp: Plan is incomplete here)
     // the resident chunk plan beside it (Plan::turn): T = C rows of a prompt over caches of the same kind, keyed as the decode plan plus C
     Plan* prefill_plan = nullptr;
     std::string prefill_key;
@@ -201,6 +201,13 @@ inline float half_to_float(uint16_t h) {
     else v = std::ldexp((float)(man | 0x400), (int)exp - 25);
     return sign ? -v : v;
 }
+
+// Plan::in_flight from the first enqueue to the wait at the end of the scope; an exception on the way leaves it set (the plan's destructor then waits for the device)
+struct FlightGuard {
+    bool& f;
+    explicit FlightGuard(bool& f_) : f(f_) { f = true; }
+    ~FlightGuard() { if (!std::uncaught_exceptions()) f = false; }
+};
 
 struct Plan {
     Plan(Model& m, HipBackend& be, ConstPool& pool, size_t batch);
@@ -385,6 +392,24 @@ struct Plan {
     void* dec_history = nullptr;              // device int64 [n_history]: the caller's history, uploaded per call
     size_t dec_counts_bytes = 0, dec_adjusted_bytes = 0, dec_history_bytes = 0;
     int cache_index(const std::string& name, const std::string& prefix) const;   // i of "<prefix><i>", i < n_caches; -1 otherwise
+    // ---- the LLM calls (plan_llm.cpp): generate and turn below, built from the steps they share.  Members here: what both refuse (check_loop_call), the kept
+    // plan (resident_plan) and one pass of it (run_pass, plan_run.cpp, beside capture); file-local there: the plan's loop bindings, the table limits, the
+    // host-cache scratch with staging in and publishing out, the choice of pick launch ----
+    using CacheGeo = std::vector<std::array<long, 2>>;      // (Hkv, d) per cache
+    // what differs between the Model's two resident plans: the decode plan (T = 1, one sequence per sample of the batch) and the chunk plan (T = C, batch 1)
+    struct ResidentKind {
+        Plan*& slot; std::string& slot_key;       // where the ConstPool keeps it: decode_plan / decode_key, prefill_plan / prefill_key
+        long chunk;                               // DecodeSpec::chunk: 0 = T is 1; C = T is C, and the ids / pos staging starts out zeroed (padding rows)
+        long batch;                               // samples of the plan (part of the key)
+        long key_dim;                             // the key's one field of the call: V, which a decode plan's logits must have; C for a chunk plan
+        std::vector<const char*> appends;         // what the steps that append to a cache in place are called in such a plan
+        std::function<bool(long)> logits_ok;      // whether an fp32 logits output of that many elements per sample is the loop's ...
+        std::string logits_want;                  // ... and what to call it when none is
+    };
+    static Plan* resident_plan(Model& m, const std::string& fn, const DecodeSpec& names, const CacheGeo& geo, long min_cap, const ResidentKind& k);
+    void run_pass();
+    // a Tensor that owns the device buffer `dev` of `bytes` bytes (execute()'s resident outputs, the caches generate and turn publish); plan_run.cpp
+    static Tensor resident_tensor(Model& m, const std::string& name, std::vector<size_t> shape, void* dev, size_t bytes);
     // the reference app's token loop (src/llm.cpp:472-496) on the device: see model_hip_generate (exports.cpp) for the contract.  A static member of Plan
     // for the reason given at on_plan_of; the decode plan itself is kept in the Model's ConstPool.
     // how a token is taken from the logits: default-constructed = greedy, the app's argmax (osg_decode_pick); temperature > 0 = the sampling rule of
@@ -400,6 +425,9 @@ struct Plan {
         // what every call refuses, `fn` its prefix; V < 0: the vocabulary is not known yet (the history's tokens are checked once it is)
         void check(const std::string& fn, long long max_new, long V) const;
     };
+    // run_first_why: the caller's reason inside "run() once first (...)" -- generate starts from a run()'s logits and caches, a turn only needs its weights
+    static void check_loop_call(Model& m, const std::string& fn, const DecodeSpec& names, int max_new, const int64_t* tokens, const SampleRule& rule,
+                                const char* run_first_why);
     // batch (model_hip_generate_batch): n_seq sampled sequences from the one prompt in a decode plan of batch n_seq, sequence s with seeds[s] and its own
     // state, caches and stop; the outputs are arrays over the sequences and m_data is left untouched.  n_seq is part of the decode plan's key.
     // entry (Plan::turn): the loop starts from what a prefill leaves on the device instead of from m_data -- caches of P rows in capacity buffers of
@@ -408,7 +436,7 @@ struct Plan {
     // whether cache i was device-resident come with it; nothing of it is read from m_data.
     struct TurnEntry {
         long P = 0, cap = 0, V = 0, min_cap = 0;
-        std::vector<std::array<long, 2>> geo;        // (Hkv, d) per cache
+        CacheGeo geo;
         std::vector<const void*> caches;             // capacity buffers [Hkv][cap][d]
         std::vector<char> was_resident;
         std::vector<size_t> logits_shape;            // [1, T, V]: the rank to keep
